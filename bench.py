@@ -5,13 +5,19 @@ Workload (BASELINE.json configs[1]): LibriSpeech-100 char LAS, 3 x pBLSTM-256 Li
 1 x LSTM-512 Speller, additive attention, bf16 contractions, on the reference's own bucket shape
 B=48, T=1274 (tfrecord_data_loader.py:75,83), synthetic MFCC-39 cube and labels per SURVEY.md 8(d).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 With N > 1 and no WORLD_SIZE in the environment this process starts N fresh ranks itself
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...`, one rank per GPU over RCCL), relays rank 0's
 JSON line and exits with the launcher's code; under a launcher (the driver's form) it is one of the ranks.
 Every rank trains on its own 48-utterance shard (weak scaling), one flat-bucket all-reduce per step.
 
-Prints ONE JSON line (rank 0):
+A plain run sets up, warms up, times K steps and prints ONE JSON line (rank 0): metric, value, unit, higher_is_better,
+dtype, ms_per_step, the configuration and the schedule the timed steps ran.
+--dump-outputs DIR  after the timed steps, what the last of them computed as DIR/<name>.npy (float32, at most 61 MB in all;
+                    an array larger than its share is replaced by a fixed, seeded sample of its elements, <name>_sample.npy):
+                    loss, logits, alphas, params (the weights after the step's update) and a sample of its gradients.  The
+                    inputs and the initial weights are seeded: the same arguments give the same inputs in every run.
+--full              also everything else, in the same line (the --no-* options leave parts out):
   roofline      dominant kernel family (the recurrent sweep), measured live with HIP events on the launch stream, plus the
                 WHOLE-STEP algorithmic rates against the HBM and MFMA roofs (BASELINE.md section 3 per-utterance figures x utt/s)
   cpu_baseline  the oracle restatement of the reference graph AS WRITTEN (un-hoisted key projection, per-step cells) on
@@ -562,6 +568,26 @@ def parity_mode_bench(dev, a, xs, ys, steps=5, warmup=2):
         L.set_precision(a.dtype)
 
 
+# --dump-outputs: elements written per array at most (float32); beyond that a fixed, seeded sample.  Sum: 61 MB + the loss.
+DUMP_CAP = {"logits": 2 << 20, "alphas": 2 << 20, "params": 10_000_000, "grads": 1 << 20}
+
+
+def dump_outputs(path, las, st):
+    """What the last timed step returned to its caller (loss, logits [B, U, V], alignments [B, U, T']) and what it left in the store
+    (the flat parameters after its update, its gradients) as <path>/<name>.npy in float32."""
+    out = las.last_out                              # (the re-run step's result when check_status recovered a lost one)
+    arrays = (("loss", out[0]), ("logits", out[3]), ("alphas", out[4]), ("params", st.flat), ("grads", st.flat_grad))
+    os.makedirs(path, exist_ok=True)
+    for i, (name, t) in enumerate(arrays):
+        t = torch.as_tensor(t).detach()
+        cap = DUMP_CAP.get(name)
+        if cap is not None and t.numel() > cap:
+            idx = np.sort(np.random.RandomState(1000 + i).randint(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def self_launch(n, argv):
     """Run `python -m torch.distributed.run --nproc-per-node n bench.py <argv>` as a child (one rank per GPU over RCCL).
     Called before anything initialises the GPU in this process (torch.cuda.device_count() does not)."""
@@ -601,13 +627,20 @@ def main():
     ap.add_argument("--config", type=int, default=1, choices=[1, 3], help="BASELINE.json configs[] index (1 = headline, 3 = subword + location-aware)")
     ap.add_argument("--only-leg", default=None, choices=["run_sh", "run_sh_rnn", "run_sh_lstm", "config2_sampling"],
                     help="run ONE side leg alone and print its JSON object (for rocprofv3 kernel traces of that leg)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-decode", action="store_true")
-    ap.add_argument("--no-train-loop", action="store_true")
-    ap.add_argument("--no-side-legs", action="store_true", help="skip the config3 / cell_rnn / stacked objects")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline and per-phase spans of the timed steps, parity mode, side configurations, "
+                         "train loop, decode and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-decode", action="store_true", help="(--full) skip the decode leg")
+    ap.add_argument("--no-train-loop", action="store_true", help="(--full) skip the parity mode, side legs and train loop")
+    ap.add_argument("--no-side-legs", action="store_true", help="(--full) skip the config3 / cell_rnn / stacked objects")
     ap.add_argument("--decode-only", action="store_true", help="only the decode leg (BASELINE configs[4]); prints its JSON object")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.dump_outputs and (a.only_leg or a.decode_only):
+        ap.error("--dump-outputs writes the headline's outputs: not with --only-leg / --decode-only")
     if a.cpu_baseline_only:
         cpu_baseline_child(a.cell)
         return
@@ -699,10 +732,11 @@ def main():
     for _ in range(a.warmup):
         las.train(xs, ys)
     sync()
-    _hip.prof_begin()
+    if a.full:
+        _hip.prof_begin()                           # (HIP events around the phases and sweeps: the roofline / kernel_ms figures)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss = las.train(xs, ys)[0]
+        las.train(xs, ys)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     las.check_status()                              # a sweep exchange timeout would invalidate the measurement
@@ -712,7 +746,9 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax[0])
     prof = _hip.prof_end()
-    loss = float(loss)
+    loss = float(las.last_out[0])
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, las, st)
 
     if rank == 0:
         ms = elapsed / a.steps * 1e3
@@ -720,7 +756,7 @@ def main():
         G = 4 if a.cell == "lstm" else 1
         H = args.enc_units
         per = {k: (sum(v) / len(v), len(v)) for k, v in prof.items()}
-        if os.environ.get("LAS_PHASES"):            # spans of the step's phases and sweeps on the launch stream (no profiler needed)
+        if os.environ.get("LAS_PHASES"):            # (--full) spans of the step's phases and sweeps on the launch stream (no profiler needed)
             for k in sorted(per):
                 print("  %-34s %8.3f ms  x%d" % (k, per[k][0], per[k][1] // a.steps), file=sys.stderr)
         # dominant kernel = the recurrent-sweep kernel family (fwd or bwd) with the largest total time in the timed
@@ -791,6 +827,9 @@ def main():
         }
         out["scale_measured"] = world > 1           # (no multi-GPU node was available to rounds 1-3: until a line with n_gpus > 1 exists, the
                                                     #  data-parallel path is covered by gloo / RCCL-world-1 tests only)
+        if not a.full:                              # a plain run: the headline alone
+            del out["roofline"], out["kernel_ms"]
+            a.no_train_loop = a.no_decode = a.no_cpu_baseline = True
         if a.config != 1:
             a.no_train_loop = a.no_decode = a.no_cpu_baseline = True       # side legs belong to the headline configuration
         if world == 1 and a.dtype == "bf16" and a.config == 1 and not a.no_train_loop:

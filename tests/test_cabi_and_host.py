@@ -164,6 +164,32 @@ def test_bench_gpus_n_self_launch_refuses_without_enough_devices():
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_float32_within_budget_and_reproducible(tmp_path):
+    """bench.py --dump-outputs: every array float32, an oversized one replaced by the same seeded sample in every run, 64 MB at most
+    in all -- here at config 3's vocabulary (V = 5000: the logits alone are 183 MB)."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    las = types.SimpleNamespace(last_out=(torch.tensor(3.25), None, 25, torch.randn(48, 191, 5000, generator=g),
+                                          torch.rand(48, 191, 160, generator=g), {}, 1.0))
+    st = types.SimpleNamespace(flat=torch.randn(9679776, generator=g), flat_grad=torch.randn(9679776, generator=g))
+    runs = []
+    for k in range(2):
+        d = str(tmp_path / ("d%d" % k))
+        bench.dump_outputs(d, las, st)
+        runs.append({f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64e6
+    assert sorted(runs[0]) == ["alphas.npy", "grads_sample.npy", "logits_sample.npy", "loss.npy", "params.npy"]
+    for f, a in runs[0].items():
+        assert a.dtype == np.float32 and np.array_equal(a, runs[1][f]), f
+    assert float(runs[0]["loss.npy"]) == 3.25 and np.array_equal(runs[0]["params.npy"], st.flat.numpy())
+    assert runs[0]["logits_sample.npy"].size == bench.DUMP_CAP["logits"]
+    assert np.isin(runs[0]["logits_sample.npy"], las.last_out[3].numpy()).all()
+
+
 def test_sampling_seed_is_per_rank_and_per_step():
     from las.parallel import sampling_seed
     seen = {sampling_seed(s, r) for s in range(50) for r in range(8)}

@@ -19,7 +19,7 @@ def test_input_reader_under_address_and_ub_sanitizers(tmp_path):
     sys.path.insert(0, PKG)
     import tfrecord_data_loader as tdl
     exe = str(tmp_path / "input_asan")
-    cmd = [HIPCC, "--offload-host-only", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+    cmd = [HIPCC, "--offload-host-only", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-omit-frame-pointer",
            "-Wno-unused-result", os.path.join(PKG, "csrc", "input.hip"),
            os.path.join(ROOT, "tests", "native", "input_asan_main.cpp"), "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -39,6 +39,7 @@ def test_input_reader_under_address_and_ub_sanitizers(tmp_path):
     raw[3] ^= 1                                             # and the first length field for certain
     open(bad, "wb").write(raw)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
+               LSAN_OPTIONS="suppressions=" + os.path.join(ROOT, "tests", "native", "lsan_rocr.supp"),    # (the ROCm runtime's own objects)
                HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
     r = subprocess.run([exe, bad] + files, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0 and "INPUT_SANITIZER_OK" in r.stdout, (r.stdout[-1500:], r.stderr[-4000:])
