@@ -3231,63 +3231,35 @@ static int fill_dev(const las_speller_fwd_args* f, DecDev& d) {
 static int g_last_variant[2] = {0, 0};     // (process-wide: a backward pass runs on the autograd engine's thread)
 extern "C" int las_speller_last_variant(int which) { return g_last_variant[which ? 1 : 0]; }
 
-// speed mode, additive attention: the row kernels read bf16 copies of Ws / keys / encoder rows (made once per call)
-static bool bf_rows_ok(const DecDev& d) {
-    return !(d.flags & LAS_SPELLER_NO_BF_ROWS) && d.mode == LAS_ATT_ADD && (d.A % 8) == 0 && (d.Hd % 8) == 0 && d.A <= 256;
-}
-// ... and, for the common single-layer geometry, the fully prefetching variants
-static bool pf_geom_ok(const DecDev& d) {
-    return d.NL == 1 && d.D <= 512 && d.A <= 128 && d.Hd <= 512 && d.Tp <= 224 && d.E <= 1024 && (d.E % 2) == 0 && (d.D % 2) == 0 &&
-           (d.A % 8) == 0 && (d.Hd % 8) == 0;
-}
-static bool pf_rows_ok(const DecDev& d) { return !(d.flags & LAS_SPELLER_NO_PF_ROWS) && bf_rows_ok(d) && pf_geom_ok(d); }
-// ... and the whole loop in one launch: 8 groups of pn product + R row workgroups, all co-resident (one per compute unit),
-// tpw column tiles per product workgroup and kw k-steps per product wave as instantiated in the kernels
-constexpr int LOOP_TPW_F = 5, LOOP_KW_F = 3, LOOP_TPW_B = 3, LOOP_KW_B = 4;
-static bool loop_geom_ok(const DecDev& d, int ncols, int K, int tpw, int kw) {
-    const int R = cdiv(d.B, 8), pn = las_device_cus() / 8 - R;
-    // (U >= 4: a launch of the persistent grid costs ~100 us before its first step -- 256 workgroups, placement handshake -- which
-    //  30 us saved per step only repays from the fourth step on; beam search calls the step with U = 1: 141 vs 43 us, r3 decode trace)
-    return d.U >= 4 && (d.E % 4) == 0 && (d.D % 4) == 0 && (d.Hd % 4) == 0 && ((d.E + d.Hd + d.D) % 8) == 0 && (K % 8) == 0 && R <= 16 &&
-           pn >= 1 && pn + R <= 32 && pn * tpw >= cdiv(ncols, 16) && 16 * kw >= cdiv(K, 32);
-}
-static bool loop_ok(const DecDev& d, int ncols, int K, int tpw, int kw) {
-    return !(d.flags & LAS_SPELLER_NO_FUSED_STEP) && pf_rows_ok(d) && loop_geom_ok(d, ncols, K, tpw, kw);
-}
-// Location-aware attention (round 3): served by the SAME loop kernels (pf_fwd_row / pf_bwd_row with LOC = true: conv1d over the
-// previous alignment from LDS, the f . Wf term in the energies, d f / d alpha_{t-1} in the gradient loop; keys / Wf / filter gradients
-// contracted over the steps afterwards) when BOTH loops are eligible, so that forward and gradient stay in one arithmetic family
-// (bf16 row operands); otherwise the per-step fp32-operand row kernels dec_step_{fwd,bwd}_kernel<.,.,true>.
-static bool loc_loop_ok(const DecDev& d, int G) {
-    const int GD = G * d.D, I0D = d.E + d.Hd + d.D;
-    return d.mode == LAS_ATT_LOC && !(d.flags & (LAS_SPELLER_NO_PF_ROWS | LAS_SPELLER_NO_BF_ROWS | LAS_SPELLER_NO_FUSED_STEP)) &&
-           pf_geom_ok(d) && (d.A % 32) == 0 && d.C >= 1 && d.C <= 10 && d.Kc * d.C <= 4096 && cdiv(d.Tp, 8) <= RNG &&
-           cdiv(d.Tp, 16) <= RNW && bf_lds_bytes(d) <= 128 * 1024 &&     // the MFMA convs: one wave per 16-frame tile; the row state in LDS
-           loop_geom_ok(d, GD, I0D, LOOP_TPW_F, LOOP_KW_F) && loop_geom_ok(d, d.Hd + d.D, GD, LOOP_TPW_B, LOOP_KW_B);
-}
+#include "speller_plan.h"
+
 static void loop_prod_dims(LoopProd& p, int B, int ncols, int K) {
     p.KS = cdiv(K, 32); p.K = K; p.N = ncols; p.nct = cdiv(ncols, 16); p.M = B; p.R = cdiv(B, 8);
     p.pn = las_device_cus() / 8 - p.R;
 }
-static constexpr size_t LOOP_LDS_MAX = 159 * 1024;                 // a loop workgroup has its CU to itself (160 KB less the kernels' static LDS)
-template <class K> static int loop_lds_attr(K kernel) {   // the product workgroups' partial tiles need > 64 KB of dynamic LDS
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LOOP_LDS_MAX);
+// a kernel's dynamic-LDS ceiling, above the 64 KB a launch gets without asking: set once per kernel and call site
+#define LAS_LDS_ATTR(kernel, max_lds)                                                                                               \
+    do {                                                                                                                            \
+        static const int attr__ = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                                           (int)(max_lds));                                                         \
+        if (attr__) { las_set_error("hipFuncSetAttribute(%s, %d) failed: %d", #kernel, (int)(max_lds), attr__); return attr__; }   \
+    } while (0)
+#define LAS_LDS_LAUNCH(kernel, grid, block, lds, max_lds, st, ...)                                                                  \
+    do {                                                                                                                            \
+        LAS_LDS_ATTR(kernel, max_lds);                                                                                              \
+        LAS_ARG((size_t)(lds) <= (size_t)(max_lds), "%s: dynamic LDS %zu bytes > %zu", #kernel, (size_t)(lds), (size_t)(max_lds));  \
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);                                                              \
+        LAS_LAUNCHED();                                                                                                             \
+    } while (0)
+// T' -> the row kernels' frames-per-wave instantiation NE (loop_ne): fn(std::integral_constant<int, NE>) -> its return code
+template <class F> static int with_ne(int Tp, F&& fn) {
+    switch (loop_ne(Tp)) {
+    case 8:  return fn(std::integral_constant<int, 8>{});
+    case 10: return fn(std::integral_constant<int, 10>{});
+    case 12: return fn(std::integral_constant<int, 12>{});
+    default: return fn(std::integral_constant<int, 14>{});
+    }
 }
-#define LAS_LOOP_LAUNCH1(KERNEL, CELL, NE, LOC, grid, lds, st, d)                                          \
-    do {                                                                                                   \
-        static int attr__ = loop_lds_attr(KERNEL<CELL, NE, LOC>);                                          \
-        if (attr__ != 0) { las_set_error("hipFuncSetAttribute(speller loop) failed: %d", attr__); return attr__; } \
-        hipLaunchKernelGGL((KERNEL<CELL, NE, LOC>), grid, dim3(RNT), lds, st, d);                          \
-    } while (0)
-#define LAS_LOOP_LAUNCH2(KERNEL, CELL, Tp, LOC, grid, lds, st, d)                                          \
-    do {                                                                                                   \
-        if ((Tp) <= 128)      LAS_LOOP_LAUNCH1(KERNEL, CELL, 8, LOC, grid, lds, st, d);                    \
-        else if ((Tp) <= 160) LAS_LOOP_LAUNCH1(KERNEL, CELL, 10, LOC, grid, lds, st, d);                   \
-        else if ((Tp) <= 192) LAS_LOOP_LAUNCH1(KERNEL, CELL, 12, LOC, grid, lds, st, d);                   \
-        else                  LAS_LOOP_LAUNCH1(KERNEL, CELL, 14, LOC, grid, lds, st, d);                   \
-    } while (0)
-#define LAS_LOOP_LAUNCH(KERNEL, CELL, Tp, loc, grid, lds, st, d)                                           \
-    do { if (loc) LAS_LOOP_LAUNCH2(KERNEL, CELL, Tp, true, grid, lds, st, d); else LAS_LOOP_LAUNCH2(KERNEL, CELL, Tp, false, grid, lds, st, d); } while (0)
 static int make_bf_copies(DecDev& d, char* base, const BwdWs& w, hipStream_t st) {
     unsigned short* wsb = (unsigned short*)(base + w.wsbf);
     unsigned short* kb = (unsigned short*)(base + w.keysbf);
@@ -3323,61 +3295,36 @@ static int speller_fwd_impl(const las_speller_fwd_args* f, DecDev d, hipStream_t
     constexpr int G = CELL == LAS_CELL_LSTM ? 4 : 1;
     const int B = d.B, D = d.D, NL = d.NL, U = d.U, E = d.E, Hd = d.Hd, V = d.V;
     const int GD = G * D, I0D = E + Hd + D;
-    const size_t lds = row_lds_bytes(d, false);
-    LAS_ARG(lds <= 150 * 1024, "speller: row state does not fit LDS (%zu bytes)", lds);
-    if (lds > 64 * 1024) {   // location-aware attention with the reference's K = 201, C = 10: the staged filter + Wf push the carve past 64 KB
-        static int attr__ = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_step_fwd_kernel<CELL, FAST, true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        LAS_ARG(attr__ == 0, "hipFuncSetAttribute(dec_step_fwd_kernel) failed: %d", attr__);
-        LAS_ARG(d.mode == LAS_ATT_LOC, "speller: row state does not fit LDS (%zu bytes)", lds);
-    }
+    const BwdWs wl_ = bwd_layout(B, d.Tp, Hd, d.A, D, NL, E, V, U, G, d.Kc, d.C);
+    SpellerPlan p;
+    if (int rc = plan_speller<CELL, FAST>(d, false, wl_, f->ws ? f->ws_bytes : 0, p)) return rc;
+    if (p.lds_row > 64 * 1024) LAS_LDS_ATTR((dec_step_fwd_kernel<CELL, FAST, true>), 150 * 1024);
     for (int l = 0; l < NL && !f->keep_state0; ++l) {
         LAS_HIP(hipMemsetAsync(d.hs + (size_t)l * (U + 1) * B * D, 0, (size_t)B * D * sizeof(float), st));
         if (CELL == LAS_CELL_LSTM) LAS_HIP(hipMemsetAsync(d.cs + (size_t)l * (U + 1) * B * D, 0, (size_t)B * D * sizeof(float), st));
     }
     // per-step cell product: with bf16 arithmetic the weights are packed once into MFMA fragments and every
     // step runs the skinny-M kernel (M = batch rows); fp32 mode keeps the generic exact path
-    const BwdWs wl_ = bwd_layout(B, d.Tp, Hd, d.A, D, NL, E, V, U, G, d.Kc, d.C);
-    const bool skinny = FAST && f->ws && f->ws_bytes >= wl_.embp && (I0D % 8) == 0 && las_skinny_ok(B, I0D, GD, I0D, d.xin0);
+    const bool skinny = p.skinny, pf = p.family == LAS_SPELLER_RAN_PF_ROWS;
     void* packF = skinny ? (char*)f->ws + wl_.packF : nullptr;
     if (skinny) d.xbf = (unsigned short*)((char*)f->ws + wl_.xbf);
-    bool bfrows = skinny && bf_rows_ok(d);
-    bool pf = bfrows && pf_rows_ok(d);
-    bool locloop = skinny && loc_loop_ok(d, G);
-    bool loop = locloop || (pf && loop_ok(d, GD, I0D, LOOP_TPW_F, LOOP_KW_F));
-    // round 6: geometries outside the loop kernels' (the reference's run.sh recipe: two 1024-unit layers, T' = 319, location-aware) take
-    // the wide path (speller_wide.h) instead of the per-utterance fp32-operand rows
-    const bool wide = wide_selected<FAST>(d, f->ws && f->ws_bytes >= wl_.gemm, skinny, loop, pf);
-    if (wide) bfrows = pf = locloop = loop = false;
-    const size_t lds_bf = bf_lds_bytes(d);
-    if (bfrows || locloop || (wide && FAST)) {
-        if (!wide) LAS_ARG(lds_bf <= (locloop ? 128 : 64) * 1024, "speller: row state does not fit LDS (%zu bytes)", lds_bf);   // (loop launches: 96 KB attribute)
-        GEMM_OK(make_bf_copies(d, (char*)f->ws, wl_, st));
-    }
+    if (p.bf_copies) GEMM_OK(make_bf_copies(d, (char*)f->ws, wl_, st));
     if (skinny && !(d.flags & LAS_SPELLER_REUSE_PREP)) GEMM_OK(las_skinny_pack(f->cellW[0], GD, I0D, GD, 0, packF, st));
-    if (f->act_save) {   // the prefetching rows keep their attention activations for the gradient rows; any other kernel family leaves the header cleared
-        if (wide && d.mode == LAS_ATT_LOC && U > 1) {   // the wide path keeps the conv outputs f only (its own header word)
-            LAS_HIP(hipMemsetAsync(f->act_save, 0, 4, st));
-            d.actS = (unsigned*)f->act_save;
-            d.fcSave = (float*)((char*)f->act_save + act_save_f_offset(U, B, d.Tp, d.A));
-        } else if (FAST && (loop || pf) && U > 1) {
+    if (f->act_save) {   // (plan_speller: which forward families leave what in act_save)
+        if (!p.act_save || p.family == LAS_SPELLER_RAN_WIDE) LAS_HIP(hipMemsetAsync(f->act_save, 0, 4, st));
+        if (p.act_save) {
             d.actS = (unsigned*)f->act_save;
             if (d.mode == LAS_ATT_LOC) d.fcSave = (float*)((char*)f->act_save + act_save_f_offset(U, B, d.Tp, d.A));
-        } else LAS_HIP(hipMemsetAsync(f->act_save, 0, 4, st));
+        }
     }
-    g_last_variant[0] = (wide ? LAS_SPELLER_RAN_WIDE : loop ? LAS_SPELLER_RAN_LOOP : pf ? LAS_SPELLER_RAN_PF_ROWS : bfrows ? LAS_SPELLER_RAN_BF_ROWS : LAS_SPELLER_RAN_F32_ROWS) |
-                        (skinny ? LAS_SPELLER_RAN_SKINNY : 0) | (d.mode == LAS_ATT_LOC ? LAS_SPELLER_RAN_LOC : 0) |
-                        (wide && FAST && NL > 1 ? LAS_SPELLER_RAN_UPPER_SKINNY : 0);
-    LAS_ARG(!d.shared_ops || ((d.flags & LAS_SPELLER_NO_LOGITS) && pf && !loop && !wide && U == 1),
+    g_last_variant[0] = p.ran;
+    LAS_ARG(!d.shared_ops || ((d.flags & LAS_SPELLER_NO_LOGITS) && pf && U == 1),
             "speller: LAS_SPELLER_SHARED_OPERANDS is served by the search step's prefetching row kernels only (LAS_SPELLER_NO_LOGITS, U = 1)");
     if (d.flags & LAS_SPELLER_NO_LOGITS)
-        LAS_ARG(CELL == LAS_CELL_LSTM && NL == 1 && U == 1 && skinny && pf && !loop && (D % 32) == 0 && (I0D % 32) == 0 && d.step_logits,
+        LAS_ARG(CELL == LAS_CELL_LSTM && NL == 1 && U == 1 && skinny && pf && (D % 32) == 0 && (I0D % 32) == 0 && d.step_logits,
                 "speller: LAS_SPELLER_NO_LOGITS needs U = 1, one LSTM layer, speed mode with the prefetching row kernels, D and E + Hd + D multiples of 32");
-    if (loop) {   // the whole loop in one launch
-        const size_t lds_pr = (size_t)RNW * LOOP_TPW_F * 1024;       // the product workgroups' partial tiles (80 KB)
-        const size_t lds_rw = lds_bf + enc_res_bytes(d, locloop, loop_ne(d.Tp));   // row state + resident encoder slabs
-        const size_t lds_lp = lds_rw < lds_pr ? lds_pr : lds_rw;
-        LAS_ARG(lds_lp <= LOOP_LDS_MAX, "speller: the loop's row state does not fit LDS (%zu bytes)", lds_lp);
+    switch (p.family) {
+    case LAS_SPELLER_RAN_LOOP: {   // the whole loop in one launch
         loop_prod_dims(d.lp, B, GD, I0D);
         d.lp.Bp = reinterpret_cast<const u16x8_t*>(packF); d.lp.bias = f->cellb[0]; d.lp.C = nullptr; d.lp.c_step = 0; d.lp.ldc = 0;
         d.lp.gA = (unsigned long long*)((char*)f->ws + wl_.granX); d.lp.gA_row = I0D / 4;
@@ -3385,75 +3332,79 @@ static int speller_fwd_impl(const las_speller_fwd_args* f, DecDev d, hipStream_t
         d.lp.xcc = (unsigned long long*)((char*)f->ws + wl_.xccs);
         // tags of an earlier call must not match: granX, granF, (granG, granB,) xccs are one contiguous stretch -> one fill
         LAS_HIP(hipMemsetAsync((char*)f->ws + wl_.granX, 0, wl_.xccs + 256 * 8 - wl_.granX, st));
-        LAS_LOOP_LAUNCH(dec_loop_fwd_kernel, CELL, d.Tp, locloop, dim3(8 * (d.lp.pn + d.lp.R)), lds_lp, st, d);
-        LAS_LAUNCHED();
+        GEMM_OK(with_ne(d.Tp, [&](auto ne) {
+            constexpr int NE = decltype(ne)::value;
+            if (p.locloop) LAS_LDS_LAUNCH((dec_loop_fwd_kernel<CELL, NE, true>), dim3(8 * (d.lp.pn + d.lp.R)), dim3(RNT), p.lds_loop, LOOP_LDS_MAX, st, d);
+            else           LAS_LDS_LAUNCH((dec_loop_fwd_kernel<CELL, NE, false>), dim3(8 * (d.lp.pn + d.lp.R)), dim3(RNT), p.lds_loop, LOOP_LDS_MAX, st, d);
+            return 0;
+        }));
+        break;
     }
-    if (wide) GEMM_OK((wide_fwd_steps<CELL, FAST>(f, d, wl_, packF, st)));
-    for (int t = 0; t <= U && !loop && !wide; ++t) {
-        // (t == U only finishes the last cell [+ logits]: the prefetching kernel would issue a whole step's bulk loads first --
-        //  the generic bf16 row kernel loads on demand and returns after the cell; half of a beam-search step's Speller time)
-        if (pf && t == 0 && f->companion_rows && (d.flags & LAS_SPELLER_NO_LOGITS)) {
-            // beam-search step: the LM's first layer as extra workgroups of the attention-row launch
-            const LstmCellLaunch& lm = *f->companion_rows;
-            if (int rc = las_lstm_cell_check(lm)) return rc;
-            LAS_ARG(!lm.fast && !lm.x_bf16, "las_speller_fwd: companion_rows must be an exact (fast = 0) cell with fp32 rows");
-            const int nlm = (lm.H / 16) * cdiv(lm.M, 32);
-            const size_t ldsc = lds_bf > (size_t)PF_LM_LDS ? lds_bf : (size_t)PF_LM_LDS;
-            if (d.Tp <= 128)      hipLaunchKernelGGL((dec_step_fwd_pf_lm_kernel<CELL, 8>), dim3(nlm + xcd_local_grid(B, d.row_group)), dim3(RNT), ldsc, st, d, t, lm, nlm);
-            else if (d.Tp <= 160) hipLaunchKernelGGL((dec_step_fwd_pf_lm_kernel<CELL, 10>), dim3(nlm + xcd_local_grid(B, d.row_group)), dim3(RNT), ldsc, st, d, t, lm, nlm);
-            else if (d.Tp <= 192) hipLaunchKernelGGL((dec_step_fwd_pf_lm_kernel<CELL, 12>), dim3(nlm + xcd_local_grid(B, d.row_group)), dim3(RNT), ldsc, st, d, t, lm, nlm);
-            else                  hipLaunchKernelGGL((dec_step_fwd_pf_lm_kernel<CELL, 14>), dim3(nlm + xcd_local_grid(B, d.row_group)), dim3(RNT), ldsc, st, d, t, lm, nlm);
-        }
-        else if (pf && t == 0 && U == 1 && f->keep_state0 && (d.flags & LAS_SPELLER_ROWS_SHARE4) && (d.flags & LAS_SPELLER_NO_LOGITS)) {
-            // beam-search step over many rows: four hypotheses of an utterance per workgroup, shared operands read once
-            const size_t l4 = beam_rows4_lds(d);
-            static int attr4 = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_beam_rows4_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) |
-                               (int)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_beam_rows4_kernel<10>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) |
-                               (int)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_beam_rows4_kernel<12>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) |
-                               (int)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_beam_rows4_kernel<14>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            LAS_ARG(attr4 == 0 && l4 <= 128 * 1024, "speller: hipFuncSetAttribute(dec_beam_rows4_kernel) failed (%d) or the rows' state does not fit LDS (%zu)", attr4, l4);
-            LAS_ARG((B % BR4) == 0 && d.tok_in, "speller: LAS_SPELLER_ROWS_SHARE4 needs a row count that is a multiple of 4");
-            if (d.Tp <= 128)      hipLaunchKernelGGL((dec_beam_rows4_kernel<8>), dim3(xcd_local_grid(B / BR4, d.row_group / BR4)), dim3(RNT), l4, st, d);
-            else if (d.Tp <= 160) hipLaunchKernelGGL((dec_beam_rows4_kernel<10>), dim3(xcd_local_grid(B / BR4, d.row_group / BR4)), dim3(RNT), l4, st, d);
-            else if (d.Tp <= 192) hipLaunchKernelGGL((dec_beam_rows4_kernel<12>), dim3(xcd_local_grid(B / BR4, d.row_group / BR4)), dim3(RNT), l4, st, d);
-            else                  hipLaunchKernelGGL((dec_beam_rows4_kernel<14>), dim3(xcd_local_grid(B / BR4, d.row_group / BR4)), dim3(RNT), l4, st, d);
-        }
-        else if (pf && t == U)          hipLaunchKernelGGL((dec_step_fwd_bf_kernel<CELL, 1>), dim3(B), dim3(RNT), lds_bf, st, d, t);
-        else if (pf && d.Tp <= 128)     hipLaunchKernelGGL((dec_step_fwd_pf_kernel<CELL, 8>), dim3(xcd_local_grid(B, d.row_group)), dim3(RNT), lds_bf, st, d, t);
-        else if (pf && d.Tp <= 160)     hipLaunchKernelGGL((dec_step_fwd_pf_kernel<CELL, 10>), dim3(xcd_local_grid(B, d.row_group)), dim3(RNT), lds_bf, st, d, t);
-        else if (pf && d.Tp <= 192)     hipLaunchKernelGGL((dec_step_fwd_pf_kernel<CELL, 12>), dim3(xcd_local_grid(B, d.row_group)), dim3(RNT), lds_bf, st, d, t);
-        else if (pf)                    hipLaunchKernelGGL((dec_step_fwd_pf_kernel<CELL, 14>), dim3(xcd_local_grid(B, d.row_group)), dim3(RNT), lds_bf, st, d, t);
-        else if (bfrows && d.A <= 128)  hipLaunchKernelGGL((dec_step_fwd_bf_kernel<CELL, 1>), dim3(B), dim3(RNT), lds_bf, st, d, t);
-        else if (bfrows)                hipLaunchKernelGGL((dec_step_fwd_bf_kernel<CELL, 2>), dim3(B), dim3(RNT), lds_bf, st, d, t);
-        else if (d.mode == LAS_ATT_LOC) hipLaunchKernelGGL((dec_step_fwd_kernel<CELL, FAST, true>), dim3(B), dim3(RNT), lds, st, d, t);
-        else                            hipLaunchKernelGGL((dec_step_fwd_kernel<CELL, FAST, false>), dim3(B), dim3(RNT), lds, st, d, t);
-        LAS_LAUNCHED();
-        if (t == U) break;
-        if (d.flags & LAS_SPELLER_NO_LOGITS) {   // beam-search step: the cell (product + gate math) in one launch, no projection
-            LstmCellLaunch c;
-            c.x = d.xbf; c.x_bf16 = 1; c.ldx = I0D; c.I = I0D; c.ids = nullptr; c.id_shift = 0; c.xrows = nullptr; c.h = nullptr; c.ldh = 0;
-            c.Wx = packF; c.Wh = nullptr; c.bias = f->cellb[0]; c.c_prev = d.cs; c.fb = d.fb;
-            c.c_out = d.cs + (size_t)B * D; c.h_out = d.hs + (size_t)B * D; c.gates_out = d.gates; c.M = B; c.H = D; c.fast = 1; c.h_bf16 = 0; c.h_out_bf16 = nullptr;
-            if (int rc = f->companion ? las_lstm_cell_rows_launch2(c, *f->companion, st) : las_lstm_cell_rows_launch(c, st)) return rc;
-            break;
-        }
-        if (skinny) {
-            GEMM_OK(las_skinny_gemm_bf16(d.xbf, I0D, B, I0D, packF, GD, d.gates + ((size_t)0 * U + t) * B * GD, GD, f->cellb[0], st));
-        } else {
-            // (parity mode: the skinny fp32 product takes K slices when it is given scratch -- the after-loop contractions' region)
-            const bool hw = f->ws && f->ws_bytes > wl_.gemm;
-            GEMM_OK(las_gemm(f->prec, 0, 0, B, GD, I0D, 1.f, d.xin0 + (size_t)t * B * I0D, I0D, 0, f->cellW[0], GD, 0, 0.f,
-                             d.gates + ((size_t)0 * U + t) * B * GD, GD, 0, f->cellb[0], LAS_ACT_NONE, 1, 0, 0,
-                             hw ? (char*)f->ws + wl_.gemm : nullptr, hw ? f->ws_bytes - wl_.gemm : 0, st));
-        }
-        for (int l = 1; l < NL; ++l) {
-            hipLaunchKernelGGL((dec_pointwise_fwd_kernel<CELL, FAST>), dim3(B), dim3(256), 0, st, d, l - 1, t);
+    case LAS_SPELLER_RAN_WIDE:
+        GEMM_OK((wide_fwd_steps<CELL, FAST>(f, d, wl_, packF, st)));
+        break;
+    default:
+        for (int t = 0; t <= U; ++t) {
+            // (t == U only finishes the last cell [+ logits]: the prefetching kernel would issue a whole step's bulk loads first --
+            //  the generic bf16 row kernel loads on demand and returns after the cell; half of a beam-search step's Speller time)
+            const size_t lds_bf = p.lds_bf;
+            switch (pf && t == U ? LAS_SPELLER_RAN_BF_ROWS : p.family) {
+            case LAS_SPELLER_RAN_PF_ROWS:
+                if (t == 0 && f->companion_rows && (d.flags & LAS_SPELLER_NO_LOGITS)) {
+                    // beam-search step: the LM's first layer as extra workgroups of the attention-row launch
+                    const LstmCellLaunch& lm = *f->companion_rows;
+                    if (int rc = las_lstm_cell_check(lm)) return rc;
+                    LAS_ARG(!lm.fast && !lm.x_bf16, "las_speller_fwd: companion_rows must be an exact (fast = 0) cell with fp32 rows");
+                    const int nlm = (lm.H / 16) * cdiv(lm.M, 32);
+                    const size_t ldsc = lds_bf > (size_t)PF_LM_LDS ? lds_bf : (size_t)PF_LM_LDS;
+                    GEMM_OK(with_ne(d.Tp, [&](auto ne) { hipLaunchKernelGGL((dec_step_fwd_pf_lm_kernel<CELL, decltype(ne)::value>),
+                                                                   dim3(nlm + xcd_local_grid(B, d.row_group)), dim3(RNT), ldsc, st, d, t, lm, nlm); return 0; }));
+                } else if (t == 0 && U == 1 && f->keep_state0 && (d.flags & LAS_SPELLER_ROWS_SHARE4) && (d.flags & LAS_SPELLER_NO_LOGITS)) {
+                    // beam-search step over many rows: four hypotheses of an utterance per workgroup, shared operands read once
+                    LAS_ARG((B % BR4) == 0 && d.tok_in, "speller: LAS_SPELLER_ROWS_SHARE4 needs a row count that is a multiple of 4");
+                    GEMM_OK(with_ne(d.Tp, [&](auto ne) { LAS_LDS_LAUNCH((dec_beam_rows4_kernel<decltype(ne)::value>),
+                                                                        dim3(xcd_local_grid(B / BR4, d.row_group / BR4)), dim3(RNT), beam_rows4_lds(d), 128 * 1024, st, d); return 0; }));
+                } else {
+                    GEMM_OK(with_ne(d.Tp, [&](auto ne) { hipLaunchKernelGGL((dec_step_fwd_pf_kernel<CELL, decltype(ne)::value>),
+                                                                   dim3(xcd_local_grid(B, d.row_group)), dim3(RNT), lds_bf, st, d, t); return 0; }));
+                }
+                break;
+            case LAS_SPELLER_RAN_BF_ROWS:
+                if (d.A <= 128) hipLaunchKernelGGL((dec_step_fwd_bf_kernel<CELL, 1>), dim3(B), dim3(RNT), lds_bf, st, d, t);
+                else            hipLaunchKernelGGL((dec_step_fwd_bf_kernel<CELL, 2>), dim3(B), dim3(RNT), lds_bf, st, d, t);
+                break;
+            default:
+                if (d.mode == LAS_ATT_LOC) hipLaunchKernelGGL((dec_step_fwd_kernel<CELL, FAST, true>), dim3(B), dim3(RNT), p.lds_row, st, d, t);
+                else                       hipLaunchKernelGGL((dec_step_fwd_kernel<CELL, FAST, false>), dim3(B), dim3(RNT), p.lds_row, st, d, t);
+            }
             LAS_LAUNCHED();
-            float* gl = d.gates + ((size_t)l * U + t) * B * GD;
-            GEMM_OK(las_gemm(f->prec, 0, 0, B, GD, D, 1.f, d.hs + ((size_t)(l - 1) * (U + 1) + t + 1) * B * D, D, 0,
-                             f->cellW[l], GD, 0, 0.f, gl, GD, 0, f->cellb[l], LAS_ACT_NONE, 1, 0, 0, nullptr, 0, st));
-            GEMM_OK(las_gemm(f->prec, 0, 0, B, GD, D, 1.f, d.hs + ((size_t)l * (U + 1) + t) * B * D, D, 0,
-                             f->cellW[l] + (size_t)D * GD, GD, 0, 1.f, gl, GD, 0, nullptr, LAS_ACT_NONE, 1, 0, 0, nullptr, 0, st));
+            if (t == U) break;
+            if (d.flags & LAS_SPELLER_NO_LOGITS) {   // beam-search step: the cell (product + gate math) in one launch, no projection
+                LstmCellLaunch c;
+                c.x = d.xbf; c.x_bf16 = 1; c.ldx = I0D; c.I = I0D; c.ids = nullptr; c.id_shift = 0; c.xrows = nullptr; c.h = nullptr; c.ldh = 0;
+                c.Wx = packF; c.Wh = nullptr; c.bias = f->cellb[0]; c.c_prev = d.cs; c.fb = d.fb;
+                c.c_out = d.cs + (size_t)B * D; c.h_out = d.hs + (size_t)B * D; c.gates_out = d.gates; c.M = B; c.H = D; c.fast = 1; c.h_bf16 = 0; c.h_out_bf16 = nullptr;
+                if (int rc = f->companion ? las_lstm_cell_rows_launch2(c, *f->companion, st) : las_lstm_cell_rows_launch(c, st)) return rc;
+                break;
+            }
+            if (skinny) {
+                GEMM_OK(las_skinny_gemm_bf16(d.xbf, I0D, B, I0D, packF, GD, d.gates + ((size_t)0 * U + t) * B * GD, GD, f->cellb[0], st));
+            } else {
+                // (parity mode: the skinny fp32 product takes K slices when it is given scratch -- the after-loop contractions' region)
+                const bool hw = f->ws && f->ws_bytes > wl_.gemm;
+                GEMM_OK(las_gemm(f->prec, 0, 0, B, GD, I0D, 1.f, d.xin0 + (size_t)t * B * I0D, I0D, 0, f->cellW[0], GD, 0, 0.f,
+                                 d.gates + ((size_t)0 * U + t) * B * GD, GD, 0, f->cellb[0], LAS_ACT_NONE, 1, 0, 0,
+                                 hw ? (char*)f->ws + wl_.gemm : nullptr, hw ? f->ws_bytes - wl_.gemm : 0, st));
+            }
+            for (int l = 1; l < NL; ++l) {
+                hipLaunchKernelGGL((dec_pointwise_fwd_kernel<CELL, FAST>), dim3(B), dim3(256), 0, st, d, l - 1, t);
+                LAS_LAUNCHED();
+                float* gl = d.gates + ((size_t)l * U + t) * B * GD;
+                GEMM_OK(las_gemm(f->prec, 0, 0, B, GD, D, 1.f, d.hs + ((size_t)(l - 1) * (U + 1) + t + 1) * B * D, D, 0,
+                                 f->cellW[l], GD, 0, 0.f, gl, GD, 0, f->cellb[l], LAS_ACT_NONE, 1, 0, 0, nullptr, 0, st));
+                GEMM_OK(las_gemm(f->prec, 0, 0, B, GD, D, 1.f, d.hs + ((size_t)l * (U + 1) + t) * B * D, D, 0,
+                                 f->cellW[l] + (size_t)D * GD, GD, 0, 1.f, gl, GD, 0, nullptr, LAS_ACT_NONE, 1, 0, 0, nullptr, 0, st));
+            }
         }
     }
     if (d.step_logits != 1) {  // vocab projection of all steps at once (dense MFMA work): las/las.py:156-158
@@ -3492,37 +3443,18 @@ static int speller_bwd_impl(const las_speller_bwd_args* bk, DecDev d, int part, 
     float* tmp = (float*)(base + w.tmp);          // [NL][B][2D] input/recurrent grads of layers >= 1
     void* gws = base + w.gemm;
     const size_t gws_bytes = f->ws_bytes - w.gemm;
-    const size_t lds = row_lds_bytes(d, true);
-    LAS_ARG(lds <= 150 * 1024, "speller bwd: row state does not fit LDS (%zu bytes)", lds);
-    if (lds > 64 * 1024) {
-        static int attr__ = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_step_bwd_kernel<CELL, FAST, true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        LAS_ARG(attr__ == 0, "hipFuncSetAttribute(dec_step_bwd_kernel) failed: %d", attr__);
-        LAS_ARG(d.mode == LAS_ATT_LOC, "speller bwd: row state does not fit LDS (%zu bytes)", lds);
-    }
-
-    const bool skinny = FAST && (GD % 8) == 0 && las_skinny_ok(B, GD, I0D, GD, d.gates);
+    SpellerPlan p;
+    if (int rc = plan_speller<CELL, FAST>(d, true, w, f->ws_bytes, p)) return rc;
+    if (p.lds_row > 64 * 1024) LAS_LDS_ATTR((dec_step_bwd_kernel<CELL, FAST, true>), 150 * 1024);
+    const bool skinny = p.skinny, wide = p.family == LAS_SPELLER_RAN_WIDE, loop = p.family == LAS_SPELLER_RAN_LOOP;
     void* packB = base + w.packB;
     if (skinny) d.dgbf = (unsigned short*)(base + w.dgbf);
-    bool bfrows = skinny && bf_rows_ok(d);
-    bool pf = bfrows && pf_rows_ok(d);
-    bool locloop = skinny && loc_loop_ok(d, G);
-    const bool wide = wide_selected<FAST>(d, true, skinny, locloop || (pf && loop_ok(d, Hd + D, GD, LOOP_TPW_B, LOOP_KW_B)), pf);
-    if (wide) bfrows = pf = locloop = false;
-    const size_t lds_bf = bf_lds_bytes(d);
-    if (bfrows || locloop || wide) {
-        if (!wide) LAS_ARG(lds_bf <= (locloop ? 128 : 64) * 1024, "speller bwd: row state does not fit LDS (%zu bytes)", lds_bf);
-        if ((part & 1) && (FAST || !wide)) GEMM_OK(make_bf_copies(d, base, w, st));
+    if (p.family != LAS_SPELLER_RAN_F32_ROWS) {
+        if ((part & 1) && p.bf_copies) GEMM_OK(make_bf_copies(d, base, w, st));
         d.dE = (float*)(base + w.dE);
     }
-    // the whole loop in one launch: the in-loop product covers the chain columns [E, I0D) only (every product workgroup then
-    // feeds granules to the rows, which is what makes the single-buffered exchange safe); the embedding columns of dXin0 are
-    // one tall contraction after the loop (part 2)
-    const bool loop = locloop || (pf && loop_ok(d, Hd + D, GD, LOOP_TPW_B, LOOP_KW_B));
-    if (part & 1)
-        g_last_variant[1] = (wide ? LAS_SPELLER_RAN_WIDE : loop ? LAS_SPELLER_RAN_LOOP : pf ? LAS_SPELLER_RAN_PF_ROWS : bfrows ? LAS_SPELLER_RAN_BF_ROWS : LAS_SPELLER_RAN_F32_ROWS) |
-                            (skinny ? LAS_SPELLER_RAN_SKINNY : 0) | (loc ? LAS_SPELLER_RAN_LOC : 0) | (wide && FAST && NL > 1 ? LAS_SPELLER_RAN_UPPER_SKINNY : 0);
-    if ((loop || pf || (wide && loc)) && bk->f.act_save) {   // (the rows check the header: only what a forward of the same family left is used)
+    if (part & 1) g_last_variant[1] = p.ran;
+    if (p.act_save && bk->f.act_save) {   // (the rows check the header: only what a forward of the same family left is used)
         d.actS = (unsigned*)bk->f.act_save;
         if (d.mode == LAS_ATT_LOC) d.fcSave = (float*)((char*)bk->f.act_save + act_save_f_offset(U, B, Tp, A));   // f of every step: kept by the forward rows, or recomputed into the same place
     }
@@ -3543,11 +3475,11 @@ static int speller_bwd_impl(const las_speller_bwd_args* bk, DecDev d, int part, 
         GEMM_OK(las_gemm(prec, 0, 0, U * B, A, D, 1.f, d.hs + (size_t)l * (U + 1) * B * D, D, 0, d.Ws + (size_t)l * D * A, A, 0,
                          l ? 1.f : 0.f, d.Q, A, 0, nullptr, LAS_ACT_NONE, 1, 0, 0, nullptr, 0, st));
 
-    if (loop) {
-        const size_t lds_pr = (size_t)RNW * LOOP_TPW_B * 1024;
-        const size_t lds_rw = lds_bf + enc_res_bytes(d, locloop, loop_ne(Tp), true);     // row state + resident encoder frames
-        const size_t lds_lp = lds_rw < lds_pr ? lds_pr : lds_rw;
-        LAS_ARG(lds_lp <= LOOP_LDS_MAX, "speller bwd: the loop's row state does not fit LDS (%zu bytes)", lds_lp);
+    switch (p.family) {
+    case LAS_SPELLER_RAN_LOOP:
+        // the whole loop in one launch: the in-loop product covers the chain columns [E, I0D) only (every product workgroup then
+        // feeds granules to the rows, which is what makes the single-buffered exchange safe); the embedding columns of dXin0 are
+        // one tall contraction after the loop (part 2)
         loop_prod_dims(d.lp, B, Hd + D, GD);
         d.lp.Bp = reinterpret_cast<const u16x8_t*>(packB); d.lp.bias = nullptr;
         d.lp.C = d.dXin0 + E; d.lp.c_step = (long long)B * I0D; d.lp.ldc = I0D;
@@ -3555,46 +3487,57 @@ static int speller_bwd_impl(const las_speller_bwd_args* bk, DecDev d, int part, 
         d.lp.gC = (unsigned long long*)(base + w.granB); d.lp.gC_row = (Hd + D) / 2;
         d.lp.xcc = (unsigned long long*)(base + w.xccs);
         LAS_HIP(hipMemsetAsync(base + w.granG, 0, w.xccs + 256 * 8 - w.granG, st));       // granG, granB, xccs: contiguous, one fill
-        LAS_LOOP_LAUNCH(dec_loop_bwd_kernel, CELL, Tp, locloop, dim3(8 * (d.lp.pn + d.lp.R)), lds_lp, st, d);
-        LAS_LAUNCHED();
-    }
-    if (wide) GEMM_OK((wide_bwd_steps<CELL, FAST>(bk, d, w, base, packB, dHl, tmp, gws, gws_bytes, st)));
-    for (int t = U - 1; t >= -1 && !loop && !wide; --t) {
-        DecDev ds = d;
-        if (t + 1 < U) ds.rec[0] = d.dXin0 + (size_t)(t + 1) * B * I0D;
-        const int ta = (t + 1 < U) ? t + 1 : -1;
-        if (pf && Tp <= 128)      hipLaunchKernelGGL((dec_step_bwd_pf_kernel<CELL, 8>), dim3(B), dim3(RNT), lds_bf, st, ds, ta, t);
-        else if (pf && Tp <= 160) hipLaunchKernelGGL((dec_step_bwd_pf_kernel<CELL, 10>), dim3(B), dim3(RNT), lds_bf, st, ds, ta, t);
-        else if (pf && Tp <= 192) hipLaunchKernelGGL((dec_step_bwd_pf_kernel<CELL, 12>), dim3(B), dim3(RNT), lds_bf, st, ds, ta, t);
-        else if (pf)              hipLaunchKernelGGL((dec_step_bwd_pf_kernel<CELL, 14>), dim3(B), dim3(RNT), lds_bf, st, ds, ta, t);
-        else if (bfrows && A <= 128) hipLaunchKernelGGL((dec_step_bwd_bf_kernel<CELL, 1>), dim3(B), dim3(RNT), lds_bf, st, ds, (t + 1 < U) ? t + 1 : -1, t);
-        else if (bfrows) hipLaunchKernelGGL((dec_step_bwd_bf_kernel<CELL, 2>), dim3(B), dim3(RNT), lds_bf, st, ds, (t + 1 < U) ? t + 1 : -1, t);
-        else if (loc) hipLaunchKernelGGL((dec_step_bwd_kernel<CELL, FAST, true>), dim3(B), dim3(RNT), lds, st, ds, (t + 1 < U) ? t + 1 : -1, t);
-        else          hipLaunchKernelGGL((dec_step_bwd_kernel<CELL, FAST, false>), dim3(B), dim3(RNT), lds, st, ds, (t + 1 < U) ? t + 1 : -1, t);
-        LAS_LAUNCHED();
-        if (t < 0) break;
-        for (int l = TOP; l >= 0; --l) {
-            const float* dG = d.gates + ((size_t)l * U + t) * B * GD;
-            if (l == 0 && skinny) {
-                GEMM_OK(las_skinny_gemm_bf16(d.dgbf, GD, B, GD, packB, I0D, d.dXin0 + (size_t)t * B * I0D, I0D, nullptr, st));
-            } else if (l == 0) {
-                GEMM_OK(las_gemm(prec, 0, 1, B, I0D, GD, 1.f, dG, GD, 0, f->cellW[0], GD, 0, 0.f, d.dXin0 + (size_t)t * B * I0D,
-                                 I0D, 0, nullptr, LAS_ACT_NONE, 1, 0, 0, gws, gws_bytes, st));
-            } else {
-                float* tl = tmp + (size_t)l * B * 2 * D;
-                GEMM_OK(las_gemm(prec, 0, 1, B, 2 * D, GD, 1.f, dG, GD, 0, f->cellW[l], GD, 0, 0.f, tl, 2 * D, 0, nullptr,
-                                 LAS_ACT_NONE, 1, 0, 0, nullptr, 0, st));
-                hipLaunchKernelGGL((dec_pointwise_bwd_kernel<CELL, FAST>), dim3(B), dim3(256), 0, st, d, l - 1, t, (const float*)tl, 2 * D);
-                LAS_LAUNCHED();
+        GEMM_OK(with_ne(Tp, [&](auto ne) {
+            constexpr int NE = decltype(ne)::value;
+            if (p.locloop) LAS_LDS_LAUNCH((dec_loop_bwd_kernel<CELL, NE, true>), dim3(8 * (d.lp.pn + d.lp.R)), dim3(RNT), p.lds_loop, LOOP_LDS_MAX, st, d);
+            else           LAS_LDS_LAUNCH((dec_loop_bwd_kernel<CELL, NE, false>), dim3(8 * (d.lp.pn + d.lp.R)), dim3(RNT), p.lds_loop, LOOP_LDS_MAX, st, d);
+            return 0;
+        }));
+        break;
+    case LAS_SPELLER_RAN_WIDE:
+        GEMM_OK((wide_bwd_steps<CELL, FAST>(bk, d, w, base, packB, dHl, tmp, gws, gws_bytes, st)));    // (with its own keys gradient)
+        break;
+    default:
+        for (int t = U - 1; t >= -1; --t) {
+            DecDev ds = d;
+            if (t + 1 < U) ds.rec[0] = d.dXin0 + (size_t)(t + 1) * B * I0D;
+            const int ta = (t + 1 < U) ? t + 1 : -1;
+            switch (p.family) {
+            case LAS_SPELLER_RAN_PF_ROWS:
+                GEMM_OK(with_ne(Tp, [&](auto ne) { hipLaunchKernelGGL((dec_step_bwd_pf_kernel<CELL, decltype(ne)::value>), dim3(B), dim3(RNT), p.lds_bf, st, ds, ta, t); return 0; }));
+                break;
+            case LAS_SPELLER_RAN_BF_ROWS:
+                if (A <= 128) hipLaunchKernelGGL((dec_step_bwd_bf_kernel<CELL, 1>), dim3(B), dim3(RNT), p.lds_bf, st, ds, ta, t);
+                else          hipLaunchKernelGGL((dec_step_bwd_bf_kernel<CELL, 2>), dim3(B), dim3(RNT), p.lds_bf, st, ds, ta, t);
+                break;
+            default:
+                if (loc) hipLaunchKernelGGL((dec_step_bwd_kernel<CELL, FAST, true>), dim3(B), dim3(RNT), p.lds_row, st, ds, ta, t);
+                else     hipLaunchKernelGGL((dec_step_bwd_kernel<CELL, FAST, false>), dim3(B), dim3(RNT), p.lds_row, st, ds, ta, t);
+            }
+            LAS_LAUNCHED();
+            if (t < 0) break;
+            for (int l = TOP; l >= 0; --l) {
+                const float* dG = d.gates + ((size_t)l * U + t) * B * GD;
+                if (l == 0 && skinny) {
+                    GEMM_OK(las_skinny_gemm_bf16(d.dgbf, GD, B, GD, packB, I0D, d.dXin0 + (size_t)t * B * I0D, I0D, nullptr, st));
+                } else if (l == 0) {
+                    GEMM_OK(las_gemm(prec, 0, 1, B, I0D, GD, 1.f, dG, GD, 0, f->cellW[0], GD, 0, 0.f, d.dXin0 + (size_t)t * B * I0D,
+                                     I0D, 0, nullptr, LAS_ACT_NONE, 1, 0, 0, gws, gws_bytes, st));
+                } else {
+                    float* tl = tmp + (size_t)l * B * 2 * D;
+                    GEMM_OK(las_gemm(prec, 0, 1, B, 2 * D, GD, 1.f, dG, GD, 0, f->cellW[l], GD, 0, 0.f, tl, 2 * D, 0, nullptr,
+                                     LAS_ACT_NONE, 1, 0, 0, nullptr, 0, st));
+                    hipLaunchKernelGGL((dec_pointwise_bwd_kernel<CELL, FAST>), dim3(B), dim3(256), 0, st, d, l - 1, t, (const float*)tl, 2 * D);
+                    LAS_LAUNCHED();
+                }
             }
         }
     }
 
-    if (wide) {}    // (wide_bwd_steps ran its own keys kernel)
-    else if (locloop) {  // keys gradient with the conv term in the pre-activation; the same pass leaves the Wf-gradient partials
+    if (p.locloop) {  // keys gradient with the conv term in the pre-activation; the same pass leaves the Wf-gradient partials
         hipLaunchKernelGGL(dkeys_loc_kernel, dim3(cdiv(Tp, 8), B), dim3(256), 0, st, d, bk->d_keys);
         LAS_LAUNCHED();
-    } else if (bfrows) {   // keys gradient: contraction over the steps, every (utterance, frame) independent
+    } else if (!wide && p.family != LAS_SPELLER_RAN_F32_ROWS) {   // keys gradient: contraction over the steps, every (utterance, frame) independent
         hipLaunchKernelGGL(dkeys_kernel, dim3(cdiv(Tp, 8), B), dim3(256), 0, st, d, bk->d_keys);
         LAS_LAUNCHED();
     }
@@ -3630,16 +3573,10 @@ static int speller_bwd_impl(const las_speller_bwd_args* bk, DecDev d, int part, 
         int* estart = (int*)(base + w.embp);
         int* epos = estart + V + 1;
         // (the token list / the histogram in LDS: up to 96 / 68 KB at the limits -- above the 64 KB a launch gets without asking)
-        static int attr_h = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(emb_hist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (EMB_MAX_V + 1024) * (int)sizeof(int));
-        static int attr_p = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(emb_place_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (EMB_MAX_N + 264) * (int)sizeof(unsigned short));
-        LAS_ARG(attr_h == 0 && attr_p == 0, "hipFuncSetAttribute(emb_*_kernel) failed: %d %d", attr_h, attr_p);
-        hipLaunchKernelGGL(emb_hist_kernel, dim3(1), dim3(1024), (size_t)(V + 1024) * sizeof(int), st, (const int*)d.tok_in, UB, V, estart);
-        LAS_LAUNCHED();
-        hipLaunchKernelGGL(emb_place_kernel, dim3(cdiv(UB, 256)), dim3(256), (size_t)((UB + 263) & ~7) * sizeof(unsigned short), st,
-                           (const int*)d.tok_in, UB, V, (const int*)estart, epos);
-        LAS_LAUNCHED();
+        LAS_LDS_LAUNCH(emb_hist_kernel, dim3(1), dim3(1024), (size_t)(V + 1024) * sizeof(int), (EMB_MAX_V + 1024) * sizeof(int), st,
+                       (const int*)d.tok_in, UB, V, estart);
+        LAS_LDS_LAUNCH(emb_place_kernel, dim3(cdiv(UB, 256)), dim3(256), (size_t)((UB + 263) & ~7) * sizeof(unsigned short),
+                       (EMB_MAX_N + 264) * sizeof(unsigned short), st, (const int*)d.tok_in, UB, V, (const int*)estart, epos);
         hipLaunchKernelGGL(emb_reduce_kernel, dim3(V), dim3(1024), 0, st, (const int*)estart, (const int*)epos, (const float*)d.dXin0, I0D, E,
                            (const float*)d.emb_mask, bk->demb);
         LAS_LAUNCHED();
@@ -3651,7 +3588,7 @@ static int speller_bwd_impl(const las_speller_bwd_args* bk, DecDev d, int part, 
         GEMM_OK(las_colsum(epart, EMB_CHUNKS, V * E, V * E, 1.f, bk->demb, gws, gws_bytes, st));
     }
     bool loc_rows = loc;                           // the per-utterance rows dlocwRows / dlocbRows hold the filter / bias gradient
-    if (locloop || (wide && loc)) {  // filter / bias gradient from the saved d f rows of every step
+    if (p.locloop || (wide && loc)) {  // filter / bias gradient from the saved d f rows of every step
         const int nks = (Tp + 31) / 32, nmt = (d.Kc + 15) / 16;
         const size_t lds = (size_t)(((nks * 32 + 16 * nmt + 8 + 3) & ~3) + 16 * (nks * 32 + 4) + 256) * sizeof(float);
         if (nmt <= 16 && lds <= 64 * 1024) {

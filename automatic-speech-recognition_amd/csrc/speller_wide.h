@@ -1163,7 +1163,3 @@ static void wide_fill(const DecDev& d, WideDev& w, char* base, const WideWs& L) 
     w.xu = (unsigned short*)(base + L.xu); w.dqbf = (unsigned short*)(base + L.dqbf); w.dgu = (unsigned short*)(base + L.dgu);
     w.dS = (float*)(base + L.dS); w.dWfW = (float*)(base + L.dWfW); w.egran = (unsigned long long*)(base + L.egran); w.bgran = (unsigned long long*)(base + L.bgran);
 }
-template <class K> static int wide_lds_attr(K kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return 0;
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}

@@ -45,66 +45,28 @@ def synthetic_batch(B, T, U_max, V, seed=0, feat_dim=13, min_frac=0.5):
     return (audio, audiolen), (y, tokenlen)
 
 
-def loc_loop_eligible(args, B, Tp, U, cell="lstm", cus=256):
-    """mirror of csrc/speller.hip loc_loop_ok: location-aware attention runs in the one-launch loop kernels (bf16 row operands)
-    when both the decode loop and the gradient loop are eligible, else in the per-step fp32-operand row kernels"""
-    if args.mode != "loc" or B is None or Tp is None or U is None:
-        return False
-    G = 4 if cell == "lstm" else 1
-    D, A, E = args.dec_units, args.attention_size, args.embedding_size
-    Hd = 2 * args.enc_units if str(args.enc_type).lower() == "pblstm" else args.enc_units
-    GD, I0D, C, Kc = G * D, E + Hd + D, args.loc_num_channels, args.loc_kernel_size
-    cd = lambda a, b: -(-a // b)
-    geom = (args.num_dec_layers == 1 and D <= 512 and A <= 128 and Hd <= 512 and Tp <= 224 and E <= 1024 and E % 2 == 0 and D % 2 == 0
-            and A % 32 == 0 and Hd % 8 == 0 and 1 <= C <= 10 and Kc * C <= 4096 and cd(Tp, 8) <= 32)
-    R = cd(B, 8)
-    pn = cus // 8 - R
-
-    def loop(ncols, K, tpw, kw):
-        return (U >= 4 and E % 4 == 0 and D % 4 == 0 and Hd % 4 == 0 and I0D % 8 == 0 and K % 8 == 0 and R <= 16 and pn >= 1
-                and pn + R <= 32 and pn * tpw >= cd(ncols, 16) and 16 * kw >= cd(K, 32))
-    # the MFMA convs: (channel, u step) pairs of the transposed conv per wave, frame tiles per wave, and the row state in 128 KB of LDS
-    u4, u16 = (lambda x: (x + 3) // 4 * 4), (lambda x: (x + 15) // 16 * 16)
-    apad, dpad, wld = u16(Tp) + cd(Kc, 32) * 32 + 16, u16(Tp) + cd(Kc + 15, 32) * 32 + 16, 16 + cd(Kc + 15, 32) * 32
-    lds = (u4(D) + u4(A) + 2 * u4(Tp) + u4(D) + u4(Hd) + 64 +
-           u4(apad) + u4(Tp) + u4(Tp * C) + u4(dpad * C) + u4(C * wld) + u4(C * A) + u4(8 * A) + cd(Kc, 32) * 512 +
-           max(16 * max(Hd, 2 * A), 16 * 256, 16 * 2 * A + u16(Tp) * (A // 2))) * 4 + 64
-    conv = cd(Tp, 16) <= 16 and lds <= 128 * 1024
-    return bool(geom and conv and I0D % 8 == 0 and GD % 8 == 0 and B <= 1024 and loop(GD, I0D, 5, 3) and loop(Hd + D, GD, 3, 4))
+def row_mode(fam):
+    """The oracle's row arithmetic for what the library reports it ran (_hip.speller_last_variant()): the fp32-operand rows keep
+    query / keys / context operands in fp32 ('f32'); the loop, the prefetching and generic bf16 rows and the wide path round them to
+    bf16 ('bf').  A forward and a backward of different families still share one rounding mode (csrc/speller.hip plan_speller)."""
+    modes = {k: "f32" if "f32_rows" in fam[k] else "bf" for k in ("fwd", "bwd")}
+    assert modes["fwd"] == modes["bwd"], fam
+    return modes["fwd"]
 
 
-def wide_eligible(args, U, forced=False):
-    """mirror of csrc/speller_wide_host.h wide_selected (speed mode): multi-layer and location-aware training calls (U >= 2, workspace
-    given) outside the one-launch loop kernels' geometry run the wide per-step path, whose arithmetic is the loop kernels' ('bf' rows);
-    `forced`: LAS_SPELLER_WIDE is set (every call whose geometry allows it)"""
-    if U is None or U < 2:
-        return False
-    D, A, E = args.dec_units, args.attention_size, args.embedding_size
-    Hd = 2 * args.enc_units if str(args.enc_type).lower() == "pblstm" else args.enc_units
-    if A % 8 or Hd % 8 or D % 8 or E % 8 or A > 256:
-        return False
-    if args.mode == "loc" and not (1 <= args.loc_num_channels <= 16):
-        return False
-    return bool(forced or args.num_dec_layers >= 2 or args.mode == "loc")
-
-
-def oracle_mode_for(args, prec, B=None, Tp=None, U=None, cell="lstm"):
-    """The oracle arithmetic mode that restates what the HIP path runs for this configuration (oracle.set_precision):
-    speed mode rounds every contraction operand to bf16; with additive attention the Speller row kernels also keep
-    keys / context operands in bf16 ('bf' rows) -- and so do the loop kernels that serve location-aware attention when the call
-    is eligible for them (B, Tp, U given: loc_loop_eligible); otherwise only the GEMM operands are rounded ('f32' rows)."""
+def oracle_mode_for(args, prec, rows=None):
+    """The oracle arithmetic mode that restates what the HIP path runs (oracle.set_precision): speed mode rounds every contraction
+    operand to bf16; the Speller's row operands follow `rows` (row_mode of the families the library reported for the step).  Without
+    it -- the U = 1 search paths, which neither the loop kernels nor the wide path take -- additive attention runs the bf16 rows."""
     if prec != "bf16":
         return ("f32", "bf", False)
-    I0D = args.embedding_size + (2 * args.enc_units if str(args.enc_type).lower() == "pblstm" else args.enc_units) + args.dec_units
-    hd = 2 * args.enc_units if str(args.enc_type).lower() == "pblstm" else args.enc_units
-    from las import _hip
-    forced = bool(_hip.speller_flags & _hip.SPELLER_WIDE)
-    no_wide = bool(_hip.speller_flags & _hip.SPELLER_NO_WIDE)
-    bf_rows = (args.mode == "add" and I0D % 8 == 0 and args.attention_size % 8 == 0 and hd % 8 == 0) or \
-        loc_loop_eligible(args, B, Tp, U, cell) or (not no_wide and wide_eligible(args, U, forced))
+    if rows is None:
+        I0D = args.embedding_size + (2 * args.enc_units if str(args.enc_type).lower() == "pblstm" else args.enc_units) + args.dec_units
+        hd = 2 * args.enc_units if str(args.enc_type).lower() == "pblstm" else args.enc_units
+        rows = "bf" if (args.mode == "add" and I0D % 8 == 0 and args.attention_size % 8 == 0 and hd % 8 == 0) else "f32"
     # the listener keeps its activations in HBM as bf16 when the MFMA sweeps serve the hidden size
     store = args.enc_units in (64, 128, 256, 512)
-    return ("bf16", "bf" if bf_rows else "f32", store)
+    return ("bf16", rows, store)
 
 
 def encoder_frames(args, T):
@@ -115,25 +77,16 @@ def encoder_frames(args, T):
 
 
 def train_step_pair(args, cell, prec, xs, ys, seed=11, coins=None, sampled=None, enc_type="pblstm", oracle_dtype=None):
-    """One LAS.train step through the C ABI on cuda and the oracle's train_step in the matching arithmetic mode, on
-    identical weights / inputs.  Returns a dict of both sides' loss, logits, alphas, gradients, updated parameters."""
+    """One LAS.train step through the C ABI on cuda and the oracle's train_step in the matching arithmetic mode (the row mode of
+    the Speller families the step ran), on identical weights / inputs.  Returns a dict of both sides' loss, logits, alphas,
+    gradients, updated parameters."""
     import torch
+    from las import _hip
     from las import layers as L
     from las import variables as V
     from las.las import LAS, Listener, Speller
     from oracle import las_oracle as O
     p0 = O.init_params(args, seed=seed, cell=cell, enc_type=enc_type)
-    mode = oracle_mode_for(args, prec, B=len(xs[1]), Tp=encoder_frames(args, np.shape(xs[0])[1]), U=int(np.max(ys[1])), cell=cell)
-    O.set_precision(*mode)
-    try:
-        po = O.to_torch(p0, requires_grad=True)
-        zeros = {k: torch.zeros_like(v) for k, v in po.items()}
-        loss_o, logits_o, alphas_o, g_o, newp, _, _ = O.train_step(
-            po, zeros, {k: torch.zeros_like(v) for k, v in po.items()}, 0,
-            (torch.tensor(xs[0]), xs[1]), (torch.tensor(ys[0]), ys[1]), args, cell, coins=coins,
-            sampled=None if sampled is None else torch.tensor(sampled))
-    finally:
-        O.set_precision("f32")
     L.set_cell(cell)
     L.set_precision(prec)
     st = V.reset_default_store(device="cuda")
@@ -147,11 +100,22 @@ def train_step_pair(args, cell, prec, xs, ys, seed=11, coins=None, sampled=None,
         # what train() returned belongs to the lost attempt, the parity statement is about the step that was applied
         print("train_step_pair: the step was lost and re-run (%d)" % las.recovered_steps)
         loss, _, gs, logits, alphas, summ, rate = las.last_out
+    fam = _hip.speller_last_variant()
     grads = {n: st.vars[n].grad.detach().cpu() for n in st.order}
     params = {n: st.vars[n].detach().cpu() for n in st.order}
+    O.set_precision(*oracle_mode_for(args, prec, rows=row_mode(fam)))
+    try:
+        po = O.to_torch(p0, requires_grad=True)
+        zeros = {k: torch.zeros_like(v) for k, v in po.items()}
+        loss_o, logits_o, alphas_o, g_o, newp, _, _ = O.train_step(
+            po, zeros, {k: torch.zeros_like(v) for k, v in po.items()}, 0,
+            (torch.tensor(xs[0]), xs[1]), (torch.tensor(ys[0]), ys[1]), args, cell, coins=coins,
+            sampled=None if sampled is None else torch.tensor(sampled))
+    finally:
+        O.set_precision("f32")
     return dict(loss_o=float(loss_o), loss=float(loss), logits_o=logits_o, logits=logits.cpu(), alphas_o=alphas_o,
                 alphas=alphas.cpu(), g_o=g_o, grads=grads, newp=newp, params=params, names=sorted(p0), gs=gs, las=las,
-                tokens_in=las.speller.last_tokens_in.cpu())
+                tokens_in=las.speller.last_tokens_in.cpu(), fam=fam)
 
 
 def hip_step(args, cell, prec, xs, ys, seed=11, coins=None, sampled=None, enc_type="pblstm", seq_flags=0):

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import make_args
+from helpers import make_args, row_mode
 
 pytestmark = pytest.mark.gpu
 
@@ -41,17 +41,17 @@ def _run(flags, NL, D, A, Hd2, B, Tp, U, mixed, loc=None):
             sampled = rng.randint(3, 30, size=(B, U)).astype(np.int32)
         w = torch.tensor(rng.randn(B, U, 30).astype(np.float32))
         logits, _, alphas = sp(enc, enc_len, U, teacher=y, is_training=True, coins=coins, sampled=sampled)
+        fam = _hip.speller_last_variant()
         (logits * w.cuda()).sum().backward()
         _hip.join_side_stream()
         torch.cuda.synchronize()
+        fam["bwd"] = _hip.speller_last_variant()["bwd"]
         st = V.default_store()
         grads = {n: st.vars[n].grad.detach().cpu().clone() for n in st.order}
         grads["enc"] = enc.grad.detach().cpu().clone()
-        # oracle, bf16-operand mode; fp32-operand rows (flag 2) keep query / keys / context in fp32
+        # oracle, bf16-operand mode; fp32-operand rows keep query / keys / context in fp32
         p0 = {n: st.vars[n].detach().cpu().numpy() for n in st.order}
-        from helpers import loc_loop_eligible, wide_eligible
-        bf_rows = not (flags & 2) and (loc is None or loc_loop_eligible(args, B, Tp, U) or wide_eligible(args, U))
-        O.set_precision("bf16", "bf" if bf_rows else "f32")
+        O.set_precision("bf16", row_mode(fam))
         try:
             po = O.to_torch(p0, requires_grad=True)
             enc_o = torch.tensor(enc_np, requires_grad=True)
@@ -62,7 +62,7 @@ def _run(flags, NL, D, A, Hd2, B, Tp, U, mixed, loc=None):
             O.set_precision("f32")
         go = {n: po[n].grad for n in po if po[n].grad is not None}
         go["enc"] = enc_o.grad
-        return logits.detach().cpu(), alphas.detach().cpu(), grads, lo.detach(), ao.detach(), go
+        return logits.detach().cpu(), alphas.detach().cpu(), grads, lo.detach(), ao.detach(), go, fam
     finally:
         _hip.speller_flags = 0
 
@@ -93,7 +93,11 @@ SHAPES = [
 @pytest.mark.parametrize("shape", SHAPES)
 def test_bf16_row_kernels_match_oracle(shape, flags):
     NL, D, A, H, B, Tp, U, mixed = shape
-    ln, an, gn, lo, ao, go = _run(flags, NL, D, A, H, B, Tp, U, mixed)
+    ln, an, gn, lo, ao, go, fam = _run(flags, NL, D, A, H, B, Tp, U, mixed)
+    for k in ("fwd", "bwd"):       # what the switches turn off (the families they select: tests/test_gpu_speller_families.py)
+        assert flags != 2 or "f32_rows" in fam[k], fam
+        assert flags != 1 or not {"pf_rows", "loop"} & set(fam[k]), fam
+        assert flags != 4 or "loop" not in fam[k], fam
     assert (an - ao).abs().max().item() < 2e-3
     assert (an.sum(-1) - 1).abs().max().item() < 1e-4
     assert (ln - lo).abs().max().item() < 5e-3 * max(1.0, lo.abs().max().item())
@@ -107,7 +111,7 @@ def test_bf16_row_kernels_match_oracle(shape, flags):
 def test_embedding_gradient_buckets_with_more_than_32k_positions():
     """The embedding gradient's token buckets (emb_hist / emb_place / emb_reduce) keep the token list in LDS: at B U = 35,200
     positions that is more than the 64 KB a launch gets without asking (a stacked B = 192 step has 36,672)."""
-    ln, an, gn, lo, ao, go = _run(0, 1, 64, 32, 32, 176, 20, 200, False)
+    ln, an, gn, lo, ao, go, fam = _run(0, 1, 64, 32, 32, 176, 20, 200, False)
     n = "embedding/embedding_matrix"
     scale = max(go[n].abs().max().item(), 1e-3)
     assert (gn[n] - go[n]).abs().max().item() / scale < 2e-2
@@ -130,9 +134,9 @@ def test_location_aware_loop_kernels_match_oracle(shape):
     d alpha_{t-1} in the gradient loop; keys / Wf / filter gradients contracted after the loop by dkeys_loc_kernel / dlocw_kernel)
     against the oracle's LocationAwareAttention (reference las/layers.py:259-311) in its bf16-row mode: logits, alignments, every
     gradient including conv1d/kernel, conv1d/bias and dense_2/kernel."""
-    from helpers import loc_loop_eligible
     D, A, H, B, Tp, U, mixed, loc = shape
-    ln, an, gn, lo, ao, go = _run(0, 1, D, A, H, B, Tp, U, mixed, loc=loc)
+    ln, an, gn, lo, ao, go, fam = _run(0, 1, D, A, H, B, Tp, U, mixed, loc=loc)
+    assert "loop" in fam["fwd"] and "loop" in fam["bwd"], fam
     assert (an - ao).abs().max().item() < 2e-3
     assert (ln - lo).abs().max().item() < 5e-3 * max(1.0, lo.abs().max().item())
     for n in sorted(go):
@@ -152,10 +156,10 @@ def test_location_aware_gradient_loop_with_and_without_the_saved_activations(sha
     from las import las as LL
     D, A, H, B, Tp, U, mixed, loc = shape
     assert LL.SAVE_ACTIVATIONS, "the default is to save"
-    ln, an, gn, lo, ao, go = _run(0, 1, D, A, H, B, Tp, U, mixed, loc=loc)
+    ln, an, gn, lo, ao, go, fam = _run(0, 1, D, A, H, B, Tp, U, mixed, loc=loc)
     LL.SAVE_ACTIVATIONS = False
     try:
-        ln2, an2, gn2, _, _, _ = _run(0, 1, D, A, H, B, Tp, U, mixed, loc=loc)
+        ln2, an2, gn2, _, _, _, _ = _run(0, 1, D, A, H, B, Tp, U, mixed, loc=loc)
     finally:
         LL.SAVE_ACTIVATIONS = True
     assert torch.equal(ln, ln2) and torch.equal(an, an2)

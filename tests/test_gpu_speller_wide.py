@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import make_args, wide_eligible
+from helpers import make_args, row_mode
 
 pytestmark = pytest.mark.gpu
 
@@ -62,8 +62,7 @@ def _run(flags, prec, cell, NL, D, A, Hd, E, B, Tp, U, mixed, loc=None, V=30, dr
         if not oracle:
             return dict(logits=logits.detach().cpu(), alphas=alphas.detach().cpu(), grads=grads, fam=fam)
         if prec == "bf16":
-            wide = not (flags & _hip.SPELLER_NO_WIDE) and wide_eligible(args, U, bool(flags & _hip.SPELLER_WIDE))
-            O.set_precision("bf16", "bf" if (wide or args.mode == "add") else "f32")
+            O.set_precision("bf16", row_mode(fam))
         try:
             po = O.to_torch(p0, requires_grad=True)
             enc_o = torch.tensor(enc_np, requires_grad=True)
@@ -178,7 +177,7 @@ def test_wide_path_equals_the_per_utterance_rows_in_parity_mode(shape):
     cell, NL, D, A, Hd, E, B, Tp, U, mixed, loc = shape
     a = _run(_hip.SPELLER_WIDE, "f32", cell, NL, D, A, Hd, E, B, Tp, U, mixed, loc=loc)
     b = _run(_hip.SPELLER_NO_WIDE, "f32", cell, NL, D, A, Hd, E, B, Tp, U, mixed, loc=loc)
-    assert "wide" in a["fam"]["fwd"] and "wide" not in b["fam"]["fwd"]
+    assert "wide" in a["fam"]["fwd"] and "wide" in a["fam"]["bwd"] and "wide" not in b["fam"]["fwd"] and "wide" not in b["fam"]["bwd"], (a["fam"], b["fam"])
     assert (a["logits"] - b["logits"]).abs().max().item() < 2e-5 and (a["alphas"] - b["alphas"]).abs().max().item() < 2e-6
     for n in a["grads"]:
         scale = max(b["grads"][n].abs().max().item(), 1e-3)
@@ -223,7 +222,7 @@ def test_wide_path_with_embedding_dropout_and_variational_noise_equals_the_per_u
     a = _run(_hip.SPELLER_WIDE, "f32", cell, NL, D, A, Hd, E, B, Tp, U, mixed, loc=loc, dropout=dropout, add_vn=add_vn, oracle=False)
     b = _run(_hip.SPELLER_NO_WIDE, "f32", cell, NL, D, A, Hd, E, B, Tp, U, mixed, loc=loc, dropout=dropout, add_vn=add_vn, oracle=False)
     c = _run(_hip.SPELLER_NO_WIDE, "f32", cell, NL, D, A, Hd, E, B, Tp, U, mixed, loc=loc, oracle=False)
-    assert "wide" in a["fam"]["fwd"] and "wide" not in b["fam"]["fwd"]
+    assert "wide" in a["fam"]["fwd"] and "wide" in a["fam"]["bwd"] and "wide" not in b["fam"]["fwd"] and "wide" not in b["fam"]["bwd"], (a["fam"], b["fam"])
     assert (a["logits"] - b["logits"]).abs().max().item() < 2e-5 and (a["alphas"] - b["alphas"]).abs().max().item() < 2e-6
     assert (b["logits"] - c["logits"]).abs().max().item() > 1e-3           # (the masks / the noise really were applied)
     for n in a["grads"]:
