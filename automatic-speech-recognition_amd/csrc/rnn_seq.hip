@@ -301,37 +301,37 @@ struct RnnCfg {
     static constexpr int DP_BYTES = 2 * 16 * LDG * 2;
     static constexpr int RFB = cmin(NFB, RCAP);
     static constexpr int LFB = cmax(0, cmin(NFB - RFB, (150 * 1024 - DP_BYTES) / 4096));
-    static constexpr int FWD_LDS = HS_BYTES + 4 * LF * 1024;      // for RT = 1; RT > 1 requires LF == 0 / LFB == 0
+    static constexpr int FWD_LDS = HS_BYTES + 4 * LF * 1024;      // the plain kernels' dynamic LDS
     static constexpr int BWD_LDS = DP_BYTES + 4 * LFB * 1024;
     static constexpr int GPM_F = 16 * UPM / 2;        // granules one member publishes per step, forward
     static constexpr int GPM_B = 16 * G * UPM / 2;    // ... backward
     static constexpr bool OK = (UT % P == 0) && (RF + LF == NFW) && (RFB + LFB == NFB);
 };
 
-template <int CELL, int UT, int P, int RT>
-__global__ __launch_bounds__(256 * RT, 1) void rnn_seq_fwd_bf16_kernel(RnnArgs a) {
+template <int CELL, int UT, int P>
+__global__ __launch_bounds__(256, 1) void rnn_seq_fwd_bf16_kernel(RnnArgs a) {
     using C = RnnCfg<CELL, UT, P>;
     constexpr int G = C::G, H = C::H, GH = C::GH, KS = C::KS, NFW = C::NFW, LDH = C::LDH, LF = C::LF, RF = C::RF;
     constexpr int UTP = C::UTP, UPM = C::UPM, GPM = C::GPM_F;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // RT row tiles (16 batch rows each) share this workgroup as independent wave groups: 4 waves per row tile,
-    // RT waves per SIMD -> the SIMD always has another chain's instructions to issue while one waits
+    // rt = threadIdx.x >> 8 is always 0 (256 threads).  It stays in the tile index and the h tile's address because the compiler's
+    // register allocation of this kernel and of rnn_seq_bwd_bf16_kernel depends on it: the wave-uniform form spills more in the BPTT one.
     const int rt = threadIdx.x >> 8;
-    unsigned short* hs = reinterpret_cast<unsigned short*>(smem + rt * C::HS_BYTES);   // [2][16][LDH] per row tile
-    u16x8_t* wl = reinterpret_cast<u16x8_t*>(smem + RT * C::HS_BYTES);          // [4][LF][64] shared by the row tiles
+    unsigned short* hs = reinterpret_cast<unsigned short*>(smem + rt * C::HS_BYTES);   // [2][16][LDH]
+    u16x8_t* wl = reinterpret_cast<u16x8_t*>(smem + C::HS_BYTES);               // [4][LF][64]
     const int tid = threadIdx.x & 255, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
     const int T = a.T, B = a.B;
-    const int cg = blockIdx.x % a.ncl_pad, pm = blockIdx.x / a.ncl_pad;         // (tile group, direction), member
+    const int cg = blockIdx.x % a.ncl_pad, pm = blockIdx.x / a.ncl_pad;         // (row tile, direction), member
     if (cg >= a.ncl) return;
-    const int dir = cg & 1, tile = (cg >> 1) * RT + rt, b0 = tile * 16;
-    if (b0 >= B) return;                         // surplus row-tile group: terminated waves leave the barrier count
+    const int dir = cg & 1, tile = (cg >> 1) + rt, b0 = tile * 16;
+    if (b0 >= B) return;
     const int cl = tile * 2 + dir;
     const int vw = pm * 4 + w;                                                   // virtual wave: owns units [vw*16*UTP, ..)
     const u16x8_t* __restrict__ Wp = reinterpret_cast<const u16x8_t*>(a.wpack) + ((size_t)dir * 4 * P + vw) * NFW * 64;
     unsigned long long* xb = a.xbuf + (size_t)cl * 2 * P * GPM;                 // [2 slots][P][GPM]
     const __amdgpu_buffer_rsrc_t xrs = granule_rsrc(xb);
     int errflag = 0;
-    const bool local = (P > 1 && RT == 1 && !a.force_agent) ? cluster_same_xcd(a.xcc + (size_t)cl * P, pm, P, tid, &errflag, a.spin) : false;
+    const bool local = (P > 1 && !a.force_agent) ? cluster_same_xcd(a.xcc + (size_t)cl * P, pm, P, tid, &errflag, a.spin) : false;
 
     u16x8_t wreg[RF > 0 ? RF : 1];
 #pragma unroll
@@ -1014,27 +1014,27 @@ __global__ __launch_bounds__(512, 1) void rnn_seq_fwd_hw_kernel(RnnArgs a) {
     if (errflag) { if (a.err) a.err[0] = 1; if (a.status) a.status[0] = a.status_code; }
 }
 
-template <int CELL, int UT, int P, int RT>
-__global__ __launch_bounds__(256 * RT, 1) void rnn_seq_bwd_bf16_kernel(RnnArgs a) {
+template <int CELL, int UT, int P>
+__global__ __launch_bounds__(256, 1) void rnn_seq_bwd_bf16_kernel(RnnArgs a) {
     using C = RnnCfg<CELL, UT, P>;
     constexpr int G = C::G, H = C::H, GH = C::GH, KSB = C::KSB, NFB = C::NFB, LDG = C::LDG, LFB = C::LFB, RFB = C::RFB;
     constexpr int UTP = C::UTP, UPM = C::UPM, GPM = C::GPM_B;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int rt = threadIdx.x >> 8;
-    unsigned short* dps = reinterpret_cast<unsigned short*>(smem + rt * C::DP_BYTES);  // [2][16][LDG] per row tile
-    u16x8_t* wl = reinterpret_cast<u16x8_t*>(smem + RT * C::DP_BYTES);          // [4][LFB][64]
+    const int rt = threadIdx.x >> 8;                                             // always 0: see rnn_seq_fwd_bf16_kernel
+    unsigned short* dps = reinterpret_cast<unsigned short*>(smem + rt * C::DP_BYTES);  // [2][16][LDG]
+    u16x8_t* wl = reinterpret_cast<u16x8_t*>(smem + C::DP_BYTES);               // [4][LFB][64]
     const int tid = threadIdx.x & 255, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
     const int T = a.T, B = a.B;
     const int cg = blockIdx.x % a.ncl_pad, pm = blockIdx.x / a.ncl_pad;
     if (cg >= a.ncl) return;
-    const int dir = cg & 1, tile = (cg >> 1) * RT + rt, b0 = tile * 16;
+    const int dir = cg & 1, tile = (cg >> 1) + rt, b0 = tile * 16;
     if (b0 >= B) return;
     const int cl = tile * 2 + dir;
     const int vw = pm * 4 + w;
     const u16x8_t* __restrict__ Wp = reinterpret_cast<const u16x8_t*>(a.wpack) + ((size_t)dir * 4 * P + vw) * NFB * 64;
     unsigned long long* xb = a.xbuf + (size_t)cl * 2 * P * GPM;
     int errflag = 0;
-    const bool local = (P > 1 && RT == 1 && !a.force_agent) ? cluster_same_xcd(a.xcc + (size_t)cl * P, pm, P, tid, &errflag, a.spin) : false;
+    const bool local = (P > 1 && !a.force_agent) ? cluster_same_xcd(a.xcc + (size_t)cl * P, pm, P, tid, &errflag, a.spin) : false;
 
     u16x8_t wreg[RFB > 0 ? RFB : 1];
 #pragma unroll
@@ -1773,141 +1773,152 @@ static int set_lds(K kern, int bytes) {
     return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-// which kernels can sweep 8-row tiles (lane-compacted duplicate MFMA rows)
-template <int CELL, int UT, int P>
-static constexpr bool rb8_ok(bool bwd) {
-    if constexpr (P > 1) return bwd ? KsCfg<CELL, UT, P, 8>::OK : HwCfg<CELL, UT, P, 8>::OK;
-    else return false;
+// How a sweep runs (plan_sweep).  The 8-row kernels compact duplicated MFMA rows; of the sweep's modes, the helper-wave kernels alone
+// wait for x-projection chunks, FWD_HW8_RAGGED alone honours row_T, BWD_KS8_CH / _CH_PG alone wait for dout chunks (and publish progress).
+enum SweepPath { SWEEP_BF16, SWEEP_MF32, SWEEP_VALU };       // clustered bf16 MFMA / clustered exact-fp32 MFMA (rnn_seq_f32.hip) / round-1 VALU
+enum SweepKernel { SWEEP_NONE, FWD_PLAIN, FWD_HW16, FWD_HW8, FWD_HW8_RAGGED, BWD_PLAIN, BWD_KS16, BWD_KS8, BWD_KS8_CH, BWD_KS8_CH_PG };
+enum { SWEEP_ROWS = 1, SWEEP_CHUNKS = 2, SWEEP_PROGRESS = 4 };  // plan_sweep's `mode`: what the call asks of its kernel
+enum { PACK_FWD = 0, PACK_BWD = 1, PACK_KS = 2 };                // W_hh pack layouts (= SeqPrepJob::kind)
+struct SweepInst;
+struct SweepPlan {
+    int path;                // SweepPath; the rest describes SWEEP_BF16
+    const SweepInst* inst;   // the kernels of the width that runs (nullptr: none at the picked width or any narrower one)
+    int P;                   // cluster width
+    int rb;                  // batch rows per tile (8 or 16)
+    int kernel;              // SweepKernel
+    int pack;                // PACK_*
+    bool warm;               // warmer workgroups, in every launch that leaves room for them
+    int max_tiles;           // row tiles per launch (a larger batch is swept in row chunks)
+    bool x_chunks;           // las_rnn_seq_fwd_chunks_ok
+    bool rows;               // las_rnn_seq_fwd_rows_ok
+    bool dout_chunks;        // las_rnn_seq_bwd_chunks_ok
+    int progress_words;      // las_rnn_seq_bwd_progress_words
+};
+
+// One launch of KERN with LDS bytes of dynamic LDS.  KERN is a template argument so that the attribute is set once per kernel (every
+// sweep kernel has the type void(RnnArgs): a static keyed on the type alone would be shared by all of them).
+template <void (*KERN)(RnnArgs), int LDS>
+static int launch_kernel(dim3 grid, int threads, const RnnArgs& a, hipStream_t st) {
+    static const int attr = set_lds(KERN, LDS);
+    if (attr != 0) { las_set_error("rnn_seq: hipFuncSetAttribute failed: %d", attr); return attr; }
+    hipLaunchKernelGGL(KERN, grid, dim3(threads), LDS, st, a);
+    return 0;
 }
 
-template <int CELL, int UT, int P, int RT>
-static int launch_bf16_rt(bool bwd, const RnnArgs& a0, int ntiles, hipStream_t st) {
+// the plain kernels keep W_hh resident: an instantiation that cannot instantiates nothing
+template <int CELL, int UT, int P>
+static constexpr bool inst_ok() {
     using C = RnnCfg<CELL, UT, P>;
-    constexpr int FL = RT * C::HS_BYTES + 4 * C::LF * 1024, BL = RT * C::DP_BYTES + 4 * C::LFB * 1024;
-    if constexpr (!C::OK || FL > 160 * 1024 || BL > 160 * 1024) {
-        las_set_error("rnn_seq: cluster width %d / %d row tiles cannot keep W_hh resident for H=%d", P, RT, C::H);
-        return -2;
-    } else {
-        RnnArgs a = a0;
-        if (a.rb == 8 && !rb8_ok<CELL, UT, P>(bwd)) { las_set_error("rnn_seq: no 8-row kernel for this configuration"); return -1; }
-        a.ncl = cdiv(ntiles, RT) * 2;                      // (tile group, direction) pairs
-        a.ncl_pad = (a.ncl + 7) / 8 * 8;                   // members of a cluster share blockIdx % 8 (same XCD: speed only)
-        if ((long long)a.ncl_pad * P > las_device_cus()) {     // every member must be co-resident (1 workgroup per CU)
-            las_set_error("rnn_seq: %d workgroups exceed the %d compute units of this device", a.ncl_pad * P, las_device_cus());
-            return -2;
-        }
-        dim3 grid(a.ncl_pad * P), blk(256 * RT);
-        // one more workgroup per cluster (same XCD) that keeps the operands of the next steps in that XCD's L2
-        const bool warm = P > 1 && a.warm && (long long)a.ncl_pad * (P + 1) <= las_device_cus();
-        const dim3 gridw(a.ncl_pad * (P + (warm ? 1 : 0)));
-        a.warm = warm ? 1 : 0;
-        if (!bwd && RT == 1 && a.rb == 8) {
-            if constexpr (HwCfg<CELL, UT, P, 8>::OK) {
-                constexpr int HL = ks_lds(HwCfg<CELL, UT, P, 8>::LDS);    // (the CU to itself, as for the K-split BPTT kernel: 67 KB used,
-                                                                          //  198 registers x 8 waves -- a 64 KB / 110-register GEMM workgroup fits next to it)
-                static int attr = set_lds(rnn_seq_fwd_hw_kernel<CELL, UT, P, 8>, HL);
-                if (attr != 0) { las_set_error("hipFuncSetAttribute(fwd hw) failed: %d", attr); return attr; }
-                if (a.row_T) {
-                    static int attr2 = set_lds(rnn_seq_fwd_hw_kernel<CELL, UT, P, 8, true>, HL);
-                    if (attr2 != 0) { las_set_error("hipFuncSetAttribute(fwd hw, ragged) failed: %d", attr2); return attr2; }
-                    hipLaunchKernelGGL((rnn_seq_fwd_hw_kernel<CELL, UT, P, 8, true>), gridw, dim3(512), HL, st, a);
-                } else
-                hipLaunchKernelGGL((rnn_seq_fwd_hw_kernel<CELL, UT, P, 8>), gridw, dim3(512), HL, st, a);
-            }
-        } else if (!bwd && RT == 1 && HwCfg<CELL, UT, P>::OK && !a0.no_helpers) {
-            if constexpr (HwCfg<CELL, UT, P>::OK) {
-                constexpr int HL = ks_lds(HwCfg<CELL, UT, P>::LDS);
-                static int attr = set_lds(rnn_seq_fwd_hw_kernel<CELL, UT, P, 16>, HL);
-                if (attr != 0) { las_set_error("hipFuncSetAttribute(fwd hw) failed: %d", attr); return attr; }
-                hipLaunchKernelGGL((rnn_seq_fwd_hw_kernel<CELL, UT, P, 16>), gridw, dim3(512), HL, st, a);
-            }
-        } else if (!bwd) {
-            static int attr = set_lds(rnn_seq_fwd_bf16_kernel<CELL, UT, P, RT>, FL);
-            if (attr != 0) { las_set_error("hipFuncSetAttribute(fwd) failed: %d", attr); return attr; }
-            hipLaunchKernelGGL((rnn_seq_fwd_bf16_kernel<CELL, UT, P, RT>), grid, blk, FL, st, a);
-        } else if (P > 1 && KsCfg<CELL, UT, P>::OK && a.ks_packed) {
-            if constexpr (P > 1 && KsCfg<CELL, UT, P>::OK) {
-                // The K-split kernel keeps its weights in registers and needs 9-17 KB of LDS and half of the register file: other
-                // kernels' workgroups (the side stream's weight-gradient GEMMs) WOULD be scheduled onto the same CU and share its
-                // SIMDs, LDS and L1 with the dependent chain.  Asking for (nearly) the whole LDS keeps the CU to the sweep (ks_lds).
-                if (a.rb == 8 && a.dflag && a.prog) {
-                    constexpr int KZ = ks_lds(KsCfg<CELL, UT, P, 8>::DZ_BYTES);
-                    static int attr = set_lds(rnn_seq_bwd_ks_kernel<CELL, UT, P, 8, true, true>, KZ);
-                    if (attr != 0) { las_set_error("hipFuncSetAttribute(bwd ks) failed: %d", attr); return attr; }
-                    hipLaunchKernelGGL((rnn_seq_bwd_ks_kernel<CELL, UT, P, 8, true, true>), grid, dim3(256), KZ, st, a);
-                } else if (a.rb == 8 && a.dflag) {
-                    constexpr int KZ = ks_lds(KsCfg<CELL, UT, P, 8>::DZ_BYTES);
-                    static int attr = set_lds(rnn_seq_bwd_ks_kernel<CELL, UT, P, 8, true>, KZ);
-                    if (attr != 0) { las_set_error("hipFuncSetAttribute(bwd ks) failed: %d", attr); return attr; }
-                    hipLaunchKernelGGL((rnn_seq_bwd_ks_kernel<CELL, UT, P, 8, true>), grid, dim3(256), KZ, st, a);
-                } else if (a.rb == 8) {
-                    constexpr int KZ = ks_lds(KsCfg<CELL, UT, P, 8>::DZ_BYTES);
-                    static int attr = set_lds(rnn_seq_bwd_ks_kernel<CELL, UT, P, 8>, KZ);
-                    if (attr != 0) { las_set_error("hipFuncSetAttribute(bwd ks) failed: %d", attr); return attr; }
-                    hipLaunchKernelGGL((rnn_seq_bwd_ks_kernel<CELL, UT, P, 8>), grid, dim3(256), KZ, st, a);
-                } else {
-                    constexpr int KZ = ks_lds(KsCfg<CELL, UT, P, 16>::DZ_BYTES);
-                    static int attr = set_lds(rnn_seq_bwd_ks_kernel<CELL, UT, P, 16>, KZ);
-                    if (attr != 0) { las_set_error("hipFuncSetAttribute(bwd ks) failed: %d", attr); return attr; }
-                    hipLaunchKernelGGL((rnn_seq_bwd_ks_kernel<CELL, UT, P, 16>), grid, dim3(256), KZ, st, a);
-                }
-            }
-        } else {
-            static int attr = set_lds(rnn_seq_bwd_bf16_kernel<CELL, UT, P, RT>, BL);
-            if (attr != 0) { las_set_error("hipFuncSetAttribute(bwd) failed: %d", attr); return attr; }
-            hipLaunchKernelGGL((rnn_seq_bwd_bf16_kernel<CELL, UT, P, RT>), grid, blk, BL, st, a);
-        }
-        return 0;
-    }
+    return C::OK && C::FWD_LDS <= 160 * 1024 && C::BWD_LDS <= 160 * 1024;
 }
 
-// row tiles per workgroup: as many waves per SIMD as registers and LDS allow (measured per configuration)
-static int pick_rt(int cell, int H, int P, bool bwd, int ntiles) {
-    // measured on MI355X: extra row-tile waves on the same CU lose (the step is bound by the CU's MFMA +
-    // transcendental issue rate, not by latency) -> one row tile per workgroup, tiles spread over CUs
-    int rt = 1;
-    (void)cell; (void)H; (void)P; (void)bwd;
-    return rt < ntiles ? rt : (ntiles < 1 ? 1 : ntiles);
-}
-
+// The planned kernel of one (cell, H / 64, P): a.ncl_pad clusters of P members, the helper-wave kernels with a.warm warmers per cluster.
+// The K-split and helper-wave kernels keep their weights in registers and use a fraction of the LDS, but other kernels' workgroups (the
+// side stream's weight-gradient GEMMs) WOULD be scheduled onto the same CU and share its SIMDs, LDS and L1 with the dependent chain:
+// asking for (nearly) the whole LDS keeps the CU to the sweep (ks_lds).
 template <int CELL, int UT, int P>
-static int launch_bf16(bool bwd, const RnnArgs& a, hipStream_t st, bool query) {
-    if (query) {       // bit 0: an 8-row-tile kernel exists for the direction; bit 1: the forward helper-wave kernel exists for 16-row tiles
-        int r = rb8_ok<CELL, UT, P>(bwd) ? 1 : 0;
-        if constexpr (P > 1) r |= (!bwd && HwCfg<CELL, UT, P, 16>::OK) ? 2 : 0;
-        return r;                                                   // (bwd: bit 0 also means the chunk-aware K-split variant exists)
+static int launch_inst(const SweepPlan& p, const RnnArgs& a, hipStream_t st) {
+    const dim3 grid(a.ncl_pad * P), gridw(a.ncl_pad * (P + a.warm));
+    if constexpr (inst_ok<CELL, UT, P>()) {
+        using C = RnnCfg<CELL, UT, P>;
+        if constexpr (HwCfg<CELL, UT, P, 8>::OK) {
+            constexpr int L = ks_lds(HwCfg<CELL, UT, P, 8>::LDS);
+            if (p.kernel == FWD_HW8) return launch_kernel<rnn_seq_fwd_hw_kernel<CELL, UT, P, 8>, L>(gridw, 512, a, st);
+            if (p.kernel == FWD_HW8_RAGGED) return launch_kernel<rnn_seq_fwd_hw_kernel<CELL, UT, P, 8, true>, L>(gridw, 512, a, st);
+        }
+        if constexpr (HwCfg<CELL, UT, P, 16>::OK)
+            if (p.kernel == FWD_HW16) return launch_kernel<rnn_seq_fwd_hw_kernel<CELL, UT, P, 16>, ks_lds(HwCfg<CELL, UT, P, 16>::LDS)>(gridw, 512, a, st);
+        if (p.kernel == FWD_PLAIN) return launch_kernel<rnn_seq_fwd_bf16_kernel<CELL, UT, P>, C::FWD_LDS>(grid, 256, a, st);
+        if constexpr (P > 1 && KsCfg<CELL, UT, P>::OK) {
+            constexpr int L8 = ks_lds(KsCfg<CELL, UT, P, 8>::DZ_BYTES), L16 = ks_lds(KsCfg<CELL, UT, P, 16>::DZ_BYTES);
+            if (p.kernel == BWD_KS8_CH_PG) return launch_kernel<rnn_seq_bwd_ks_kernel<CELL, UT, P, 8, true, true>, L8>(grid, 256, a, st);
+            if (p.kernel == BWD_KS8_CH) return launch_kernel<rnn_seq_bwd_ks_kernel<CELL, UT, P, 8, true>, L8>(grid, 256, a, st);
+            if (p.kernel == BWD_KS8) return launch_kernel<rnn_seq_bwd_ks_kernel<CELL, UT, P, 8>, L8>(grid, 256, a, st);
+            if (p.kernel == BWD_KS16) return launch_kernel<rnn_seq_bwd_ks_kernel<CELL, UT, P, 16>, L16>(grid, 256, a, st);
+        }
+        if (p.kernel == BWD_PLAIN) return launch_kernel<rnn_seq_bwd_bf16_kernel<CELL, UT, P>, C::BWD_LDS>(grid, 256, a, st);
     }
-    const int ntiles = cdiv(a.B, a.rb);
-    int rt = pick_rt(CELL, UT * 64, P, bwd, ntiles);
-    for (; rt >= 1; --rt) {
-        int rc;
-        rc = launch_bf16_rt<CELL, UT, P, 1>(bwd, a, ntiles, st);
-        if (rc != -2) return rc;
-    }
-    return -2;
+    las_set_error("rnn_seq: kernel %d is not instantiated for cell=%d H=%d P=%d", p.kernel, CELL, UT * 64, P);
+    return -1;
 }
 
-// query = true: 1 if this configuration has an 8-row-tile kernel for the direction, else 0 (nothing is launched)
-static int dispatch_bf16(int cell, int P, bool bwd, const RnnArgs& a, hipStream_t st, bool query = false) {
-    const int key = (cell == LAS_CELL_LSTM ? 1000 : 0) + (a.H / 64) * 10 + P;
-    switch (key) {
-        case 1011: return launch_bf16<LAS_CELL_LSTM, 1, 1>(bwd, a, st, query);
-        case 1021: return launch_bf16<LAS_CELL_LSTM, 2, 1>(bwd, a, st, query);
-        case 1022: return launch_bf16<LAS_CELL_LSTM, 2, 2>(bwd, a, st, query);
-        case 1042: return launch_bf16<LAS_CELL_LSTM, 4, 2>(bwd, a, st, query);
-        case 1044: return launch_bf16<LAS_CELL_LSTM, 4, 4>(bwd, a, st, query);
-        case 1088: return launch_bf16<LAS_CELL_LSTM, 8, 8>(bwd, a, st, query);
-        case 11:   return launch_bf16<LAS_CELL_RNN, 1, 1>(bwd, a, st, query);
-        case 21:   return launch_bf16<LAS_CELL_RNN, 2, 1>(bwd, a, st, query);
-        case 41:   return launch_bf16<LAS_CELL_RNN, 4, 1>(bwd, a, st, query);
-        case 42:   return launch_bf16<LAS_CELL_RNN, 4, 2>(bwd, a, st, query);
-        case 82:   return launch_bf16<LAS_CELL_RNN, 8, 2>(bwd, a, st, query);
-        case 84:   return launch_bf16<LAS_CELL_RNN, 8, 4>(bwd, a, st, query);
-        default:
-            if (query) return 0;
-            las_set_error("rnn_seq: no bf16 kernel for cell=%d H=%d P=%d", cell, a.H, P);
-            return -2;
+// The instantiated widths and what their kernels can do: the forward helper-wave kernels for 16- / 8-row tiles, the K-split BPTT kernels
+// (for either row tile: KsCfg::OK does not depend on it).
+struct SweepInst {
+    int cell, H, P;
+    bool ok, hw16, hw8, ks;
+    int (*launch)(const SweepPlan&, const RnnArgs&, hipStream_t);
+};
+template <int CELL, int UT, int P>
+static constexpr SweepInst sweep_inst() {
+    constexpr bool ok = inst_ok<CELL, UT, P>();
+    return {CELL, UT * 64, P, ok, ok && HwCfg<CELL, UT, P, 16>::OK, ok && HwCfg<CELL, UT, P, 8>::OK, ok && P > 1 && KsCfg<CELL, UT, P>::OK,
+            launch_inst<CELL, UT, P>};
+}
+static constexpr SweepInst SWEEP_INSTS[] = {
+    sweep_inst<LAS_CELL_LSTM, 1, 1>(), sweep_inst<LAS_CELL_LSTM, 2, 1>(), sweep_inst<LAS_CELL_LSTM, 2, 2>(),
+    sweep_inst<LAS_CELL_LSTM, 4, 2>(), sweep_inst<LAS_CELL_LSTM, 4, 4>(), sweep_inst<LAS_CELL_LSTM, 8, 8>(),
+    sweep_inst<LAS_CELL_RNN, 1, 1>(),  sweep_inst<LAS_CELL_RNN, 2, 1>(),  sweep_inst<LAS_CELL_RNN, 4, 1>(),
+    sweep_inst<LAS_CELL_RNN, 4, 2>(),  sweep_inst<LAS_CELL_RNN, 8, 2>(),  sweep_inst<LAS_CELL_RNN, 8, 4>(),
+};
+
+// The chunks' producers run WHILE the sweep holds its compute units (whole CUs: 159 KB of LDS each): the hand-over only makes sense
+// while the sweep -- clusters + warmers -- leaves at least half of the machine to them.  r4, B = 144 / 192 at H = 256 (180 / 240 of 256
+// CUs): the x-projection chunks crawl on the few free CUs, 52 ms per step instead of 26 / the sweep runs into its chunk-wait bound.
+static bool handover_room(int B, int rows_per_tile, int P) {
+    const int ncl_pad = (cdiv(B, rows_per_tile) * 2 + 7) / 8 * 8;
+    return (long long)ncl_pad * (P + 1) * 2 <= las_device_cus();
+}
+
+// The one place that decides how a sweep of (cell, prec, B, H, flags) runs in either direction -- path, cluster width, row tile,
+// kernel, pack, warmers, tiles per launch -- and what it serves: a chunked, ragged or progress-publishing call is correct only on the
+// kernel that honours its mode, so the queries and the calls' checks read the same plan as the launch.  `mode` (SWEEP_ROWS /
+// _CHUNKS / _PROGRESS) picks that kernel's variant for a call; nothing else depends on it.
+static SweepPlan plan_sweep(int cell, int prec, int B, int H, int flags, bool bwd, int mode = 0) {
+    SweepPlan p{};
+    if (prec != LAS_PREC_BF16 || !mfma_shape_ok(H)) {
+        p.path = prec == LAS_PREC_F32 && !(flags & LAS_SEQ_F32_VALU) && las_rnn_seq_mf32_ok(cell, H) ? SWEEP_MF32 : SWEEP_VALU;
+        return p;
     }
+    p.path = SWEEP_BF16;
+    const int cus = las_device_cus();
+    // pick_cluster's width, or the next narrower one that has kernels and room for one cluster per direction
+    for (int P = pick_cluster(cell, H, flags); P >= 1 && !p.inst; P >>= 1)
+        for (const SweepInst& k : SWEEP_INSTS)
+            if (k.cell == cell && k.H == H && k.P == P && k.ok && cus / P / 8 >= 1) p.inst = &k;
+    if (!p.inst) return p;
+    const SweepInst& k = *p.inst;
+    p.P = k.P;
+    p.max_tiles = (cus / p.P / 8) * 8 / 2;      // clusters (tile, direction) are padded to a multiple of 8 workgroups per member
+    // 8-row tiles (twice the CUs, half the per-lane work of a dependent step) while the whole batch still fits one launch
+    const bool fit8 = B > 0 && cdiv(B, 8) <= p.max_tiles && !(flags & LAS_SEQ_ROWS16);
+    if (!bwd) {
+        const bool helpers = !(flags & LAS_SEQ_NO_HELPER_WAVES);
+        p.rb = helpers && k.hw8 && fit8 ? 8 : 16;
+        p.kernel = p.rb == 8 ? FWD_HW8 : helpers && k.hw16 ? FWD_HW16 : FWD_PLAIN;
+        p.pack = PACK_FWD;
+    } else {
+        const bool ks = k.ks && !(flags & LAS_SEQ_NO_KSPLIT);
+        p.rb = ks && fit8 ? 8 : 16;
+        p.kernel = !ks ? BWD_PLAIN : p.rb == 8 ? BWD_KS8 : BWD_KS16;
+        p.pack = ks ? PACK_KS : PACK_BWD;
+    }
+    p.warm = p.P > 1 && !(flags & LAS_SEQ_NO_WARMERS);
+    const bool room = B > 0 && cdiv(B, p.rb) <= p.max_tiles && handover_room(B, p.rb, p.P);     // one launch, with room beside it
+    p.x_chunks = p.P > 1 && (p.kernel == FWD_HW8 || p.kernel == FWD_HW16) && room;
+    p.rows = p.kernel == FWD_HW8;
+    p.dout_chunks = p.kernel == BWD_KS8 && room;
+    p.progress_words = p.dout_chunks ? 2 * cdiv(B, 8) * p.P : 0;          // one per cluster member
+    if (p.kernel == FWD_HW8 && (mode & SWEEP_ROWS)) p.kernel = FWD_HW8_RAGGED;
+    if (p.kernel == BWD_KS8 && (mode & SWEEP_CHUNKS)) p.kernel = (mode & SWEEP_PROGRESS) ? BWD_KS8_CH_PG : BWD_KS8_CH;
+    return p;
+}
+
+extern "C" int las_rnn_seq_fwd_chunks_ok(int cell, int prec, int B, int H, int flags) { return plan_sweep(cell, prec, B, H, flags, false).x_chunks; }
+extern "C" int las_rnn_seq_fwd_rows_ok(int cell, int prec, int B, int H, int flags) { return plan_sweep(cell, prec, B, H, flags, false).rows; }
+extern "C" int las_rnn_seq_bwd_chunks_ok(int cell, int prec, int B, int H, int flags) { return plan_sweep(cell, prec, B, H, flags, true).dout_chunks; }
+extern "C" int las_rnn_seq_bwd_progress_words(int cell, int prec, int B, int H, int flags) {
+    return plan_sweep(cell, prec, B, H, flags, true).progress_words;
 }
 
 static int check_common(const char* who, int cell, int prec, int B, int T, int H, const void* gates, const void* w0,
@@ -1922,72 +1933,63 @@ static int check_common(const char* who, int cell, int prec, int B, int T, int H
     return 0;
 }
 
-// bf16 path: pack W_hh, zero the exchange granules, launch the (clustered) persistent sweep.  Every member of every
-// cluster has to be resident at once (one workgroup per CU), so a batch with more row tiles than the device's CUs can
-// hold is swept in row chunks, one launch after the other on the same stream, each with its own exchange region.
-static int run_bf16(bool bwd, int cell, const RnnArgs& a_in, const float* w0, const float* w1, int ldw, void* ws, size_t ws_bytes,
+// bf16 path: pack W_hh, zero the exchange granules, launch the (clustered) persistent sweep as planned.  Every member of every
+// cluster has to be resident at once (one workgroup per CU), so a batch with more row tiles than one launch holds is swept in
+// row chunks, one launch after the other on the same stream, each with its own exchange region.
+static int run_bf16(const SweepPlan& p, int cell, const RnnArgs& a_in, const float* w0, const float* w1, int ldw, void* ws, size_t ws_bytes,
                     int flags, hipStream_t st, float* db_fw = nullptr, float* db_bw = nullptr, int* db_done = nullptr) {
-    const int G = cell == LAS_CELL_LSTM ? 4 : 1, H = a_in.H, B = a_in.B, T = a_in.T;
+    const int G = cell == LAS_CELL_LSTM ? 4 : 1, H = a_in.H, B = a_in.B, T = a_in.T, P = p.P, RB = p.rb;
     const SeqWs L = seq_ws_layout(cell, H, B);
     LAS_ARG(ws && ws_bytes >= L.total, "las_rnn_seq: workspace too small (%zu < %zu)", ws_bytes, L.total);
+    if (!p.inst) {
+        las_set_error("rnn_seq: no bf16 kernel for cell=%d H=%d at cluster width %d or narrower", cell, H, pick_cluster(cell, H, flags));
+        return -2;
+    }
     char* base = (char*)ws;
-    int P = pick_cluster(cell, H, flags);
-    int rc = -2;
-    for (int attempt = 0; attempt < 5 && rc == -2; ++attempt) {
-        if (attempt > 0) {                               // fall back to the next narrower cluster
-            if (P == 1) break;
-            P >>= 1;
-        }
-        RnnArgs a = a_in;
-        a.wpack = base + L.pack;
-        a.err = (int*)(base + L.err);
-        a.sink = (float*)(base + L.sink);
-        a.sink16 = (unsigned short*)(base + L.sink);
-        a.force_agent = (flags & LAS_SEQ_AGENT_GRANULES) ? 1 : 0;
-        a.no_helpers = (flags & LAS_SEQ_NO_HELPER_WAVES) ? 1 : 0;
-        a.ks_packed = (bwd && P > 1 && !(flags & LAS_SEQ_NO_KSPLIT)) ? 1 : 0;
-        // (err, sink, and for clusters the handshake / bias partials / granule tags: multiples of 256 bytes by construction)
-        uint4* zr = (uint4*)(base + L.err);
-        const long long z16 = (long long)(((P > 1 ? L.total : L.xbuf) - L.err) / 16);
-        // LAS_SEQ_PREPARED: las_rnn_seq_prepare left this cluster width's pack and a clean exchange state in `ws` (first attempt only:
-        // a narrower fall-back cluster packs for itself)
-        if ((flags & LAS_SEQ_PREPARED) && attempt == 0) {}
-        else if (a.ks_packed) hipLaunchKernelGGL(pack_whh_ks_kernel, dim3(cdiv(2LL * G * H * H, 256 * 4)), dim3(256), 0, st, w0, w1, ldw, H, G, P,
-                                            (unsigned short*)a.wpack, zr, z16);
-        else hipLaunchKernelGGL(pack_whh_kernel, dim3(cdiv(2LL * G * H * H, 256 * 4)), dim3(256), 0, st, w0, w1, ldw, H, G, bwd ? 1 : 0, P,
-                                (unsigned short*)a.wpack, zr, z16);
+    RnnArgs a = a_in;
+    a.wpack = base + L.pack;
+    a.err = (int*)(base + L.err);
+    a.sink = (float*)(base + L.sink);
+    a.sink16 = (unsigned short*)(base + L.sink);
+    a.force_agent = (flags & LAS_SEQ_AGENT_GRANULES) ? 1 : 0;
+    a.no_helpers = (flags & LAS_SEQ_NO_HELPER_WAVES) ? 1 : 0;
+    a.ks_packed = p.pack == PACK_KS ? 1 : 0;
+    a.rb = RB;
+    // (err, sink, and for clusters the handshake / bias partials / granule tags: multiples of 256 bytes by construction)
+    uint4* zr = (uint4*)(base + L.err);
+    const long long z16 = (long long)(((P > 1 ? L.total : L.xbuf) - L.err) / 16);
+    // LAS_SEQ_PREPARED: las_rnn_seq_prepare left this plan's pack and a clean exchange state in `ws`
+    if (flags & LAS_SEQ_PREPARED) {}
+    else if (p.pack == PACK_KS) hipLaunchKernelGGL(pack_whh_ks_kernel, dim3(cdiv(2LL * G * H * H, 256 * 4)), dim3(256), 0, st, w0, w1, ldw, H, G, P,
+                                                   (unsigned short*)a.wpack, zr, z16);
+    else hipLaunchKernelGGL(pack_whh_kernel, dim3(cdiv(2LL * G * H * H, 256 * 4)), dim3(256), 0, st, w0, w1, ldw, H, G, p.pack, P,
+                            (unsigned short*)a.wpack, zr, z16);
+    LAS_LAUNCHED();
+    const int ntiles = cdiv(B, RB);
+    const size_t per_cl = L.xbuf_per;                // granule words per cluster
+    int rc = 0;
+    for (int tile0 = 0; tile0 < ntiles && rc == 0; tile0 += p.max_tiles) {
+        const int b0 = tile0 * RB, rows = (B - b0) < p.max_tiles * RB ? (B - b0) : p.max_tiles * RB;
+        RnnArgs c = a;
+        c.B = rows;
+        c.gates16 = a.gates16 + (size_t)b0 * T * 2 * G * H;
+        c.out16 = a.out16 + (size_t)b0 * a.obs;
+        if (a.cstate16) c.cstate16 = a.cstate16 + (size_t)b0 * T * 2 * H;
+        if (a.dout16) c.dout16 = a.dout16 + (size_t)b0 * a.dobs;
+        c.xbuf = (unsigned long long*)(base + L.xbuf) + (size_t)tile0 * 2 * per_cl;
+        c.xcc = (unsigned long long*)(base + L.xcc) + (size_t)tile0 * 2 * 8;
+        c.bpart = (float*)(base + L.bpart) + (size_t)tile0 * 2 * G * H;
+        c.ncl = cdiv(rows, RB) * 2;                      // (row tile, direction) pairs
+        c.ncl_pad = (c.ncl + 7) / 8 * 8;                 // members of a cluster share blockIdx % 8 (same XCD: speed only); <= CUs / P
+        // one more workgroup per cluster (same XCD) that keeps the operands of the next steps in that XCD's L2
+        c.warm = p.warm && (long long)c.ncl_pad * (P + 1) <= las_device_cus() ? 1 : 0;
+        rc = p.inst->launch(p, c, st);
+    }
+    if (rc == 0 && p.pack == PACK_KS && (db_fw || db_bw)) {    // the K-split kernel left per-tile column sums of dz: finish the bias gradient
+        hipLaunchKernelGGL(bias_finish_kernel, dim3(cdiv(2 * G * H, 256)), dim3(256), 0, st, (const float*)(base + L.bpart), ntiles, G * H,
+                           db_fw, db_bw);
         LAS_LAUNCHED();
-        // row tiles per launch: clusters (tile, direction) are padded to a multiple of 8 workgroups per member
-        int max_tiles = (las_device_cus() / P / 8) * 8 / 2;
-        if (max_tiles < 1) { las_set_error("rnn_seq: cluster width %d does not fit %d compute units", P, las_device_cus()); rc = -2; continue; }
-        // 8-row tiles (twice the CUs, half the per-lane work of a dependent step) while the whole batch still fits one launch
-        const bool k8 = (bwd ? a.ks_packed != 0 : !a.no_helpers) && !(flags & LAS_SEQ_ROWS16) && cdiv(B, 8) <= max_tiles &&
-                        (dispatch_bf16(cell, P, bwd, a, st, true) & 1);
-        const int RBk = k8 ? 8 : 16;
-        a.rb = RBk;
-        const int ntiles = cdiv(B, RBk);
-        const size_t per_cl = L.xbuf_per;                // granule words per cluster
-        rc = 0;
-        for (int tile0 = 0; tile0 < ntiles && rc == 0; tile0 += max_tiles) {
-            const int b0 = tile0 * RBk, rows = (B - b0) < max_tiles * RBk ? (B - b0) : max_tiles * RBk;
-            RnnArgs c = a;
-            c.B = rows;
-            c.gates16 = a.gates16 + (size_t)b0 * T * 2 * G * H;
-            c.out16 = a.out16 + (size_t)b0 * a.obs;
-            if (a.cstate16) c.cstate16 = a.cstate16 + (size_t)b0 * T * 2 * H;
-            if (a.dout16) c.dout16 = a.dout16 + (size_t)b0 * a.dobs;
-            c.xbuf = (unsigned long long*)(base + L.xbuf) + (size_t)tile0 * 2 * per_cl;
-            c.xcc = (unsigned long long*)(base + L.xcc) + (size_t)tile0 * 2 * 8;
-            c.bpart = (float*)(base + L.bpart) + (size_t)tile0 * 2 * G * H;
-            c.ncl = c.ncl_pad = 0;                           // set per launch
-            rc = dispatch_bf16(cell, P, bwd, c, st);
-        }
-        if (rc == 0 && a.ks_packed && (db_fw || db_bw)) {    // the K-split kernel left per-tile column sums of dz: finish the bias gradient
-            hipLaunchKernelGGL(bias_finish_kernel, dim3(cdiv(2 * G * H, 256)), dim3(256), 0, st, (const float*)(base + L.bpart), ntiles, G * H,
-                               db_fw, db_bw);
-            LAS_LAUNCHED();
-            if (db_done) *db_done = 1;
-        }
+        if (db_done) *db_done = 1;
     }
     return rc;
 }
@@ -2006,13 +2008,13 @@ extern "C" int las_rnn_seq_prepare(const las_seq_prepare_desc* descs, int n, voi
             LAS_ARG(d.ldw >= G * d.H, "las_rnn_seq_prepare: leading dimension too small");
             const SeqWs L = seq_ws_layout(d.cell, d.H, d.B);
             LAS_ARG(d.ws_bytes >= L.total, "las_rnn_seq_prepare: workspace too small (%zu < %zu)", d.ws_bytes, L.total);
-            const int P = pick_cluster(d.cell, d.H, d.flags);
-            const bool ks = d.bwd && P > 1 && !(d.flags & LAS_SEQ_NO_KSPLIT);
+            const SweepPlan p = plan_sweep(d.cell, LAS_PREC_BF16, d.B, d.H, d.flags, d.bwd != 0);
+            LAS_ARG(p.inst, "las_rnn_seq_prepare: descriptor %d: no bf16 kernel for cell=%d H=%d", i0 + i, d.cell, d.H);
             char* base = (char*)d.ws;
             SeqPrepJob& q = jobs.j[i];
-            q.w0 = d.whh_fw; q.w1 = d.whh_bw; q.ldw = d.ldw; q.H = d.H; q.G = G; q.P = P; q.kind = ks ? 2 : (d.bwd ? 1 : 0);
+            q.w0 = d.whh_fw; q.w1 = d.whh_bw; q.ldw = d.ldw; q.H = d.H; q.G = G; q.P = p.P; q.kind = p.pack;
             q.out = (unsigned short*)(base + L.pack); q.zero = (uint4*)(base + L.err);
-            q.zero16 = (long long)(((P > 1 ? L.total : L.xbuf) - L.err) / 16);
+            q.zero16 = (long long)(((p.P > 1 ? L.total : L.xbuf) - L.err) / 16);
             const long long work = 2LL * G * d.H * d.H / 4 + q.zero16;
             if (work > most) most = work;
         }
@@ -2034,41 +2036,6 @@ static void seq_common_args(RnnArgs& a, int flags, int* status, int code) {
     a.spin = lg ? (1 << lg) : LAS_SPIN_BUDGET_DEFAULT;
     a.status = status; a.status_code = code;
     a.announce = (flags >> 21) & 0x3ff;
-}
-
-// 1 if las_rnn_seq_fwd would serve (cell, prec, B, H, flags) with ONE launch of the helper-wave kernel -- the only kernel that
-// understands x-projection chunks (las_rnn_seq_fwd_chunked)
-static bool handover_room(int B, int rows_per_tile, int P) {
-    const int ncl_pad = (cdiv(B, rows_per_tile) * 2 + 7) / 8 * 8;
-    return (long long)ncl_pad * (P + 1) * 2 <= las_device_cus();
-}
-
-extern "C" int las_rnn_seq_fwd_chunks_ok(int cell, int prec, int B, int H, int flags) {
-    if (prec != LAS_PREC_BF16 || !mfma_shape_ok(H) || B <= 0 || (flags & LAS_SEQ_NO_HELPER_WAVES)) return 0;
-    const int P = pick_cluster(cell, H, flags);
-    if (P <= 1) return 0;
-    RnnArgs a; a.H = H; a.B = B;
-    const int q = dispatch_bf16(cell, P, false, a, nullptr, true);
-    const int max_tiles = (las_device_cus() / P / 8) * 8 / 2;
-    if (max_tiles < 1) return 0;
-    const bool k8 = !(flags & LAS_SEQ_ROWS16) && cdiv(B, 8) <= max_tiles && (q & 1);
-    // The chunks' producers run WHILE the sweep holds its compute units (whole CUs: 159 KB of LDS each): the hand-over only makes sense
-    // while the sweep -- clusters + warmers -- leaves at least half of the machine to them.  r4, B = 144 / 192 at H = 256 (180 / 240 of 256
-    // CUs): the x-projection chunks crawl on the few free CUs, 52 ms per step instead of 26 / the sweep runs into its chunk-wait bound.
-    if (!handover_room(B, k8 ? 8 : 16, P)) return 0;
-    if (k8) return 1;
-    return ((q & 2) && cdiv(B, 16) <= max_tiles) ? 1 : 0;
-}
-
-// rows of different lengths (las_rnn_seq_fwd_rows): the 8-row helper-wave kernel, whole batch in one launch
-extern "C" int las_rnn_seq_fwd_rows_ok(int cell, int prec, int B, int H, int flags) {
-    if (prec != LAS_PREC_BF16 || !mfma_shape_ok(H) || B <= 0 || (flags & (LAS_SEQ_NO_HELPER_WAVES | LAS_SEQ_ROWS16))) return 0;
-    const int P = pick_cluster(cell, H, flags);
-    if (P <= 1) return 0;
-    RnnArgs a; a.H = H; a.B = B;
-    const int q = dispatch_bf16(cell, P, false, a, nullptr, true);
-    const int max_tiles = (las_device_cus() / P / 8) * 8 / 2;
-    return (max_tiles >= 1 && cdiv(B, 8) <= max_tiles && (q & 1)) ? 1 : 0;
 }
 
 extern "C" int las_rnn_seq_io_dtype(int cell, int prec, int H) {
@@ -2120,20 +2087,21 @@ static int rnn_seq_fwd_impl(int cell, int prec, int B, int T, int H, void* gates
     bind_tensors(a, gates, out, cstate, nullptr);
     a.ld_dout = 0; a.dobs = 0; a.fb = forget_bias; a.wpack = ws;
     seq_common_args(a, flags, status, LAS_SEQ_STATUS_FWD_TIMEOUT);
-    LAS_ARG(!chunk_flag || (chunk_steps > 0 && las_rnn_seq_fwd_chunks_ok(cell, prec, B, H, flags)),
+    const SweepPlan p = plan_sweep(cell, prec, B, H, flags, false, row_T ? SWEEP_ROWS : 0);
+    LAS_ARG(!chunk_flag || (chunk_steps > 0 && p.x_chunks),
             "las_rnn_seq_fwd_chunked: this configuration is not served by the kernel that waits for x-projection chunks");
     a.xflag = chunk_flag; a.xsc = chunk_steps;
     a.row_T = row_T;
-    LAS_ARG(!row_T || las_rnn_seq_fwd_rows_ok(cell, prec, B, H, flags), "las_rnn_seq_fwd_rows: rows of different lengths are served by the 8-row "
+    LAS_ARG(!row_T || p.rows, "las_rnn_seq_fwd_rows: rows of different lengths are served by the 8-row "
             "helper-wave kernel only (speed mode, clustered, the whole batch in one launch): ask las_rnn_seq_fwd_rows_ok");
 #ifdef LAS_PROF
     if (const char* e = getenv("LAS_DBG_PTR")) a.dbg = (long long*)strtoull(e, nullptr, 0);   // development build only
 #endif
-    if (prec == LAS_PREC_BF16 && mfma_shape_ok(H)) {
+    if (p.path == SWEEP_BF16) {
         LAS_ARG(ld_out % 4 == 0 && out_bstride % 4 == 0 && (((uintptr_t)gates | (uintptr_t)out | (uintptr_t)cstate) & 15) == 0,
                 "las_rnn_seq_fwd: bf16 tensors must be 16-byte aligned with pitches that are multiples of 4");
-        if (int rc = run_bf16(false, cell, a, whh_fw, whh_bw, ldw, ws, ws_bytes, flags, st)) return rc;
-    } else if (prec == LAS_PREC_F32 && !(flags & LAS_SEQ_F32_VALU) && las_rnn_seq_mf32_ok(cell, H)) {
+        if (int rc = run_bf16(p, cell, a, whh_fw, whh_bw, ldw, ws, ws_bytes, flags, st)) return rc;
+    } else if (p.path == SWEEP_MF32) {
         return las_rnn_seq_mf32_run(false, cell, a, ws, ws_bytes, flags, st);
     } else {
         const size_t lds = (size_t)H * F32_BT * sizeof(float);
@@ -2143,16 +2111,6 @@ static int rnn_seq_fwd_impl(int cell, int prec, int B, int T, int H, void* gates
     }
     LAS_LAUNCHED();
     return 0;
-}
-
-extern "C" int las_rnn_seq_bwd_chunks_ok(int cell, int prec, int B, int H, int flags) {
-    if (prec != LAS_PREC_BF16 || !mfma_shape_ok(H) || B <= 0 || (flags & (LAS_SEQ_NO_KSPLIT | LAS_SEQ_ROWS16))) return 0;
-    const int P = pick_cluster(cell, H, flags);
-    if (P <= 1) return 0;
-    RnnArgs a; a.H = H; a.B = B;
-    const int q = dispatch_bf16(cell, P, true, a, nullptr, true);
-    const int max_tiles = (las_device_cus() / P / 8) * 8 / 2;
-    return (max_tiles >= 1 && (q & 1) && cdiv(B, 8) <= max_tiles && handover_room(B, 8, P)) ? 1 : 0;      // served by ONE launch of the 8-row K-split kernel, with room beside it
 }
 
 extern "C" int las_rnn_seq_bwd(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
@@ -2186,11 +2144,6 @@ extern "C" int las_rnn_seq_bwd_db_chunked(int cell, int prec, int B, int T, int 
     return rnn_seq_bwd_db_impl(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate, dout, ld_dout, dout_bstride,
                                forget_bias, dbias_fw, dbias_bw, flags, status, chunk_flag, chunk_rows, n_rows, nullptr, 0, ws, ws_bytes, stream);
 }
-// words a las_rnn_seq_bwd_db_progress launch publishes (one per cluster member), 0 if the configuration has no progress-publishing kernel
-extern "C" int las_rnn_seq_bwd_progress_words(int cell, int prec, int B, int H, int flags) {
-    if (!las_rnn_seq_bwd_chunks_ok(cell, prec, B, H, flags)) return 0;
-    return 2 * cdiv(B, 8) * pick_cluster(cell, H, flags);
-}
 extern "C" int las_rnn_seq_bwd_db_progress(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
                                            const float* whh_bw, int ldw, const void* out, int ld_out, long long out_bstride,
                                            const void* cstate, const void* dout, int ld_dout, long long dout_bstride,
@@ -2222,8 +2175,9 @@ static int rnn_seq_bwd_db_impl(int cell, int prec, int B, int T, int H, void* ga
     bind_tensors(a, gates, const_cast<void*>(out), const_cast<void*>(cstate), dout);
     a.ld_dout = ld_dout; a.dobs = dout_bstride; a.fb = forget_bias; a.wpack = ws;
     seq_common_args(a, flags, status, LAS_SEQ_STATUS_BWD_TIMEOUT);
+    const SweepPlan p = plan_sweep(cell, prec, B, H, flags, true, (chunk_flag ? SWEEP_CHUNKS : 0) | (progress ? SWEEP_PROGRESS : 0));
     LAS_ARG(!chunk_flag || (chunk_rows > 0 && (chunk_rows & (chunk_rows - 1)) == 0 && (n_rows == T || n_rows == (T + 1) / 2) &&
-                            las_rnn_seq_bwd_chunks_ok(cell, prec, B, H, flags)),
+                            p.dout_chunks),
             "las_rnn_seq_bwd_db_chunked: bad chunk geometry, or a configuration the chunk-aware kernel does not serve");
     a.dflag = chunk_flag; a.dTq = n_rows; a.dshift = (chunk_flag && n_rows != T) ? 1 : 0;
     for (int c = chunk_rows; c > 1; c >>= 1) ++a.dcp;
@@ -2231,12 +2185,12 @@ static int rnn_seq_bwd_db_impl(int cell, int prec, int B, int T, int H, void* ga
 #ifdef LAS_PROF
     if (const char* e = getenv("LAS_DBG_PTR")) a.dbg = (long long*)strtoull(e, nullptr, 0);   // development build only
 #endif
-    const bool bf = prec == LAS_PREC_BF16 && mfma_shape_ok(H);
+    const bool bf = p.path == SWEEP_BF16;
     if (bf) {
         int db_done = 0;
-        if (int rc = run_bf16(true, cell, a, whh_fw, whh_bw, ldw, ws, ws_bytes, flags, st, dbias_fw, dbias_bw, &db_done)) return rc;
+        if (int rc = run_bf16(p, cell, a, whh_fw, whh_bw, ldw, ws, ws_bytes, flags, st, dbias_fw, dbias_bw, &db_done)) return rc;
         if (db_done) return 0;
-    } else if (prec == LAS_PREC_F32 && !(flags & LAS_SEQ_F32_VALU) && las_rnn_seq_mf32_ok(cell, H)) {
+    } else if (p.path == SWEEP_MF32) {
         if (int rc = las_rnn_seq_mf32_run(true, cell, a, ws, ws_bytes, flags, st)) return rc;
     } else {
         LAS_ARG(ws && ws_bytes >= (size_t)2 * G * H * H * sizeof(float), "las_rnn_seq_bwd: workspace too small");

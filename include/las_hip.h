@@ -157,7 +157,8 @@ int las_tanh_bwd_dt(const void* Y, int y_dt, int ldy, const void* dY, int dy_dt,
  *                            XCD that touches the operands of the next steps so that the cluster's own loads hit in L2)
  *   LAS_SEQ_F32_VALU         LAS_PREC_F32: the round-1 VALU kernels (one workgroup per (direction, 8 rows), W_hh streamed from L2)
  *                            instead of the clustered exact-fp32 MFMA kernels (csrc/rnn_seq_f32.hip) -- tests cross-check the two
- *   LAS_SEQ_P(p)             cluster width override (1, 2, 4, 8 workgroups per (direction, 16-row tile))
+ *   LAS_SEQ_P(p)             cluster width override (1, 2, 4, 8 workgroups per (direction, 16-row tile)); a width with no kernel falls
+ *                            back to the next narrower one, and the las_rnn_seq_*_ok / _progress_words queries describe the width that runs
  *   LAS_SEQ_SPIN_LOG2(n)     bound of every exchange spin = 2^n polls (default 2^22)
  *   LAS_SEQ_PREPARED         NOT a development switch: `ws` was prepared by las_rnn_seq_prepare (below) for these weights, this cell / H /
  *                            direction of the pass / flags and a batch >= B, and no sweep has used it since -- the launch then skips its own
