@@ -13,6 +13,7 @@ import torch
 from las import variables as V
 
 MAX_TO_KEEP = 30
+CTC_HEAD = ("Speller/dense/kernel", "Speller/dense/bias")      # (las.las.CTC_HEAD)
 
 
 def _epoch_of(path):
@@ -44,5 +45,9 @@ def restore(save_dir, restore_epoch=-1, store=None):
     if path is None or not os.path.exists(path):
         return None
     # weights_only: the payload is tensors, ints and dicts of them; a checkpoint path must never be able to run pickled code
-    store.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if store.flat is not None:
+        # a model built without the CTC head (decoding a --ctc checkpoint: nothing there reads the head) restores everything else
+        sd["params"] = {n: v for n, v in sd["params"].items() if n in store.vars or n not in CTC_HEAD}
+    store.load_state_dict(sd)
     return path

@@ -283,7 +283,10 @@ class Speller:
     def embedding_matrix(self):
         return V.default_store().get("embedding/embedding_matrix", self._emb_shape, init="uniform1")
 
-    def _params(self):
+    def _params(self, head=False):
+        """head: also the CTC head (las/las.py:75-77: the first `dense` of the Speller scope, [Hd, V+1] with the blank last) -- training
+        with --ctc only; decoding never reads it, so a model restored from a --ctc checkpoint decodes without it.  Created after every
+        other variable: their initial values and bucket offsets are those of a model without the head."""
         st = V.default_store()
         a = self.args
         P = dict(self.att_layer.att_layer.params())
@@ -292,6 +295,9 @@ class Speller:
         P["cellb"] = [st.get(b + "bias", (s[1],), init="zeros") for b, s in self._cell_shapes]
         P["Wv"] = st.get("Speller/decode/dense/kernel", (a.dec_units, a.vocab_size))
         P["bv"] = st.get("Speller/decode/dense/bias", (a.vocab_size,), init="zeros")
+        if head:
+            P["Wc"] = st.get(CTC_HEAD[0], (self.hidden_dim, a.vocab_size + 1))
+            P["bc"] = st.get(CTC_HEAD[1], (a.vocab_size + 1,), init="zeros")
         return P
 
     def _dims(self, B, Tp, U):
@@ -376,8 +382,6 @@ class Speller:
         per step for the whole batch, las/las.py:101); sampled [B,U] supplies the Categorical draws."""
         a = self.args
         _hip.require_gpu(enc_out)
-        if a.ctc:
-            raise NotImplementedError("CTC head (las/las.py:75-77,335-349): README 'not yet fully tested', out of scope (SURVEY T5)")
         dev = enc_out.device
         B, Tp, _ = enc_out.shape
         U = int(dec_steps)
@@ -387,7 +391,8 @@ class Speller:
         assert prepared["B"] == B and prepared["U"] == U
         enc_len_i32, tokens_in = prepared["enc_len_i32"], prepared["tokens_in"]
         step_logits, emb_mask = prepared["step_logits"], prepared["emb_mask"]
-        P = self._params()
+        head = bool(a.ctc) and is_training                  # (inference: nothing reads the CTC logits)
+        P = self._params(head=head)
         cfg = (self._dims(B, Tp, U), L._prec(), step_logits, sampling_seed(st.global_step, self.rank), emb_mask,
                prepared.get("emb_noise"))
         cp = list(P["cellW"]) + list(P["cellb"])
@@ -395,7 +400,9 @@ class Speller:
                                                   P.get("loc_w"), P.get("loc_b"), P.get("Wf"), cfg, enc_len_i32,
                                                   tokens_in, *cp)
         self.last_tokens_in = tokens_in
-        return logits_tm.permute(1, 0, 2), None, alphas_tm.permute(1, 0, 2)
+        # the CTC head behind the loop, on the launch stream (no kernel beside the one-launch loop: DESIGN section 5)
+        ctc_logits = _CTCHead.apply(enc_out, P["Wc"], P["bc"], L._prec()) if head else None
+        return logits_tm.permute(1, 0, 2), ctc_logits, alphas_tm.permute(1, 0, 2)
 
     def decode(self, enc_out, enc_len, dec_state, prev_token, prev_align, is_training, keys=None, token_ids=None):
         """One decode step, reference las/las.py:145-160 -- forward only (beam search).
@@ -540,6 +547,76 @@ def _ce_loss(logits_bt, y_i32, V_, smooth, scale):
     return sums[2], dl, sums
 
 
+CTC_HEAD = ("Speller/dense/kernel", "Speller/dense/bias")
+CTC_MAX_LABELS = 511               # las_ctc_loss: U <= 511 (include/las_hip.h)
+
+
+class _CTCHead(torch.autograd.Function):
+    """ctc_logits = enc . W + b (las/las.py:75-77) through las_gemm; backward d_enc = d . W^T on the chain, then dW += enc^T . d and
+    db += colsum(d) -- accumulated straight into the gradient bucket, enqueued before the Listener's backward (so a data-parallel step's
+    early all-reduce covers them)."""
+
+    @staticmethod
+    def forward(ctx, enc, W, b, prec):
+        enc = enc.contiguous()
+        B, Tp, Hd = enc.shape
+        Vc = W.shape[1]
+        out = torch.empty(B, Tp, Vc, device=enc.device)
+        _hip.gemm(prec, enc, W.detach(), out, False, False, B * Tp, Vc, Hd, Hd, Vc, Vc, bias=b.detach())
+        ctx.save_for_backward(enc, W, b)
+        ctx.prec = prec
+        return out
+
+    @staticmethod
+    def backward(ctx, d):
+        enc, W, b = ctx.saved_tensors
+        prec = ctx.prec
+        B, Tp, Hd = enc.shape
+        Vc = W.shape[1]
+        d = d.contiguous()
+        d_enc = torch.empty(B, Tp, Hd, device=enc.device)
+        _hip.gemm(prec, d, W.detach(), d_enc, False, True, B * Tp, Hd, Vc, Vc, Vc, Hd)
+        direct = L._direct_ok(W) and L._direct_ok(b)
+        dW = W.grad if direct else torch.zeros_like(W)
+        db = b.grad if direct else torch.zeros_like(b)
+        _hip.gemm(prec, enc, d, dW, True, False, Hd, Vc, B * Tp, Hd, Vc, Vc, beta=1.0)
+        _hip.colsum(d, B * Tp, Vc, Vc, db, beta=1.0)
+        if direct:
+            return d_enc, None, None, None
+        return d_enc, dW, db, None
+
+
+def _ctc_loss(ctc_logits, y_i32, enc_len_i32, drop_last_row, scale, grad_dtype=torch.float32):
+    """-> (scale * sum_b nll_b as a [1] tensor, nll [B], gradient w.r.t. the logits with `scale` in it): las_ctc_loss, one call."""
+    B, Tp, Vc = ctc_logits.shape
+    sb, st_, sv = ctc_logits.stride()
+    assert sv == 1 and y_i32.dtype == torch.int32 and enc_len_i32.dtype == torch.int32
+    dev = ctc_logits.device
+    nll = torch.empty(B, device=dev)
+    loss = torch.empty(1, device=dev)
+    grad = torch.empty(B, Tp, Vc, dtype=grad_dtype, device=dev)
+    nb = _hip.lib().las_ctc_workspace_bytes(B, Tp, y_i32.shape[1])
+    ws = _hip.workspace(dev, nb, "ctc")
+    _hip.check(_hip.lib().las_ctc_loss(_hip.p(ctc_logits), sb, st_, Vc, _hip.p(y_i32), y_i32.stride(0), y_i32.shape[1],
+                                       _hip.p(enc_len_i32), B, Tp, int(drop_last_row), _hip.p(nll), _hip.p(loss), _hip.p(scale),
+                                       _hip.p(grad), _hip._dt(grad), grad.stride(0), grad.stride(1), _hip.p(ws), ws.numel(),
+                                       _hip.stream()), "las_ctc_loss")
+    return loss, nll, grad
+
+
+def ctc_label_lengths(y, tokenlen, drop_last):
+    """Host-side label count of every row: tokenlen (the row's nonzero entries), less the one the reference drops from the batch's
+    last row with labels when drop_last (las/las.py:338).  Returns (lengths int64 [B], the dropping row or -1)."""
+    n = np.asarray(torch.as_tensor(tokenlen).cpu(), np.int64).reshape(-1).copy()
+    row = -1
+    if drop_last:
+        nz = np.nonzero(n > 0)[0]
+        if len(nz):
+            row = int(nz[-1])
+            n[row] -= 1
+    return n, row
+
+
 class LAS:
     """reference las/las.py:209-369."""
 
@@ -600,7 +677,7 @@ class LAS:
             with torch.no_grad():
                 dummy = torch.zeros(1, 8, a.feat_dim, 3, device=st.device)
                 self.listener(dummy, [8], "cnn", is_training=False)
-        self.speller._params()
+        self.speller._params(head=bool(a.ctc))
         st.flatten()
 
     @staticmethod
@@ -714,6 +791,22 @@ class LAS:
             return self._train_step_impl(xs, ys, coins, sampled)
 
     def _train_step_impl(self, xs, ys, coins=None, sampled=None):
+        ctc = bool(self.args.ctc)
+        if ctc:
+            # tf.nn.ctc_loss (ignore_longer_outputs_than_inputs=False) refuses a row with more labels than frames: refused here, on the
+            # host, before anything is enqueued (both lengths are host values)
+            last_rank = self.dp is None or self.dp.rank == self.dp.world - 1
+            lab_len, drop_row = ctc_label_lengths(ys[0], ys[1], last_rank)
+            frames = np.asarray(self.listener.output_length(xs[1], self.args.enc_type.lower())).astype(np.int64).reshape(-1)
+            U = int(np.max(np.asarray(torch.as_tensor(ys[1]).cpu())))
+            if U > CTC_MAX_LABELS:
+                raise ValueError("CTC: %d decoder steps; las_ctc_loss takes at most %d labels per utterance (one extended-label state per "
+                                 "lane of a 1024-thread workgroup)" % (U, CTC_MAX_LABELS))
+            bad = np.nonzero(lab_len > frames)[0]
+            if len(bad):
+                b = int(bad[0])
+                raise ValueError("CTC: not enough time for the target transition sequence: row %d has %d labels and %d encoder frames "
+                                 "(tf.nn.ctc_loss raises here too)" % (b, int(lab_len[b]), int(frames[b])))
         dev = self._device()
         st = V.default_store()
         self.build_variables()
@@ -750,6 +843,11 @@ class LAS:
             n_total = self.dp.all_reduce_scalar(n_local) if self.dp is not None else n_local
             loss_scale = self._loss_scale(n_total)
             y_u = y[:, :dec_steps].contiguous()               # (the loss's label block: copied here, off the chain)
+            if ctc:
+                # ctc_weight / (rows of the GLOBAL batch): data-parallel ranks hold shards of one batch (train_stacked)
+                b_local = torch.full((1,), float(audio.shape[0]), device=dev)
+                b_total = self.dp.all_reduce_scalar(b_local) if self.dp is not None else b_local
+                ctc_scale = (float(self.args.ctc_weight) / b_total.reshape(-1)).reshape(1).to(torch.float32)
             # the Speller's host-side preparation: token schedule, encoder lengths, masks
             prep = self.speller.prepare(audio.shape[0], self.listener.output_length(audiolen, enc_type), dec_steps, dev, y,
                                         True, coins, sampled)
@@ -763,6 +861,11 @@ class LAS:
             # the loss is the root of the graph: its gradient w.r.t. the logits (scale included) comes out of the same kernel pair and is
             # handed to the Speller's node directly -- no ones_like fill, no [B, U, V] multiply by 1.0, no scalar multiply on the chain
             loss, dlogits, _ = _ce_loss(logits.detach(), y_u, logits.shape[2], self.args.label_smoothing, loss_scale)   # sum_local / n_total
+            if ctc:
+                # the CTC term (las/las.py:259-261, 335-349): value and gradient in one call, on the launch stream behind the head
+                att_loss = loss
+                ctc_sum, ctc_nll, dctc = _ctc_loss(ctc_logits.detach(), y_u, prep["enc_len_i32"], drop_row, ctc_scale)
+                loss = att_loss + ctc_sum[0]
         early = []
         if self.dp is not None:
             def before_tail(P4, st=st, dev=dev):
@@ -782,7 +885,11 @@ class LAS:
             L.BEFORE_TAIL_HOOK[0] = before_tail
         with _hip.roctx_range("backward"):
             try:
-                logits.backward(dlogits)
+                if ctc:
+                    # two roots: the listener's d_enc is the sum of the Speller's and the head's contributions
+                    torch.autograd.backward([logits, ctc_logits], [dlogits, dctc])
+                else:
+                    logits.backward(dlogits)
             finally:
                 L.BEFORE_TAIL_HOOK[0] = None
             _hip.join_side_stream()                   # weight gradients accumulated on the side stream
@@ -824,6 +931,9 @@ class LAS:
         st.global_step += 1
         sample_rate = self.speller._scheduled_sampling()
         summaries = {"loss": loss_val, "global_step": st.global_step, "lr": lr}
+        if ctc:
+            summaries["att_loss"] = att_loss.detach()
+            summaries["ctc_loss"] = ctc_nll.sum() / b_total.reshape(-1)[0]            # mean_b nll_b over the global batch (this rank's share)
         self.last = {"logits": logits, "y": y}
         return loss_val, None, st.global_step, logits.detach(), alphas.detach(), summaries, sample_rate
 

@@ -180,6 +180,12 @@ class VariableStore:
             with torch.no_grad():
                 for n in self.order:
                     off, k = self.offsets[n], self.vars[n].numel()
+                    if n not in sd["adam_m"]:
+                        # a variable the checkpoint does not hold (the CTC head when a model without it is fine-tuned with --ctc):
+                        # its fresh initial value and empty Adam slots
+                        self.adam_m[off:off + k].zero_()
+                        self.adam_v[off:off + k].zero_()
+                        continue
                     self.adam_m[off:off + k].copy_(sd["adam_m"][n].reshape(-1))
                     self.adam_v[off:off + k].copy_(sd["adam_v"][n].reshape(-1))
 

@@ -424,6 +424,25 @@ int las_ce_loss(const float* logits, long long sb, long long st, const int* y, i
                 void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K8c  CTC term of joint CTC-attention training (las/las.py:75-77, 259-261, 335-349; tf.nn.ctc_loss, ctc_merge_repeated,
+ * blank = class Vc - 1, softmax inside the loss).  logits fp32 [B, Tp, Vc] through strides sb / st (elements, last axis
+ * contiguous).  The labels of row b are the nonzero entries of y[b, 0:U] (int32, pitch ldy >= U), in order; on row
+ * drop_last_row (or none: -1) the last of them is dropped (the reference's `[:-1]` over the whole batch).
+ * enc_len int32 [B]: frames t >= enc_len[b] contribute nothing.  U <= 511.
+ *   nll[b]   = -log p(labels_b | logits_b)   (+inf for a row that cannot be aligned, or that holds a label outside [0, Vc-2])
+ *   loss[0]  = scale_ptr[0] * sum_b nll[b]    (loss may be NULL; fixed-order sum)
+ *   grad     = scale_ptr[0] * (softmax - posterior) per (b, t) row, element type grad_dtype (LAS_DT_F32 / LAS_DT_BF16), strides
+ *              gsb / gst; zero rows at t >= enc_len[b] and for rows with nll = +inf.  NULL skips the gradient.
+ * No atomics: two calls on the same inputs give the same bits.  ws >= las_ctc_workspace_bytes(B, Tp, U).
+ */
+size_t las_ctc_workspace_bytes(int B, int Tp, int U);
+int las_ctc_loss(const float* logits, long long sb, long long st, int Vc, const int* y, int ldy, int U,
+                 const int* enc_len, int B, int Tp, int drop_last_row,
+                 float* nll, float* loss, const float* scale_ptr,
+                 void* grad, int grad_dtype, long long gsb, long long gst,
+                 void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K9  tf.clip_by_global_norm + tf.train.AdamOptimizer.apply_gradients (las/las.py:272-283) on one
  * flat fp32 parameter bucket.  las_sumsq: out[0] = sum g^2 (deterministic two-stage reduction;
  * ws >= las_sumsq_workspace_bytes(n)).  las_clip_adam: theta,m,v updated in place;
