@@ -7,6 +7,8 @@
 // SOS is never re-emitted after t=0.  The per-hypothesis top-64 cut (las/beam_search.py:123) cannot
 // bind while beam < 64 (the ranking key is monotone in the logit inside one hypothesis), so the kernel
 // selects the global top-`beam` of the num_live x V candidate grid directly and requires beam < topn.
+// With joint CTC-attention scores (las_ctc_prefix_step, ctc_prefix.hip) the key is no longer monotone in the logit and the cut
+// binds for V > 64: that kernel applies it and writes -inf for every token outside a row's bank, so the ranking here stays as is.
 // Tie order = the order a stable ascending sort of the reference's candidate bank would give:
 // (score/len, hypothesis index, logit, token id).
 // One workgroup per utterance; `beam` rounds of a block-wide arg-max over the candidates that are

@@ -91,6 +91,8 @@ _EXTRA = [
                            "step are the update of k data-parallel ranks; the latency-bound recurrent sweeps make k = 2 / 4 cost 1.4 / 2.0 steps."),
     (("--decode_batch",), int, 64, "Utterances per device-resident beam-search batch in decode.py (rows of a search step = this x beam_size; "
                                   "64 x 16 rows decode 1.8x the utterances/s of 16 x 16)."),
+    (("--ctc_decode_weight",), float, 0.0, "Weight of the CTC prefix scores in joint CTC-attention beam search (needs --ctc True; 0: attention "
+                                           "(+ LM) scores only).  A candidate scores logit + weight * (CTC prefix score gain)."),
     (("--lm_dir",), str, "lang/output/", "Output directory of train_lm.py (result.json, vocab.json, models) for --apply_lm."),
 ]
 

@@ -96,6 +96,13 @@ class BeamSearch(object):
             raise ValueError('Other units are currently not support!')
         if args.apply_lm:
             self.lm = language_model
+        # joint CTC-attention decoding: a candidate scores logit + ctc_weight * (psi(h.c) - psi(h)); 0 = attention (+ LM) only,
+        # and then none of the CTC code runs
+        self.ctc_weight = float(getattr(args, "ctc_decode_weight", 0.0) or 0.0)
+        if self.ctc_weight < 0:
+            raise ValueError("--ctc_decode_weight must be >= 0 (got %g)" % self.ctc_weight)
+        if self.ctc_weight > 0 and not getattr(args, "ctc", False):
+            raise ValueError("--ctc_decode_weight %g needs the CTC head: decode with --ctc True (a model trained with --ctc)" % self.ctc_weight)
         self._las = las
         self.use_graph = os.environ.get("LAS_NO_DECODE_GRAPH") != "1"     # decode_batch replays one captured step
         self.fuse_projection = os.environ.get("LAS_NO_DECODE_FUSED_PROJ") != "1"   # decode_batch: cell in one launch, projection inside the beam kernel
@@ -173,6 +180,8 @@ class BeamSearch(object):
                 if h.untyped_storage().data_ptr() not in seen:
                     seen.add(h.untyped_storage().data_ptr())
                     h.record_stream(main)
+            if pre[4] is not None:           # (the CTC log-probabilities, likewise)
+                pre[4].record_stream(main)
             return xs_list, pre, ev
 
         it = iter(batches)
@@ -212,8 +221,9 @@ class BeamSearch(object):
 
     def _run_encoders(self, sess, xs_list):
         """The encoders of a batch of utterances on the CURRENT stream, without waiting for the device (the encoded lengths are host
-        values): -> (encs [per utterance: [1, T'_u, Hd] views], enc_lens, dec_steps, h_one).  decode_batch's first phase; decode_batches
-        runs it for the NEXT batch on a second stream under the search of the current one."""
+        values): -> (encs [per utterance: [1, T'_u, Hd] views], enc_lens, dec_steps, h_one, ctc_lp).  ctc_lp: the CTC head's class-major
+        log-probabilities [n, V + 1, max T'_u] when ctc_decode_weight > 0, else None.  decode_batch's first phase; decode_batches runs it
+        for the NEXT batch on a second stream under the search of the current one."""
         a = self.args
         dev = self._las._device()
         n = len(xs_list)
@@ -301,7 +311,29 @@ class BeamSearch(object):
         else:
             for us in glist[1:]:
                 encode_group(us)
-        return encs, enc_lens, dec_steps, h_one
+        ctc_lp = self._ctc_log_probs(encs, h_one) if self.ctc_weight > 0 else None
+        return encs, enc_lens, dec_steps, h_one, ctc_lp
+
+    def _ctc_log_probs(self, encs, h_one):
+        """The CTC head over the encoder frames of a batch (las/las.py:75-77, the product of _CTCHead.forward through las_gemm), then
+        las_ctc_log_softmax: class-major log-probabilities [n, V + 1, T'] (frames past T'_u hold values nobody reads)."""
+        dev = self._las._device()
+        P = self.speller._params(head=True)
+        Wc, bc = P["Wc"].detach(), P["bc"].detach()
+        n = len(encs)
+        Tps = [h.shape[1] for h in encs]
+        Tp, Hd, Vc = max(Tps), encs[0].shape[2], Wc.shape[1]
+        if h_one is not None and h_one.shape[0] == n:
+            enc = h_one.contiguous()
+        else:
+            enc = torch.zeros(n, Tp, Hd, device=dev)
+            for u, h in enumerate(encs):
+                enc[u, :Tps[u]] = h[0]
+        z = torch.empty(n, Tp, Vc, device=dev)
+        _hip.gemm(L._prec(), enc, Wc, z, False, False, n * Tp, Vc, Hd, Hd, Vc, Vc, bias=bc)
+        lp = torch.empty(n, Vc, Tp, device=dev)
+        _hip.check(_hip.lib().las_ctc_log_softmax(_hip.p(z), n, Tp, Vc, _hip.p(lp), _hip.stream()), "las_ctc_log_softmax")
+        return lp
 
     def decode_batch(self, sess, xs_list, sync_every=32, _pre=None, _after_launch=None, _defer=False):
         """Beam search for several utterances at once (what decode.py's loop over utterances, decode.py:131-149, becomes on
@@ -332,7 +364,8 @@ class BeamSearch(object):
         mark("start")
         if _pre is None:
             _pre = self._run_encoders(sess, xs_list)
-        encs, enc_lens, dec_steps, h_one = _pre
+        encs, enc_lens, dec_steps, h_one, ctc_lp = _pre
+        lam = self.ctc_weight
         Tps = [h.shape[1] for h in encs]
         Tp, Hd = max(Tps), encs[0].shape[2]
         N = n * beam
@@ -443,6 +476,20 @@ class BeamSearch(object):
                         ("src_row", src_row), ("next_token", next_token)):
             setattr(ba, name, t.data_ptr())
         ba.nutt, ba.beam, ba.V, ba.Umax, ba.selcap, ba.topn = n, beam, V_, Umax, selcap, self.TOPN
+        if lam > 0:
+            # joint CTC-attention: las_ctc_prefix_step advances every live row's CTC state (r^n, r^b, psi, last label) from
+            # its gathered parent `ctc_par` into `ctc_cur` and writes the joint scores of the row's candidates into `joint`, which the pruning
+            # ranks instead of the logits; `ctc_cur` follows its hypotheses through the gather like the recurrent state
+            assert ctc_lp is not None and ctc_lp.shape == (n, V_ + 1, Tp), "decode_batch: the encoder stage made no CTC log-probabilities"
+            ctc_w = 4 * ((2 * Tp + 2 + 3) // 4)
+            ctc_par = torch.zeros(N, ctc_w, device=dev)
+            ctc_cur = torch.zeros(N, ctc_w, device=dev)
+            joint = torch.zeros(N, V_, device=dev)
+            ctc_len = torch.tensor([int(x) for x in enc_lens], **i32)
+            st_in.append(ctc_cur); st_out.append(ctc_par)
+            ba.logits = joint.data_ptr()
+        if len(st_in) > 16:
+            raise ValueError("decode_batch: %d state tensors follow the hypotheses; las_beam_loop_step gathers at most 16" % len(st_in))
         ba.start_id, ba.end_id, ba.ntens = self.start_id, self.end_id, len(st_in)
         for k, (ti, to) in enumerate(zip(st_in, st_out)):
             ba.state_in[k], ba.state_out[k], ba.state_width[k] = ti.data_ptr(), to.data_ptr(), ti.shape[-1]
@@ -480,7 +527,8 @@ class BeamSearch(object):
         # rows + ONE cell launch) and the vocabulary projection -- the Speller's output layer and, concatenated along K, the LM's softmax
         # layer scaled by lm_weight and shifted to its token columns -- happens inside las_beam_loop_step: 5 launches per step instead of 8
         E_ = a.embedding_size
-        fused_proj = (prec == _hip.PREC_BF16 and lstm and NL == 1 and self.fuse_projection and D % 32 == 0 and (E_ + Hd + D) % 32 == 0 and
+        # (not with the CTC prefix scores: they are placed between the materialised logits and the pruning launch)
+        fused_proj = (lam == 0 and prec == _hip.PREC_BF16 and lstm and NL == 1 and self.fuse_projection and D % 32 == 0 and (E_ + Hd + D) % 32 == 0 and
                       ((beam + 15) // 16) * ((V_ + 15) // 16) <= 8 and (lm is None or (lm.hidden_size % 32 == 0 and "packs" in lm_plan)))
         proj_keep = None
         mode["fused"] = fused_proj
@@ -557,6 +605,11 @@ class BeamSearch(object):
             if not mode["fused"]:
                 lm.project_fused(lm_plan, held[1][-1], logits, 2)
 
+        def ctc_part():                                  # CTC state advance and joint scores of the step (reads the device step counter)
+            _hip.check(lib.las_ctc_prefix_step(_hip.p(ctc_lp), _hip.p(ctc_len), n, beam, Tp, V_, self.end_id, _hip.p(logits), _hip.p(joint),
+                                               lam, _hip.p(ctc_par), _hip.p(ctc_cur), ctc_w, _hip.p(next_token), _hip.p(step),
+                                               _hip.p(nlive), _hip.p(done), _hip.p(dstep), Umax, _hip.stream()), "las_ctc_prefix_step")
+
         def beam_part():                                 # files alphas_cur under the device step counter, prunes, gathers, advances the counter
             _hip.check(lib.las_beam_loop_step(ctypes.byref(ba), _hip.stream()), "las_beam_loop_step")
 
@@ -566,6 +619,8 @@ class BeamSearch(object):
             speller_part()
             if lm is not None:
                 lm_part()
+            if lam > 0:
+                ctc_part()
             beam_part()
 
         steps_run = 0
@@ -645,11 +700,18 @@ class BeamSearch(object):
         results = self._decode_tail(dev, n, selcap, Umax, i32, ba, lib, alphas_hist, Tps, mark)
         mark("done")
         parts = {}
-        if tm:        # device time of the three parts of a decode step (HIP events, 50 eager repetitions each, after the search)
+        if tm:        # device time of the parts of a decode step (HIP events, 50 eager repetitions each, after the search)
+            live_steps = int((hist_n.sum(1) > 0).sum())              # steps in which some utterance still had a live hypothesis
             step.zero_()
-            for name, fn in (("speller", speller_part), ("lm", lm_part if lm is not None else None), ("beam", beam_part)):
+            for name, fn in (("speller", speller_part), ("lm", lm_part if lm is not None else None),
+                             ("ctc", ctc_part if lam > 0 else None), ("beam", beam_part)):
                 if fn is None:
                     continue
+                if name == "ctc":
+                    # every row live at a step > 0 (after the search every utterance is done and the kernel would return at once); the
+                    # loop words are put back before the pruning part is timed
+                    saved = (done.clone(), nlive.clone())
+                    done.zero_(); nlive.fill_(beam); step[0] = 1
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 with torch.no_grad():
                     fn(); e0.record()
@@ -660,9 +722,11 @@ class BeamSearch(object):
                     e1.record()
                 torch.cuda.synchronize(dev)
                 parts[name] = round(e0.elapsed_time(e1) / 50 * 1e3, 2)
+                if name == "ctc":
+                    done.copy_(saved[0]); nlive.copy_(saved[1]); step.zero_()
             ks = list(tm)
             self.last_timing = {ks[i + 1]: round(tm[ks[i + 1]] - tm[ks[i]], 4) for i in range(len(ks) - 1)}
-            self.last_timing.update(steps=steps_run, rows=N, frames=Tp, graph=graph is not None, parts_us=parts)
+            self.last_timing.update(steps=steps_run, live_steps=live_steps, rows=N, frames=Tp, graph=graph is not None, parts_us=parts)
             if self.args.verbose > 0:
                 print("decode_batch timing (s):", self.last_timing)
         return results
@@ -711,7 +775,14 @@ class BeamSearch(object):
         """Restore LAS weights (reference las/beam_search.py:272-281; the TF name remapping of
         :252-270 is unnecessary: train and decode share one variable store)."""
         from las import checkpoint
-        return checkpoint.restore(save_path, restore_epoch)
+        missing = []
+        path = checkpoint.restore(save_path, restore_epoch, missing=missing)
+        absent = [nm for nm in checkpoint.CTC_HEAD if nm in missing]
+        if path is not None and self.ctc_weight > 0 and absent:
+            # the head would keep its initial values: the prefix scores would be noise
+            raise ValueError("--ctc_decode_weight %g: checkpoint %s holds no CTC head (%s); it was not trained with --ctc True"
+                             % (self.ctc_weight, path, ", ".join(absent)))
+        return path
 
     def _select_best_k(self, beam_set, norm=False):
         """reference las/beam_search.py:297-312 (host-side: used for the final ranking of <= 2*beam items)."""

@@ -38,14 +38,17 @@ def save(save_dir, epoch, store=None):
     return path
 
 
-def restore(save_dir, restore_epoch=-1, store=None):
-    """Load `las_E{restore_epoch}` (or the latest when -1).  Returns the path, or None if nothing exists."""
+def restore(save_dir, restore_epoch=-1, store=None, missing=None):
+    """Load `las_E{restore_epoch}` (or the latest when -1).  Returns the path, or None if nothing exists.  missing: a list that receives
+    the names of the store's variables the checkpoint does not hold (they keep their current values)."""
     store = store or V.default_store()
     path = latest_checkpoint(save_dir) if restore_epoch == -1 else os.path.join(save_dir, "las_E%d" % restore_epoch)
     if path is None or not os.path.exists(path):
         return None
     # weights_only: the payload is tensors, ints and dicts of them; a checkpoint path must never be able to run pickled code
     sd = torch.load(path, map_location="cpu", weights_only=True)
+    if missing is not None:
+        missing.extend(n for n in store.vars if n not in sd["params"])
     if store.flat is not None:
         # a model built without the CTC head (decoding a --ctc checkpoint: nothing there reads the head) restores everything else
         sd["params"] = {n: v for n, v in sd["params"].items() if n in store.vars or n not in CTC_HEAD}

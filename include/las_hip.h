@@ -567,7 +567,9 @@ int las_lstm_pointwise_bwd(const float* z, const float* c_prev, const float* dh,
  * (score+logit)/(length+1) in float32 (:306) and the best `beam` are returned in ASCENDING order
  * (best last, :310-312).  Ties follow a stable ascending sort of the reference's candidate bank:
  * (key, hypothesis index, logit, token id).  The per-hypothesis top-`topn` cut (:123, 64) cannot
- * bind while beam < topn, which this entry point requires.
+ * bind while beam < topn, which this entry point requires, AS LONG AS the ranked scores are monotone in the logit within a
+ * hypothesis.  The joint CTC-attention scores of las_ctc_prefix_step (K10c) are not: that entry point applies the cut itself and
+ * gives every token outside a row's bank a -inf score, which never ranks above the bank's >= beam finite candidates.
  *   logits [nutt,beam,V]   score f32 [nutt,beam]   length int32 [nutt,beam]   nlive int32 [nutt]
  * Outputs (count in out_n[nutt]): out_parent, out_token int32 [nutt,beam]; out_score f32 [nutt,beam]
  * = new running sums.
@@ -575,6 +577,32 @@ int las_lstm_pointwise_bwd(const float* z, const float* c_prev, const float* dh,
 int las_beam_step(const float* logits, const float* score, const int* length, const int* nlive,
                   int nutt, int beam, int V, int topn, int t, int start_id,
                   int* out_parent, int* out_token, float* out_score, int* out_n, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K10c  CTC prefix scores for joint CTC-attention beam search (Watanabe et al. 2017, Algorithm 2).  blank = class V of the
+ * head's V + 1 classes; token id c is CTC class c; SOS is never a label; EOS is scored as an ordinary final label.
+ *
+ * las_ctc_log_softmax: logits fp32 [n, Tp, Vc] (contiguous; the head's enc . Wc + bc) -> out fp32 [n, Vc, Tp] = log_softmax over
+ * the Vc classes, CLASS-MAJOR (a candidate's column is contiguous over t).  Once per batch: 4 n Vc Tp bytes (410 MB at n = 64,
+ * Vc = 5001, Tp = 319).
+ *
+ * las_ctc_prefix_step: one search step, launched between the step's logits and las_beam_loop_step; all arguments are fixed across
+ * the search (the step is read from *step: hipGraph friendly).  For every live row = u * beam + j (j < nlive[u], j = 0 at step 0;
+ * utterances with done[u] or *step >= dec_step[u], and every row once *step >= Umax, are skipped) with entering token c = token[row]:
+ *   - state_in[row] is the parent g's state (as gathered by las_beam_loop_step); it is advanced by c into state_out[row]
+ *     (at step 0: the empty prefix's state, r^n = LOGZERO, r^b_t = sum_{tau <= t} y_tau[blank], psi = 0).  Row layout, state_width
+ *     >= 2 Tp + 2 floats: [0, Tp) r^n_t, [Tp, 2 Tp) r^b_t, [2 Tp] psi(h), [2 Tp + 1] last label of h (-1: empty); t < T'_u only.
+ *   - joint[row][v] = logits[row][v] + lam * (psi(h.v) - psi(h)), fp32 in this order, for v in the row's candidate bank (top-64 of
+ *     logits[row] by (logit, token id); every token when V <= 64), -inf for every other token.  psi(h.EOS) = full-sequence
+ *     log-probability of h.EOS.  Impossible prefixes get ~LOGZERO = -1e10, not -inf.
+ * lp: las_ctc_log_softmax's output; enc_len [nutt]: T'_u (clamped to [1, Tp]).  Tp <= 2048, V <= 16384, state_in != state_out.
+ * No atomics: two runs give the same bits.
+ */
+int las_ctc_log_softmax(const float* logits, int n, int Tp, int Vc, float* out, void* stream);
+int las_ctc_prefix_step(const float* lp, const int* enc_len, int nutt, int beam, int Tp, int V, int end_id,
+                        const float* logits, float* joint, float lam, const float* state_in, float* state_out,
+                        int state_width, const int* token, const int* step, const int* nlive, const int* done,
+                        const int* dec_step, int Umax, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K10b  device-resident BeamSearch.decode loop (las/beam_search.py:94-158) for `nutt` utterances at once: ONE call per
