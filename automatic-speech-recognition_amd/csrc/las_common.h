@@ -141,11 +141,15 @@ __device__ __forceinline__ float xor16_max(float v) {
 // PRECONDITION of wave_sum / wave_max / block_argmax and the xor*_ helpers: EVERY lane of the wave is active.  The lane swaps skip inactive
 // lanes and a DPP read of a disabled lane returns 0 (bound_ctrl): under divergence the result would be silently different.  Every caller
 // reaches them on uniform control flow (lanes without a value contribute the operation's identity instead of branching around the call).
-__device__ __forceinline__ float wave_sum(float v) {
-    v = xor32_sum(v); v = xor16_sum(v);
-    v += dpp_f<0x128>(v); v += dpp_f<0x124>(v); v += dpp_f<0x122>(v); v += dpp_f<0x121>(v);
+// The sum family: over a 16-lane group (a DPP row), a 32-lane half-wave, the wave -- each the tail of the next, in every lane.
+// (Tried for the 16-lane sums at the end of every frame group of the attention energies: four __shfl_xor, i.e. four ds_bpermute round trips
+// through the LDS queue in a dependent chain; result: the rotations are bit-identical and took the train step 13.98 -> 13.75 ms.)
+__device__ __forceinline__ float sub16_sum(float v) {
+    v += dpp_f<0x128>(v); v += dpp_f<0x124>(v); v += dpp_f<0x122>(v); v += dpp_f<0x121>(v);      // row_ror:8, 4, 2, 1
     return v;
 }
+__device__ __forceinline__ float sub32_sum(float v) { return sub16_sum(xor16_sum(v)); }
+__device__ __forceinline__ float wave_sum(float v) { return sub32_sum(xor32_sum(v)); }
 __device__ __forceinline__ float wave_max(float v) {
     v = xor32_max(v); v = xor16_max(v);
     v = fmaxf(v, dpp_f<0x128>(v)); v = fmaxf(v, dpp_f<0x124>(v)); v = fmaxf(v, dpp_f<0x122>(v)); v = fmaxf(v, dpp_f<0x121>(v));

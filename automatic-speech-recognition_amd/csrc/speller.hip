@@ -147,8 +147,8 @@ __device__ __forceinline__ void row_logits(const DecDev& a, const float* __restr
         const int v = tid / tpv, part = tid - v * tpv, vc = v < V ? v : V - 1;
         float acc = 0.f;
         for (int d = part; d < D; d += tpv) acc = fmaf(opnd<FAST>(h[d]), opnd<FAST>(a.Wv[(size_t)d * V + vc]), acc);
-        if (tpv == 16) {       // (char vocabularies at 1024 threads: a 16-lane group = a DPP row, the butterfly 8, 4, 2, 1 as row rotations -- sub16_sum)
-            acc += dpp_f<0x128>(acc); acc += dpp_f<0x124>(acc); acc += dpp_f<0x122>(acc); acc += dpp_f<0x121>(acc);
+        if (tpv == 16) {       // (char vocabularies at 1024 threads: a 16-lane group = a DPP row, the butterfly 8, 4, 2, 1 as row rotations)
+            acc = sub16_sum(acc);
         } else {
             for (int o = tpv >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
         }
@@ -171,12 +171,6 @@ __device__ __forceinline__ void row_logits(const DecDev& a, const float* __restr
     greedy_tok = block_argmax(bestv, besti, red, redi);
     sample_tok = block_argmax(bests, bestsi, red, redi);
     if (tid == 0) a.tok_out[(size_t)(t - 1) * B + b] = greedy_tok;
-}
-
-__device__ __forceinline__ float sub32_sum(float v) {  // sum over a 32-lane half-wave: the xor butterfly 16, 8, 4, 2, 1 without the LDS (las_common.h)
-    v = xor16_sum(v);
-    v += dpp_f<0x128>(v); v += dpp_f<0x124>(v); v += dpp_f<0x122>(v); v += dpp_f<0x121>(v);
-    return v;
 }
 
 // LDS carve shared by the forward and backward row kernels
@@ -234,52 +228,92 @@ __device__ __forceinline__ void loc_conv_fwd(const RowLds& L, const DecDev& a, i
     }
 }
 
+// alpha is exactly 0 beyond len (exp underflow of the -1e8 replace-mask): the frames a context or its gradient has to visit
+__device__ __forceinline__ int att_lim(const int len, const int Tp) { return len > 0 ? (len < Tp ? len : Tp) : Tp; }
+
+// Finish `layer`'s cell for one row: from the pre-activations of step t_out - 1 in a.gates to the activated gates (written back for the
+// gradient), c and h of slot t_out.  keep(d, h) receives every h (the row kernels' LDS copy, the wide path's bf16 operand rows).  The
+// forward twin of cell_bwd_row.  (pf_fwd_row and the MFMA cell epilogues of the wide path carry their gates in registers: their own code.)
+template <int CELL, bool FAST, typename Keep>
+__device__ __forceinline__ void cell_fwd_row(const DecDev& a, const int layer, const int t_out, const int b, const int tid, const int nthreads,
+                                             Keep&& keep) {
+    constexpr int G = CELL == LAS_CELL_LSTM ? 4 : 1;
+    const int B = a.B, D = a.D, U = a.U, GD = G * D;
+    float* gp = a.gates + (((size_t)layer * U + (t_out - 1)) * B + b) * GD;
+    float* hnew = a.hs + (((size_t)layer * (U + 1) + t_out) * B + b) * D;
+    for (int d = tid; d < D; d += nthreads) {
+        float h;
+        if (CELL == LAS_CELL_LSTM) {
+            const float* cprev = a.cs + (((size_t)layer * (U + 1) + (t_out - 1)) * B + b) * D;
+            float* cnew = a.cs + (((size_t)layer * (U + 1) + t_out) * B + b) * D;
+            const float gi = sigm<FAST>(gp[d]);
+            const float gj = tanhx<FAST>(gp[D + d]);
+            const float gf = sigm<FAST>(gp[2 * D + d] + a.fb);
+            const float go = sigm<FAST>(gp[3 * D + d]);
+            // c = cprev gf + gi gj, spelled out: left to the compiler, which of the two products is fused depends on the surrounding code, and
+            // the callers must agree with each other, with the MFMA cell epilogue of the wide path (the launch-per-phase form is compared
+            // with it bit for bit) and with results recorded earlier.  These are the forms the copies this replaces compiled to: speed mode
+            // fuses cprev gf, parity mode gi gj.
+            const float c = FAST ? fmaf(cprev[d], gf, gi * gj) : fmaf(gi, gj, cprev[d] * gf);
+            h = tanhx<FAST>(c) * go;
+            gp[d] = gi; gp[D + d] = gj; gp[2 * D + d] = gf; gp[3 * D + d] = go;
+            cnew[d] = c;
+        } else {
+            h = tanhx<FAST>(gp[d]);
+        }
+        hnew[d] = h;
+        keep(d, h);
+    }
+}
+
+// The head of a per-step row kernel (one 1024-thread workgroup per utterance): finish the top layer's cell of step t-1 (h also to hl in
+// LDS), its vocabulary projection + arg-max (+ Gumbel sample) where the step needs them, and the token entering step t (-1: the greedy
+// token, -2: the sample; written back).  false: t == U, the call only finished the last cell.
+template <int CELL, bool FAST>
+__device__ __forceinline__ bool step_prologue(const DecDev& a, const int t, const int b, const int tid, float* hl, float* red, int* redi, int& tok) {
+    const int B = a.B, U = a.U;
+    int greedy_tok = 1, sample_tok = 1;
+    if (t > 0) {
+        cell_fwd_row<CELL, FAST>(a, a.NL - 1, t, b, tid, RNT, [&](const int d, const float h) { hl[d] = h; });
+        __syncthreads();
+        if (logits_here(a, t, t < U ? a.tok_in[(size_t)t * B + b] : 0)) row_logits<FAST>(a, hl, t, b, tid, red, redi, greedy_tok, sample_tok);
+    }
+    if (t >= U) return false;
+    tok = a.tok_in[(size_t)t * B + b];
+    if (tok == -1) tok = greedy_tok;
+    else if (tok == -2) tok = sample_tok;
+    if (tid == 0) a.tok_in[(size_t)t * B + b] = tok;
+    return true;
+}
+
+// softmax over the Tp energies in ev (LDS), in place, and the alignment row of step t (the f32 / bf16 per-step rows; barriers inside)
+__device__ __forceinline__ void row_softmax(const DecDev& a, const int t, const int b, const int tid, float* ev, float* red) {
+    const int Tp = a.Tp;
+    float m = -INFINITY;
+    for (int i = tid; i < Tp; i += RNT) m = fmaxf(m, ev[i]);
+    m = block_max<RNT>(m, red);
+    float ssum = 0.f;
+    for (int i = tid; i < Tp; i += RNT) { const float e = expf(ev[i] - m); ev[i] = e; ssum += e; }
+    ssum = block_sum<RNT>(ssum, red);
+    const float inv = 1.0f / ssum;
+    float* arow = a.alphas + ((size_t)t * a.B + b) * Tp;
+    for (int i = tid; i < Tp; i += RNT) { const float al = ev[i] * inv; ev[i] = al; arow[i] = al; }
+    __syncthreads();
+}
+
 // ------------------------------------------------------------------------------------------------
 // forward row kernel
 // ------------------------------------------------------------------------------------------------
 template <int CELL, bool FAST, bool LOC>
 __global__ __launch_bounds__(RNT) void dec_step_fwd_kernel(DecDev a, int t) {
-    constexpr int G = CELL == LAS_CELL_LSTM ? 4 : 1;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const RowLds L = carve(sm, a, false);
     const int b = blockIdx.x, tid = threadIdx.x;
     const int B = a.B, Tp = a.Tp, Hd = a.Hd, A = a.A, D = a.D, NL = a.NL, E = a.E, V = a.V, U = a.U;
-    const int S = D * NL, TOP = NL - 1, GD = G * D, I0D = E + Hd + D;
-    int greedy_tok = 1, sample_tok = 1;
+    const int S = D * NL, TOP = NL - 1, I0D = E + Hd + D;
 
-    if (t > 0) {  // ---- finish the top layer's cell of step t-1
-        float* gp = a.gates + (((size_t)TOP * U + (t - 1)) * B + b) * GD;
-        float* hnew = a.hs + (((size_t)TOP * (U + 1) + t) * B + b) * D;
-        for (int d = tid; d < D; d += RNT) {
-            float h;
-            if (CELL == LAS_CELL_LSTM) {
-                const float* cprev = a.cs + (((size_t)TOP * (U + 1) + (t - 1)) * B + b) * D;
-                float* cnew = a.cs + (((size_t)TOP * (U + 1) + t) * B + b) * D;
-                const float gi = sigm<FAST>(gp[d]);
-                const float gj = tanhx<FAST>(gp[D + d]);
-                const float gf = sigm<FAST>(gp[2 * D + d] + a.fb);
-                const float go = sigm<FAST>(gp[3 * D + d]);
-                const float c = cprev[d] * gf + gi * gj;
-                h = tanhx<FAST>(c) * go;
-                gp[d] = gi; gp[D + d] = gj; gp[2 * D + d] = gf; gp[3 * D + d] = go;
-                cnew[d] = c;
-            } else {
-                h = tanhx<FAST>(gp[d]);
-            }
-            hnew[d] = h;
-            L.hl[d] = h;
-        }
-        __syncthreads();
-        if (logits_here(a, t, t < U ? a.tok_in[(size_t)t * B + b] : 0)) {  // vocab projection + argmax (+ Gumbel sample) of step t-1
-            row_logits<FAST>(a, L.hl, t, b, tid, L.red, L.redi, greedy_tok, sample_tok);
-        }
-    }
-    if (t >= U) return;
-
-    int tok = a.tok_in[(size_t)t * B + b];
-    if (tok == -1) tok = greedy_tok;
-    else if (tok == -2) tok = sample_tok;
-    if (tid == 0) a.tok_in[(size_t)t * B + b] = tok;
+    int tok;
+    if (!step_prologue<CELL, FAST>(a, t, b, tid, L.hl, L.red, L.redi, tok)) return;
 
     for (int i = tid; i < S; i += RNT) {
         const int l = i / D, d = i % D;
@@ -365,19 +399,10 @@ __global__ __launch_bounds__(RNT) void dec_step_fwd_kernel(DecDev a, int t) {
         }
     }
     __syncthreads();
-    float m = -INFINITY;
-    for (int i = tid; i < Tp; i += RNT) m = fmaxf(m, L.ev[i]);
-    m = block_max<RNT>(m, L.red);
-    float ssum = 0.f;
-    for (int i = tid; i < Tp; i += RNT) { const float e = expf(L.ev[i] - m); L.ev[i] = e; ssum += e; }
-    ssum = block_sum<RNT>(ssum, L.red);
-    const float inv = 1.0f / ssum;
-    float* arow = a.alphas + ((size_t)t * B + b) * Tp;
-    for (int i = tid; i < Tp; i += RNT) { const float al = L.ev[i] * inv; L.ev[i] = al; arow[i] = al; }
-    __syncthreads();
+    row_softmax(a, t, b, tid, L.ev, L.red);
 
     float* xrow = a.xin0 + ((size_t)t * B + b) * I0D;
-    const int lim = len > 0 ? (len < Tp ? len : Tp) : Tp;   // alpha is exactly 0 beyond len (exp underflow)
+    const int lim = att_lim(len, Tp);
     {   // context = sum_t alpha[t] * enc[b,t,:]  : 128 float4 lanes over Hd x RNH frame groups, 8 loads in flight
         const int h4 = tid & 127, half = tid >> 7;
         for (int h0 = h4; h0 < Hd / 4; h0 += 128) {
@@ -436,25 +461,6 @@ __device__ __forceinline__ void unpack8(const uint4 v, float* f) {
     f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
     f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
 }
-// sum over a 16-lane group (a DPP row), in every lane.  Row rotations by 8, 4, 2, 1 on the VALU's data-parallel path instead of four
-// __shfl_xor = four ds_bpermute round trips through the LDS queue (a dependent chain of ~100-cycle operations at the end of every frame group
-// of the energies): BIT-identical to the xor butterfly -- after the step with distance d every lane equals its partner at distance d
-// (a + b == b + a), so the value a rotation by d / 2 brings is the value the xor partner holds.
-#ifndef LAS_SUB16_DPP
-#define LAS_SUB16_DPP 1
-#endif
-__device__ __forceinline__ float sub16_sum(float v) {
-#if LAS_SUB16_DPP
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));     // row_ror:8
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false));     // row_ror:4
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, false));     // row_ror:2
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false));     // row_ror:1
-#else
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-#endif
-    return v;
-}
 // the speed mode's operand copies in one launch: job y = plain bf16 copy of n elements (R == 0) or row-pair interleaved copy of
 // `batch` matrices: src [batch][R][C] fp32 -> dst [batch][ceil(R/2)][C][2] bf16, rows 2r and 2r+1 interleaved per column (zero past R)
 struct BfCopyJob { const float* src; unsigned short* dst; size_t n; int R, C, batch; };
@@ -492,18 +498,15 @@ struct BfLds {
 // only free after the query projection); the rows do not change over the loop, a CU runs one loop workgroup, and the row state needs
 // 41 KB of the 160 KB: ENC_RES slabs of 32 Hd bytes (16 frames; 7 x 16 KB at Hd = 512 = 112 of 160 frames) are copied in once, the
 // rest is streamed per step -- few enough registers to be requested at the head of the step with the other bulk loads.
-#ifndef LAS_ENC_RES_F
-#define LAS_ENC_RES_F 7
-#endif
-#ifndef LAS_ENC_RES_B
-#define LAS_ENC_RES_B 0
-#endif
+// Forward: 7 slabs (what fits next to the row state and scratch; 0.25 us per step net of the LDS reads).  Gradient rows: 0 -- tried: the same
+// residency there; result: 0.7 us slower per step (their encoder rows are requested at the head of the step and have arrived when the
+// softmax gradient needs them; read from LDS they sit on the dependent chain).
 template <int NE, bool LOC, bool BWD = false> struct EncRes {
-    static constexpr int M = BWD ? LAS_ENC_RES_B : LAS_ENC_RES_F;
+    static constexpr int M = BWD ? 0 : 7;
     static constexpr int N = LOC ? 0 : (NE < M ? NE : M);
 };
 __host__ __device__ __forceinline__ size_t enc_res_bytes(const DecDev& a, bool loc, int ne, bool bwd = false) {
-    const int m = bwd ? LAS_ENC_RES_B : LAS_ENC_RES_F;
+    const int m = bwd ? 0 : 7;
     return loc ? 0 : (size_t)(ne < m ? ne : m) * 32 * a.Hd;
 }
 static int loop_ne(int Tp) { return Tp <= 128 ? 8 : Tp <= 160 ? 10 : Tp <= 192 ? 12 : 14; }
@@ -684,47 +687,14 @@ __device__ __forceinline__ void loc_stage_lds(const BfLds& L, const DecDev& a, c
 template <int CELL, int NJ>
 __global__ __launch_bounds__(RNT) void dec_step_fwd_bf_kernel(DecDev a, int t) {
     constexpr bool FAST = true;
-    constexpr int G = CELL == LAS_CELL_LSTM ? 4 : 1;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const BfLds L = carve_bf(sm, a);
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int B = a.B, Tp = a.Tp, Hd = a.Hd, A = a.A, D = a.D, NL = a.NL, E = a.E, V = a.V, U = a.U;
-    const int S = D * NL, TOP = NL - 1, GD = G * D, I0D = E + Hd + D;
-    int greedy_tok = 1, sample_tok = 1;
+    const int S = D * NL, TOP = NL - 1, I0D = E + Hd + D;
 
-    if (t > 0) {  // ---- finish the top layer's cell of step t-1
-        float* gp = a.gates + (((size_t)TOP * U + (t - 1)) * B + b) * GD;
-        float* hnew = a.hs + (((size_t)TOP * (U + 1) + t) * B + b) * D;
-        for (int d = tid; d < D; d += RNT) {
-            float h;
-            if (CELL == LAS_CELL_LSTM) {
-                const float* cprev = a.cs + (((size_t)TOP * (U + 1) + (t - 1)) * B + b) * D;
-                float* cnew = a.cs + (((size_t)TOP * (U + 1) + t) * B + b) * D;
-                const float gi = sigm<FAST>(gp[d]);
-                const float gj = tanhx<FAST>(gp[D + d]);
-                const float gf = sigm<FAST>(gp[2 * D + d] + a.fb);
-                const float go = sigm<FAST>(gp[3 * D + d]);
-                const float c = cprev[d] * gf + gi * gj;
-                h = tanhx<FAST>(c) * go;
-                gp[d] = gi; gp[D + d] = gj; gp[2 * D + d] = gf; gp[3 * D + d] = go;
-                cnew[d] = c;
-            } else {
-                h = tanhx<FAST>(gp[d]);
-            }
-            hnew[d] = h;
-            L.hl[d] = h;
-        }
-        __syncthreads();
-        if (logits_here(a, t, t < U ? a.tok_in[(size_t)t * B + b] : 0)) {  // vocab projection + argmax (+ Gumbel sample) of step t-1
-            row_logits<FAST>(a, L.hl, t, b, tid, L.red, L.redi, greedy_tok, sample_tok);
-        }
-    }
-    if (t >= U) return;
-
-    int tok = a.tok_in[(size_t)t * B + b];
-    if (tok == -1) tok = greedy_tok;
-    else if (tok == -2) tok = sample_tok;
-    if (tid == 0) a.tok_in[(size_t)t * B + b] = tok;
+    int tok;
+    if (!step_prologue<CELL, FAST>(a, t, b, tid, L.hl, L.red, L.redi, tok)) return;
 
     for (int i = tid; i < S; i += RNT) {
         const int l = i / D, d = i % D;
@@ -779,7 +749,7 @@ __global__ __launch_bounds__(RNT) void dec_step_fwd_bf_kernel(DecDev a, int t) {
     __syncthreads();
 
     const int len = a.enc_len[b];
-    const int lim = len > 0 ? (len < Tp ? len : Tp) : Tp;   // alpha is exactly 0 beyond len (exp underflow)
+    const int lim = att_lim(len, Tp);
     {   // energies: a 16-lane group per encoder frame, 16-byte key loads, 4 frames in flight
         float q8[NJ][8], u8[NJ][8];
 #pragma unroll
@@ -824,16 +794,7 @@ __global__ __launch_bounds__(RNT) void dec_step_fwd_bf_kernel(DecDev a, int t) {
         }
     }
     __syncthreads();
-    float m = -INFINITY;
-    for (int i = tid; i < Tp; i += RNT) m = fmaxf(m, L.ev[i]);
-    m = block_max<RNT>(m, L.red);
-    float ssum = 0.f;
-    for (int i = tid; i < Tp; i += RNT) { const float e = expf(L.ev[i] - m); L.ev[i] = e; ssum += e; }
-    ssum = block_sum<RNT>(ssum, L.red);
-    const float inv = 1.0f / ssum;
-    float* arow = a.alphas + ((size_t)t * B + b) * Tp;
-    for (int i = tid; i < Tp; i += RNT) { const float al = L.ev[i] * inv; L.ev[i] = al; arow[i] = al; }
-    __syncthreads();
+    row_softmax(a, t, b, tid, L.ev, L.red);
 
     float* xrow = a.xin0 + ((size_t)t * B + b) * I0D;
     unsigned short* xb = a.xbf + (size_t)b * I0D;
@@ -893,9 +854,6 @@ __global__ __launch_bounds__(RNT) void dec_step_fwd_bf_kernel(DecDev a, int t) {
 // recurrent state, so every load is issued when the kernel starts and only arithmetic sits on the dependent
 // chain; LDS-only barriers keep the loads in flight (a __syncthreads() would drain vmcnt at every phase).
 // ------------------------------------------------------------------------------------------------
-#ifndef LAS_LOC_WS_EARLY
-#define LAS_LOC_WS_EARLY 1        // location-aware forward rows: 1 = the Ws fragments, 2 = also the keys, requested in FRONT of the conv (0: behind it, with the rest)
-#endif
 #ifdef LAS_ROW_STAMPS   // development aid (tools/micro/bench_rows.hip): phase timestamps of workgroup 0
 __device__ unsigned long long g_stamps[32];
 #define STAMPX(i) do { if (tid == 0 && b == 0) g_stamps[i] = wall_clock64(); } while (0)
@@ -939,25 +897,9 @@ __device__ __forceinline__ void put4_bf16(const __amdgpu_buffer_rsrc_t rs, const
     const float v1 = dpp_f<0xF9>(v), v2 = dpp_f<0xFE>(v), v3 = dpp_f<0xFF>(v);
     if (!(col & 3)) granule16_store(rs, (unsigned)((row_gran + (col >> 2)) * 16), tag, f2bf2(v, v1), f2bf2(v2, v3), local);
 }
-// Where the row kernels issue the bulk loads that are consumed two phases later (measured with tools/micro/bench_fused.hip,
-// B = 48, T' = 160, profiles/r3_speller_phase_stamps.txt):
-//   LAS_E8_LATE (forward, the context's encoder rows, 164 KB per row and step): inside the energies phase instead of in front of the
-//       q reduction -- the q-reduction phase shrinks 1.32 -> 0.56 us, the energies phase grows 2.28 -> 3.12 us: 12.48 vs 12.51 us
-//       per step, no gain (a wave that waits to issue vector memory is not covered by the other waves' transcendentals) -> off;
-//   LAS_W8_LATE (backward, the Ws rows of the state gradient, 128 KB): one load per frame inside the energies-gradient loop instead
-//       of all at once in front of a barrier: 10.75 -> 10.50 us per step -> on.
-#ifndef LAS_E8_LATE
-#define LAS_E8_LATE 0
-#endif
-#ifndef LAS_E8_BEHIND_LOOP
-#define LAS_E8_BEHIND_LOOP 1      // the loop kernels' streamed encoder slabs are requested behind the query reduction too (bench_fused: 10.2-10.4 -> 10.0-10.1 us per forward step)
-#endif
-#ifndef LAS_E8_EARLY
-#define LAS_E8_EARLY 0      // (the streamed slabs requested at the head of the step instead of behind the query projection: 10.2 vs 10.0 us, 6 spilled VGPRs)
-#endif
-#ifndef LAS_W8_LATE
-#define LAS_W8_LATE 1
-#endif
+// Where the row kernels issue the bulk loads that are consumed two phases later was measured with tools/micro/bench_fused.hip
+// (B = 48, T' = 160, profiles/r3_speller_phase_stamps.txt); each finding stands as "tried / result" at the code that won (the
+// encoder rows in pf_fwd_row behind the query reduction, the Ws rows in pf_bwd_row inside the energies-gradient loop).
 #ifndef LAS_ABL_SP
 #define LAS_ABL_SP 0   // development: bit mask of parts of the forward row to leave out (timing experiments only; make abl_sp ABL=<mask>)
 #endif
@@ -982,8 +924,9 @@ __device__ __forceinline__ void pf_fwd_row(const DecDev& a, const int t, const i
     const int S = D, GD = G * D, I0D = E + Hd + D, A8 = A >> 3, A4 = A >> 2, H4 = Hd >> 2, S2 = (S + 1) >> 1, Tp2 = (Tp + 1) >> 1;
 
     uint4 w8[8];
-    if (LOC && LAS_LOC_WS_EARLY) {
-        // (experiment) the query projection's Ws fragments in front of the conv: they are the first bulk operand the step consumes
+    if (LOC) {
+        // location-aware rows: the query projection's Ws fragments are requested in FRONT of the conv -- they are the first bulk operand the
+        // step consumes.  (Tried: behind the conv with the rest, and the keys in front of it as well; result: this placement was kept.)
         const int a4c_ = a4 < A4 ? a4 : A4 - 1;
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -992,14 +935,6 @@ __device__ __forceinline__ void pf_fwd_row(const DecDev& a, const int t, const i
         }
     }
     uint4 k8[NK];
-    if (LOC && LAS_LOC_WS_EARLY > 1) {
-        const int a8c_ = a8 < A8 ? a8 : A8 - 1;
-#pragma unroll
-        for (int u = 0; u < NK; ++u) {
-            const int tt = grp + 64 * u, ttc = tt < Tp ? tt : Tp - 1;
-            k8[u] = reinterpret_cast<const uint4*>(a.keysbf)[((size_t)(LOOP ? b : op_row(a, b)) * Tp + ttc) * A8 + a8c_];
-        }
-    }
     if (LOC) {
         // f = conv1d(alpha_{t-1}): nothing in it depends on the gates of step t-1, so it runs while they are on their way -- and
         // BEFORE the step's bulk loads are issued: behind them their 60 destination registers are live and the conv's 40 spill.  The
@@ -1041,7 +976,7 @@ __device__ __forceinline__ void pf_fwd_row(const DecDev& a, const int t, const i
     const int len = a.enc_len[b];
     const int bo = LOOP ? b : op_row(a, b);          // (a search's hypothesis rows may share their utterance's operand block)
     const int a4c = a4 < A4 ? a4 : A4 - 1, a8c = a8 < A8 ? a8 : A8 - 1, h4c = h4 < H4 ? h4 : H4 - 1;
-    if (!(LOC && LAS_LOC_WS_EARLY)) {
+    if (!LOC) {
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int kp = kg + 32 * u, kpc = kp < S2 ? kp : S2 - 1;
@@ -1049,12 +984,10 @@ __device__ __forceinline__ void pf_fwd_row(const DecDev& a, const int t, const i
         }
     }
     const float4 u40 = reinterpret_cast<const float4*>(a.u)[a8c * 2], u41 = reinterpret_cast<const float4*>(a.u)[a8c * 2 + 1];
-    if (!(LOC && LAS_LOC_WS_EARLY > 1)) {
 #pragma unroll
-        for (int u = 0; u < NK; ++u) {
-            const int tt = grp + 64 * u, ttc = tt < Tp ? tt : Tp - 1;
-            k8[u] = reinterpret_cast<const uint4*>(a.keysbf)[(LAS_ABL_SP & 1024) ? (size_t)(tid & 63) : ((size_t)bo * Tp + ttc) * A8 + a8c];
-        }
+    for (int u = 0; u < NK; ++u) {
+        const int tt = grp + 64 * u, ttc = tt < Tp ? tt : Tp - 1;
+        k8[u] = reinterpret_cast<const uint4*>(a.keysbf)[(LAS_ABL_SP & 1024) ? (size_t)(tid & 63) : ((size_t)bo * Tp + ttc) * A8 + a8c];
     }
     constexpr int NEL = LOOP ? EncRes<NE, LOC>::N : 0;      // encoder slabs resident in LDS (loop kernels): see EncRes
     constexpr int NER = NE - NEL > 0 ? NE - NEL : 1;
@@ -1064,10 +997,6 @@ __device__ __forceinline__ void pf_fwd_row(const DecDev& a, const int t, const i
         const int tpc = tp < Tp2 ? tp : Tp2 - 1;
         e8[u - NEL] = reinterpret_cast<const uint4*>(a.encbf2)[(LAS_ABL_SP & 2048) ? (size_t)(tid & 63) : ((size_t)bo * Tp2 + tpc) * H4 + h4c];
     };
-    if (NEL > 0 && LAS_E8_EARLY) {                            // the streamed slabs ride with the other bulk loads
-#pragma unroll
-        for (int u = NEL; u < NE; ++u) e8_load(u);
-    }
     STAMPX(1);
     if (LOOP && t > 0 && wv * 64 < D) {   // gates of step t-1 from the product workgroups: the data is the flag
         const __amdgpu_buffer_rsrc_t rs = granule_rsrc(a.lp.gC);
@@ -1158,17 +1087,16 @@ __device__ __forceinline__ void pf_fwd_row(const DecDev& a, const int t, const i
     // encoder rows for the context (the Ws registers are free now), consumed after the softmax.  164 KB per row and step: at the
     // L1's 64 B / clock that is 1.07 us of vector-memory issue.  Issued here -- by all 16 waves at once, in front of the q
     // reduction that only waves 0-1 execute -- those two waves sat in the issue queue for ~1 us while the other 14 waited at the
-    // barrier (phase stamps: 1.32 us for a 16-term sum).  LAS_E8_LATE: the loads are issued in NK portions between the frames of
-    // the energies phase instead, where the other waves of a SIMD have transcendental work to cover a wave that waits to issue.
-    const int lim = len > 0 ? (len < Tp ? len : Tp) : Tp;   // alpha is exactly 0 beyond len (exp underflow)
+    // barrier (phase stamps: 1.32 us for a 16-term sum).
+    const int lim = att_lim(len, Tp);
     // The per-step kernel (!LOOP: a beam search's 256 rows on 256 CUs at once, not a training batch's 48) requests them BEHIND the
     // reduction: with every CU of the chip asking for its 164 KB at the same moment the reducing waves waited 4.6 us behind the requests
     // (r5 stamps, tools/probe_pf_stamps.py); the rows then land under the energies.
-    constexpr bool E8_BEHIND = ((!LOOP && NEL == 0) || (LOOP && LAS_E8_BEHIND_LOOP)) && !LAS_E8_LATE;
-    if (!E8_BEHIND && !LAS_E8_LATE && (NEL == 0 || !LAS_E8_EARLY)) {
-#pragma unroll
-        for (int u = NEL; u < NE; ++u) e8_load(u);
-    }
+    // The loop kernels' streamed slabs are requested behind it too (tried: in front of it; result: behind it a forward step in
+    // bench_fused takes 10.0-10.1 us instead of 10.2-10.4).  Tried: the streamed slabs at the head of the step with the other bulk loads; result: 10.2 vs 10.0 us
+    // and 6 spilled VGPRs.  Tried: the loads in NK portions between the frames of the energies phase (the q-reduction phase shrinks
+    // 1.32 -> 0.56 us, the energies phase grows 2.28 -> 3.12 us); result: 12.48 vs 12.51 us per step, no gain -- a wave that waits to
+    // issue vector memory is not covered by the other waves' transcendentals.
     for (int i = tid; i < A; i += RNT) {
         float q = 0.f;
 #pragma unroll
@@ -1176,10 +1104,8 @@ __device__ __forceinline__ void pf_fwd_row(const DecDev& a, const int t, const i
         L.qv[i] = q;
     }
     lds_barrier();
-    if (E8_BEHIND) {
 #pragma unroll
-        for (int u = NEL; u < NE; ++u) e8_load(u);
-    }
+    for (int u = NEL; u < NE; ++u) e8_load(u);
     STAMPX(4);
     {   // energies from the prefetched keys
         const float um = a8 < A8 ? 1.f : 0.f;        // lanes past the attention width carry clamped operands
@@ -1209,11 +1135,6 @@ __device__ __forceinline__ void pf_fwd_row(const DecDev& a, const int t, const i
         }
 #pragma unroll
         for (int u = 0; u < NK; ++u) {
-            if (LAS_E8_LATE && NEL == 0) {
-#pragma unroll
-                for (int v = u * NE / NK; v < (u + 1) * NE / NK; ++v) e8_load(v);
-                __builtin_amdgcn_sched_barrier(0);       // keep the portion in front of THIS frame's arithmetic
-            }
             const int tt = grp + 64 * u;
             float part = 0.f;
             if (tt < len && tt < Tp) {
@@ -1432,7 +1353,7 @@ __global__ __launch_bounds__(RNT) void dec_beam_rows4_kernel(DecDev a) {
     lds_barrier();
     STAMPB(3);
     // the encoder rows for the context (the Ws registers are free now), consumed after the softmax -- once for the four rows
-    const int lim = len > 0 ? (len < Tp ? len : Tp) : Tp;
+    const int lim = att_lim(len, Tp);
     for (int i = tid; i < R * A; i += RNT) {
         const int r = i / A, col = i - r * A;
         float q = 0.f;
@@ -1727,6 +1648,8 @@ __global__ __launch_bounds__(RNT) void dec_loop_fwd_kernel(DecDev a) {
 // gate nonlinearity of a non-top layer (multi-layer Speller only)
 template <int CELL, bool FAST>
 __global__ __launch_bounds__(256) void dec_pointwise_fwd_kernel(DecDev a, int layer, int t) {
+    // Not cell_fwd_row: in speed mode this kernel has always rounded BOTH products of c (the compiler packs them into one v_pk_mul_f32
+    // and adds), one ulp away from the fused forms there -- kept, so that multi-layer runs on the per-utterance rows reproduce.
     constexpr int G = CELL == LAS_CELL_LSTM ? 4 : 1;
     const int b = blockIdx.x, B = a.B, D = a.D, U = a.U, GD = G * D;
     float* gp = a.gates + (((size_t)layer * U + t) * B + b) * GD;
@@ -1825,7 +1748,7 @@ __global__ __launch_bounds__(RNT) void dec_step_bwd_kernel(DecDev a, int t_att, 
         __syncthreads();
         if (loc) loc_conv_fwd(L, a, tid);          // recompute f = conv1d(prev_align) (dfc is written for every frame below)
         const int len = a.enc_len[b];
-        const int lim = len > 0 ? (len < Tp ? len : Tp) : Tp;
+        const int lim = att_lim(len, Tp);
         {   // dalpha[t'] = dctx . enc[b,t',:]   (+ what step t+1's location conv sent back)
             // half-wave per frame, float4 over Hd, two frames (8 x 16-byte loads) in flight per lane
             const int sl = tid & 31, grp = tid >> 5;
@@ -2154,7 +2077,7 @@ __global__ __launch_bounds__(RNT) void dec_step_bwd_bf_kernel(DecDev a, int t_at
         for (int i = tid; i < A; i += RNT) L.qv[i] = a.Q[((size_t)t * B + b) * A + i];
         __syncthreads();
         const int len = a.enc_len[b];
-        const int lim = len > 0 ? (len < Tp ? len : Tp) : Tp;
+        const int lim = att_lim(len, Tp);
         {   // dalpha[t'] = dctx . enc[b,t',:] : one wave per frame, 8 frames in flight
             for (int tt = wv; tt < Tp; tt += 8 * RNW) {
                 float acc[8];
@@ -2315,9 +2238,6 @@ __global__ __launch_bounds__(RNT) void dec_step_bwd_bf_kernel(DecDev a, int t_at
 // LOOP (dec_loop_bwd_kernel): one iteration of a persistent row workgroup: the dXin0 row of step t_att (context and state
 // gradient) arrives as granules from the product workgroups, the bf16 gate gradient of step t_cell leaves as granules, dC and
 // the running du column are carried in registers.
-#ifndef LAS_KEYS_HOISTED
-#define LAS_KEYS_HOISTED 1
-#endif
 // the keys of the energies gradient: one column pair per lane, frame wv + 16 u.  They do not change over the loop: the loop kernel
 // loads them ONCE (NE registers) -- requested per step they cost 1.2 us of the 10.5 (tools/micro/bench_fused.hip, round 4)
 template <int NE>
@@ -2411,7 +2331,7 @@ __device__ __forceinline__ void pf_bwd_row(const DecDev& a, const int t_att, con
                 const int t2 = wv + RNW * u, t2c = t2 < Tp ? t2 : Tp - 1;
                 k2[u] = (a.actS + LAS_ACT_HDR)[(LAS_ABL_SP & 256) ? (size_t)(tid & 63) : (((size_t)ta * B + b) * Tp + t2c) * A2 + c2c];
             }
-        } else if (LOOP && LAS_KEYS_HOISTED) {
+        } else if (LOOP) {
 #pragma unroll
             for (int u = 0; u < NE; ++u) k2[u] = k2h[u];
         } else {
@@ -2469,7 +2389,7 @@ __device__ __forceinline__ void pf_bwd_row(const DecDev& a, const int t_att, con
                     const int t2 = wv + RNW * u, t2c = t2 < Tp ? t2 : Tp - 1;
                     k2[u] = (a.actS + LAS_ACT_HDR)[(LAS_ABL_SP & 256) ? (size_t)(tid & 63) : (((size_t)ta * B + b) * Tp + t2c) * A2 + c2c];
                 }
-            } else if (LOOP && LAS_KEYS_HOISTED && !LOC) {
+            } else if (LOOP && !LOC) {
     #pragma unroll
                 for (int u = 0; u < NE; ++u) k2[u] = k2h[u];
             } else {
@@ -2524,7 +2444,7 @@ __device__ __forceinline__ void pf_bwd_row(const DecDev& a, const int t_att, con
     if (tid < D) dhs[tid] = 0.f;
     if (att) {
         const int t = t_att;
-        const int lim = len > 0 ? (len < Tp ? len : Tp) : Tp;
+        const int lim = att_lim(len, Tp);
         if (tid < (Hd >> 1)) dcp[tid] = f2bf2(dcv.x, dcv.y);
         if (tid < Tp) L.ev[tid] = alv;
         if (tid < A) L.qv[tid] = qd;
@@ -2555,18 +2475,14 @@ __device__ __forceinline__ void pf_bwd_row(const DecDev& a, const int t_att, con
             }
         }
         // the state-gradient operand (the encoder registers are free), consumed after the energies: 128 KB per row and step.
-        // LAS_W8_LATE: issued one load per frame inside the energies-gradient loop (transcendental work of the other waves covers
-        // a wave that waits to issue) instead of all at once in front of a barrier -- see pf_fwd_row
+        // Issued one load per frame inside the energies-gradient loop (transcendental work of the other waves covers a wave that
+        // waits to issue).  Tried: all at once here, in front of the barrier; result: 10.75 vs 10.50 us per step (bench_fused).
         uint4 w8[8];
         auto w8_load = [&](const int u) __attribute__((always_inline)) {
             const int kk = grp + 64 * u;
             const int kkc = kk < S ? kk : S - 1;
             w8[u] = reinterpret_cast<const uint4*>(a.Wsbf)[(LAS_ABL_SP & 512) ? (size_t)(tid & 63) : (size_t)kkc * A8 + a8c];
         };
-        if (!LAS_W8_LATE) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) w8_load(u);
-        }
         lds_barrier();
     STAMPX(14);
         float de_own = 0.f;
@@ -2601,7 +2517,7 @@ __device__ __forceinline__ void pf_bwd_row(const DecDev& a, const int t_att, con
             }
 #pragma unroll
             for (int u = 0; u < NE; ++u) {
-                if (LAS_W8_LATE && (!LOC || ACTS) && u < 8) { w8_load(u); __builtin_amdgcn_sched_barrier(0); }
+                if ((!LOC || ACTS) && u < 8) { w8_load(u); __builtin_amdgcn_sched_barrier(0); }
                 const int t2 = wv + RNW * u;
                 const float de = t2 < lim ? dal[t2] : 0.f;
                 float v0, v1;
@@ -2637,7 +2553,7 @@ __device__ __forceinline__ void pf_bwd_row(const DecDev& a, const int t_att, con
                 reinterpret_cast<float2*>(L.scr + wv * 2 * A)[lane] = make_float2(dq0, dq1);
                 reinterpret_cast<float2*>(L.scr + wv * 2 * A + A)[lane] = make_float2(du0, du1);
             }
-            if (LAS_W8_LATE && LOC && !acts) {   // location-aware, recomputing: the loop above is at the register limit (Wf columns, d v rows) -- the Ws rows are
+            if (LOC && !acts) {   // location-aware, recomputing: the loop above is at the register limit (Wf columns, d v rows) -- the Ws rows are
 #pragma unroll                  // requested here; the d f product and the dq / du reduction below cover their latency
                 for (int u = 0; u < 8; ++u) w8_load(u);
             }
@@ -2771,7 +2687,7 @@ __global__ __launch_bounds__(RNT) void dec_loop_bwd_kernel(DecDev a) {
     }
     unsigned k2[NE] = {};
     const bool acts = a.actS && a.actS[0] == LAS_ACT_MAGIC;           // the forward rows kept their attention activations
-    if (LAS_KEYS_HOISTED && !LOC && !acts) bwd_keys_load<NE>(a, b, threadIdx.x, k2);      // (location-aware: the loop is at the register limit)
+    if (!LOC && !acts) bwd_keys_load<NE>(a, b, threadIdx.x, k2);      // (location-aware: the loop is at the register limit)
     for (int t = a.U - 1; t >= -1; --t) {
         int bb = b, tid = threadIdx.x;
         asm volatile("" : "+s"(bb), "+v"(tid));                       // see dec_loop_fwd_kernel

@@ -95,42 +95,14 @@ __device__ __forceinline__ unsigned wide_poll(const DecDev& a, __amdgpu_buffer_r
 template <int CELL, bool FAST>
 __global__ __launch_bounds__(RNT) void wide_state_kernel(DecDev a, WideDev w, int t) {
     kernarg_warm<(int)(sizeof(DecDev) + sizeof(WideDev))>();
-    constexpr int G = CELL == LAS_CELL_LSTM ? 4 : 1;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* hl = sm;                          // [D]
     float* red = sm + ((a.D + 3) & ~3);      // [32]
     int* redi = reinterpret_cast<int*>(red + 32);
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int B = a.B, D = a.D, NL = a.NL, U = a.U, S = D * NL, TOP = NL - 1, GD = G * D;
-    int greedy_tok = 1, sample_tok = 1;
-    if (t > 0) {
-        float* gp = a.gates + (((size_t)TOP * U + (t - 1)) * B + b) * GD;
-        float* hnew = a.hs + (((size_t)TOP * (U + 1) + t) * B + b) * D;
-        for (int d = tid; d < D; d += RNT) {
-            float h;
-            if (CELL == LAS_CELL_LSTM) {
-                const float* cprev = a.cs + (((size_t)TOP * (U + 1) + (t - 1)) * B + b) * D;
-                float* cnew = a.cs + (((size_t)TOP * (U + 1) + t) * B + b) * D;
-                const float gi = sigm<FAST>(gp[d]), gj = tanhx<FAST>(gp[D + d]);
-                const float gf = sigm<FAST>(gp[2 * D + d] + a.fb), go = sigm<FAST>(gp[3 * D + d]);
-                const float c = cprev[d] * gf + gi * gj;
-                h = tanhx<FAST>(c) * go;
-                gp[d] = gi; gp[D + d] = gj; gp[2 * D + d] = gf; gp[3 * D + d] = go;
-                cnew[d] = c;
-            } else {
-                h = tanhx<FAST>(gp[d]);
-            }
-            hnew[d] = h;
-            hl[d] = h;
-        }
-        __syncthreads();
-        if (logits_here(a, t, t < U ? a.tok_in[(size_t)t * B + b] : 0)) row_logits<FAST>(a, hl, t, b, tid, red, redi, greedy_tok, sample_tok);
-    }
-    if (t >= U) return;
-    int tok = a.tok_in[(size_t)t * B + b];
-    if (tok == -1) tok = greedy_tok;
-    else if (tok == -2) tok = sample_tok;
-    if (tid == 0) a.tok_in[(size_t)t * B + b] = tok;
+    const int B = a.B, D = a.D, NL = a.NL, U = a.U, S = D * NL, TOP = NL - 1;
+    int tok;
+    if (!step_prologue<CELL, FAST>(a, t, b, tid, hl, red, redi, tok)) return;
     for (int i = tid; i < S; i += RNT) {
         const int l = i / D, d = i - l * D;
         const float v = (l == TOP && t > 0) ? hl[d] : a.hs[(((size_t)l * (U + 1) + t) * B + b) * D + d];
@@ -379,7 +351,7 @@ __device__ __forceinline__ void wide_context_body(const DecDev& a, const WideDev
     // everything that does not depend on the alignment is requested first: the first four encoder rows of this thread's column chunk, and (slice
     // 0) the embedding row and h_0 -- behind the softmax each of them was a memory round trip of its own on the launch's critical path
     const int len = a.enc_len[b];
-    const int lim = len > 0 ? (len < Tp ? len : Tp) : Tp;   // alpha is exactly 0 beyond len (exp underflow)
+    const int lim = att_lim(len, Tp);
     const int c0 = hs_ * w.h4per, nch = (H4 - c0 < w.h4per ? H4 - c0 : w.h4per);
     const int ng = RNT / w.h4per;
     const int g = tid / w.h4per, ch = tid - g * w.h4per;
@@ -514,31 +486,14 @@ __global__ __launch_bounds__(RNT) void wide_attend_kernel(DecDev a, WideDev w, i
 template <int CELL, bool FAST>
 __global__ __launch_bounds__(256) void wide_pointwise_fwd_kernel(DecDev a, WideDev w, int layer, int t) {
     kernarg_warm<(int)(sizeof(DecDev) + sizeof(WideDev))>();
-    constexpr int G = CELL == LAS_CELL_LSTM ? 4 : 1;
-    const int b = blockIdx.x, B = a.B, D = a.D, U = a.U, GD = G * D;
-    float* gp = a.gates + (((size_t)layer * U + t) * B + b) * GD;
-    float* hnew = a.hs + (((size_t)layer * (U + 1) + t + 1) * B + b) * D;
+    const int b = blockIdx.x, B = a.B, D = a.D, U = a.U;
     const float* hup = a.hs + (((size_t)(layer + 1) * (U + 1) + t) * B + b) * D;
-    for (int d = threadIdx.x; d < D; d += 256) {
-        float h;
-        if (CELL == LAS_CELL_LSTM) {
-            const float* cprev = a.cs + (((size_t)layer * (U + 1) + t) * B + b) * D;
-            float* cnew = a.cs + (((size_t)layer * (U + 1) + t + 1) * B + b) * D;
-            const float gi = sigm<FAST>(gp[d]), gj = tanhx<FAST>(gp[D + d]);
-            const float gf = sigm<FAST>(gp[2 * D + d] + a.fb), go = sigm<FAST>(gp[3 * D + d]);
-            const float c = cprev[d] * gf + gi * gj;
-            h = tanhx<FAST>(c) * go;
-            gp[d] = gi; gp[D + d] = gj; gp[2 * D + d] = gf; gp[3 * D + d] = go;
-            cnew[d] = c;
-        } else {
-            h = tanhx<FAST>(gp[d]);
-        }
-        hnew[d] = h;
+    cell_fwd_row<CELL, FAST>(a, layer, t + 1, b, threadIdx.x, 256, [&](const int d, const float h) {
         if (FAST) {
             w.xu[(size_t)b * 2 * D + d] = f2bf(h);
             w.xu[(size_t)b * 2 * D + D + d] = f2bf(hup[d]);
         }
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
