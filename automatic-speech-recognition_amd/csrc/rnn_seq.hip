@@ -5,17 +5,25 @@
 // a workgroup owns (direction, batch tile) for all T steps, h/c never leave the CU (LDS + VGPRs),
 // the input projection x.W_ih+b was hoisted into one big K1 GEMM and arrives through `gates`.
 //
-//   LAS_PREC_F32 : fp32 FMA chains on the VALU, any H (parity mode).  Thread = hidden unit,
-//                  8 batch rows per workgroup, h broadcast from LDS, W_hh streamed from L2.
-//   LAS_PREC_BF16: v_mfma_f32_16x16x32_bf16.  16 batch rows per workgroup (one MFMA M-tile),
-//                  4 waves x 64 hidden units; every wave owns all G gates of its units so the gate
-//                  nonlinearity is lane-local on the accumulator layout.  W_hh is pre-packed into
-//                  MFMA B-fragment order (1 KiB contiguous per wave-load); as many fragments as fit
-//                  stay resident in LDS for the whole sweep, the rest stream from L2 each step.
-//                  Next step's x-projection is prefetched under the current step's MFMAs.
-// No grid barrier, no inter-workgroup traffic: directions and batch tiles are independent.
+// Map of this file (plan_sweep, in the host part, picks a SweepPath and, on SWEEP_BF16, a SweepKernel for every launch and query):
+//   fp32 VALU kernels          rnn_seq_{fwd,bwd}_f32_kernel: any H, thread = hidden unit, 8 batch rows per workgroup, W_hh streamed
+//                              from L2.  SWEEP_VALU: the parity mode outside H in {64, 128, 256, 512}, or LAS_SEQ_F32_VALU.  (The other
+//                              parity-mode sweeps are the exact-fp32 clusters of rnn_seq_f32.hip: SWEEP_MF32.)
+//   plain bf16 MFMA kernels    rnn_seq_{fwd,bwd}_bf16_kernel: v_mfma_f32_16x16x32_bf16, 16 batch rows per workgroup, 4 waves x 64
+//                              hidden units, every wave owns all G gates of its units (the gate math is lane-local on the accumulator
+//                              layout), W_hh pre-packed into B-fragment order and resident in registers / LDS.  FWD_PLAIN / BWD_PLAIN:
+//                              what is left when the two families below do not serve (LAS_SEQ_NO_HELPER_WAVES, LAS_SEQ_NO_KSPLIT, P = 1).
+//   helper-wave forward        rnn_seq_fwd_hw_kernel: 16- or 8-row tiles, ragged rows, chunked x-projection, L2 warmers.
+//                              FWD_HW16, FWD_HW8, FWD_HW8_RAGGED: the speed mode's forward sweep.
+//   K-split BPTT               rnn_seq_bwd_ks_kernel: 16- or 8-row tiles, chunked dout, progress publishing.
+//                              BWD_KS16, BWD_KS8, BWD_KS8_CH, BWD_KS8_CH_PG: the speed mode's BPTT with P > 1.
+//   then the pack / prepare kernels, bias_finish_kernel, and the host side: plan_sweep and the C entry points.
+// With P > 1 the hidden units of one (direction, batch tile) are split over a CLUSTER of P workgroups that exchange h (forward) or
+// d(pre-activation) / partial dh (BPTT) every step through tagged granules ("cluster exchange" below; gather_tagged in
+// rnn_seq_args.h is the one poll loop).  There is no grid barrier: clusters are independent of each other.
 #include "las_common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 #ifndef LAS_ABL
 #define LAS_ABL 0      // development: bit mask of parts of the forward sweep to leave out (timing experiments, tools/abl_rnn.py)
@@ -240,7 +248,6 @@ struct BfPtr {
     __device__ __forceinline__ BfPtr& operator+=(long long o) { p += o; return *this; }
 };
 #define GF(p) (BfPtr{(gio*)(p)})
-#define GCF(p) (BfPtr{(gio*)(p)})
 typedef __attribute__((address_space(1))) float gfloat;          // fp32 globals (helper waves' LDS rings stay fp32)
 
 // `local` = every member of this cluster runs on the same XCD (verified at kernel start, cluster_same_xcd): the
@@ -252,34 +259,6 @@ __device__ __forceinline__ void granule_store(unsigned long long* p, unsigned ta
     if (local) asm volatile("global_store_dwordx2 %0, %1, off sc0" :: "v"(p), "v"(v) : "memory");
     else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// Fetch this thread's N granules (all loads in flight at once), then re-poll only the stale ones.
-template <int N, int P, int GPM>
-__device__ __forceinline__ void gather_granules(unsigned long long (&xv)[N], const unsigned long long* xslot, int pm, int tid,
-                                                unsigned tag, int& errflag, int spin) {
-    constexpr int PER = GPM / 256;
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        const int m = (pm + 1 + n / PER) % P;
-        xv[n] = __hip_atomic_load(xslot + (size_t)m * GPM + tid + (n % PER) * 256, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    int budget = errflag ? 1 : spin;
-    for (;;) {
-        bool ok = true;
-#pragma unroll
-        for (int n = 0; n < N; ++n) ok &= (unsigned)(xv[n] >> 32) == tag;
-        if (ok) break;
-        if (--budget <= 0) { errflag = 1; break; }
-        __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-        for (int n = 0; n < N; ++n) {
-            if ((unsigned)(xv[n] >> 32) != tag) {
-                const int m = (pm + 1 + n / PER) % P;
-                xv[n] = __hip_atomic_load(xslot + (size_t)m * GPM + tid + (n % PER) * 256, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
-}
-
 template <int CELL, int UT, int P>
 struct RnnCfg {
     static constexpr int G = CELL == LAS_CELL_LSTM ? 4 : 1;
@@ -307,6 +286,33 @@ struct RnnCfg {
     static constexpr int GPM_B = 16 * G * UPM / 2;    // ... backward
     static constexpr bool OK = (UT % P == 0) && (RF + LF == NFW) && (RFB + LFB == NFB);
 };
+
+// LDS position of batch row r in the h tile.  RB = 8: rows r and r + 4 are written by the same 32-lane group (ds_write_b16),
+// and with the pitch the A-fragment reads want (8 dwords mod 16) four positions apart is the same bank -> interleave them
+template <int RB>
+__device__ __forceinline__ int h_tile_pos(int r) { return RB == 16 ? r : (((r & 3) << 1) | (r >> 2)); }
+
+// The gathered h granules of the partners -> the LDS tile of h_t.  Granule n of thread tid is the double-granule index
+// di = (w' * UTP + j') * 64 + lane' of member (pm + 1 + n / UTP) % P: what lane' of that member's wave w' published for its tile j',
+// i.e. unit m UPM + (w' UTP + j') 16 + (lane' & 15) of the rows that lane owns -- RB = 16: the four rows (lane' >> 4) * 4 + k as two
+// bf16 pairs {tag, r0 | r1, r2 | r3, tag}; RB = 8: the two rows gl * 4 + hsel * 2 + k as one pair {tag, r0 | r1}.
+template <int RB, int UTP, int UPM, int LDH, int P, int N, typename V>
+__device__ __forceinline__ void scatter_h_granules(unsigned short* hnext, const V (&xv)[N], const int pm, const int tid) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        const int m = (pm + 1 + n / UTP) % P;
+        const int di = (n % UTP) * 256 + tid;
+        const int l2 = di & 63, wj = di >> 6, g2 = l2 >> 4;
+        const int unit = m * UPM + wj * 16 + (l2 & 15);
+        const int row = RB == 16 ? g2 * 4 : (g2 & 1) * 4 + (g2 >> 1) * 2;
+        hnext[h_tile_pos<RB>(row) * LDH + unit] = (unsigned short)(xv[n].y & 0xffffu);
+        hnext[h_tile_pos<RB>(row + 1) * LDH + unit] = (unsigned short)(xv[n].y >> 16);
+        if constexpr (RB == 16) {
+            hnext[h_tile_pos<RB>(row + 2) * LDH + unit] = (unsigned short)(xv[n].z & 0xffffu);
+            hnext[h_tile_pos<RB>(row + 3) * LDH + unit] = (unsigned short)(xv[n].z >> 16);
+        }
+    }
+}
 
 template <int CELL, int UT, int P>
 __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_bf16_kernel(RnnArgs a) {
@@ -377,15 +383,9 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_bf16_kernel(RnnArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) xn[q][j][r] = gptr[r][q * H + j * 16];
     int cur = 0;
-#ifdef LAS_PROF
-    const bool prof = a.dbg && blockIdx.x == 0 && threadIdx.x == 0;
-    if (prof) { a.dbg[0] = clock64(); a.dbg[1] = wall_clock64(); }
-#define STAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (prof && s >= 200 && s < 208) a.dbg[8 + (s - 200) * 8 + (k)] = clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define STAMP(k)
-#endif
+    const bool prof = sweep_prof_begin(a.dbg);
     for (int s = 0; s < T; ++s) {
-        STAMP(0);
+        SWEEP_STAMP(0);
         f32x4_t acc[G][UTP];
 #pragma unroll
         for (int q = 0; q < G; ++q)
@@ -414,11 +414,11 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_bf16_kernel(RnnArgs a) {
                     acc[q][j] = mfma_bf16_16x16x32(av[ks], bv, acc[q][j]);
                 }
         }
-        STAMP(1);
+        SWEEP_STAMP(1);
 #ifdef LAS_PROF
         asm volatile("s_nop 0" :: "v"(acc[0][0][0]), "v"(acc[G - 1][UTP - 1][3]));
 #endif
-        STAMP(2);
+        SWEEP_STAMP(2);
         unsigned short* hnext = hs + (cur ^ 1) * 16 * LDH;
         const unsigned slot_off = (unsigned)((s & 1) * P) * GPM * 8u;
         float sv_h[UTP][4], sv_g[G][UTP][4];     // results kept in registers; written to HBM after the exchange
@@ -449,31 +449,16 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_bf16_kernel(RnnArgs a) {
                 granule16_store(xrs, slot_off + (unsigned)pm * GPM * 8u + ((unsigned)(w * UTP + j) * 64u + lane) * 16u, (unsigned)(s + 1),
                                 (unsigned)hb[0] | ((unsigned)hb[1] << 16), (unsigned)hb[2] | ((unsigned)hb[3] << 16), local);
         }
-        STAMP(3);
+        SWEEP_STAMP(3);
         if (P > 1 && s + 1 < T) {       // gather the other members' slices of h_t into the LDS tile
             constexpr int NGT = (P > 1 ? (P - 1) * UTP : 1);              // double granules per thread: UTP per partner
             u32x4_t xv[NGT];
-#pragma unroll
-            for (int n = 0; n < NGT; ++n) {
+            gather_tagged(xv, [=](int n) {
                 const int m = (pm + 1 + n / UTP) % P;
-                xv[n] = granule16_load(xrs, slot_off + (unsigned)m * GPM * 8u + ((unsigned)(n % UTP) * 256u + tid) * 16u);
-            }
-            int budget = errflag ? 1 : a.spin;
-            for (;;) {
-                bool ok = true;
-#pragma unroll
-                for (int n = 0; n < NGT; ++n) ok &= xv[n].x == (unsigned)(s + 1) && xv[n].w == (unsigned)(s + 1);
-                if (ok) break;
-                if (--budget <= 0) { errflag = 1; break; }
-                __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-                for (int n = 0; n < NGT; ++n) {
-                    if (xv[n].x != (unsigned)(s + 1) || xv[n].w != (unsigned)(s + 1)) {
-                        const int m = (pm + 1 + n / UTP) % P;
-                        xv[n] = granule16_load(xrs, slot_off + (unsigned)m * GPM * 8u + ((unsigned)(n % UTP) * 256u + tid) * 16u);
-                    }
-                }
-            }
+                return granule16_load(xrs, slot_off + (unsigned)m * GPM * 8u + ((unsigned)(n % UTP) * 256u + tid) * 16u);
+            }, (unsigned)(s + 1), errflag, a.spin);
+            // (scatter_h_granules<16>, on its own text: through the shared function the tanh cell's H = 512 / P = 4 instance goes from
+            //  243 to 253 VGPRs and loses a wave of occupancy)
 #pragma unroll
             for (int n = 0; n < NGT; ++n) {
                 const int m = (pm + 1 + n / UTP) % P;
@@ -488,7 +473,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_bf16_kernel(RnnArgs a) {
             }
         }
         lds_barrier();
-        STAMP(4);
+        SWEEP_STAMP(4);
         // bulk results of this step: nobody waits on these stores (the next vmcnt wait is a whole step away)
 #pragma unroll
         for (int j = 0; j < UTP; ++j)
@@ -507,22 +492,9 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_bf16_kernel(RnnArgs a) {
         cur ^= 1;
     }
     if (errflag) { if (a.err) a.err[0] = 1; if (a.status) a.status[0] = a.status_code; }
-#ifdef LAS_PROF
-    if (prof) { a.dbg[2] = clock64(); a.dbg[3] = wall_clock64(); }
-#endif
+    sweep_prof_end(a.dbg, prof);
 }
 
-// ------------------------------------------------------------------------------------------------
-// forward sweep with helper waves.  In the kernel above the four compute waves also issue the step's HBM traffic
-// (16 x-projection loads and 24 result stores per lane and step); removing those from the dependent chain is worth
-// 0.4 us per step (measured by ablation: 1.77 -> 1.35 us).  Here waves 4-7 own ALL bulk HBM traffic of the workgroup, a
-// quarter of the rows each: they keep the x-projections of the next steps in flight and hand them over through a
-// 3-slot LDS ring in accumulator order, and they write the previous step's results (activated gates, c, h) from a second
-// LDS ring with coalesced 16-byte stores.  The compute waves touch global memory only for the exchange granules.  One
-// LDS barrier per step still orders everything.  (A single helper wave does not work: its ~80 memory instructions per
-// step take longer than the compute chain, and the barrier then waits for it.)
-// Rows past the end of a ragged batch tile alias the last valid row for their LOADS; they store nothing (round 6).
-// ------------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------------
 // L2 warmers.  Ablations (make abl ABL=32|64|128) showed that the bulk HBM traffic of a sweep costs the dependent chain
 // 0.15 us per step NOT by its instruction count but by its MISSES: a load that goes to HBM (or walks the page table) sits in
@@ -576,11 +548,19 @@ __device__ __forceinline__ void l2_warmer(const WarmSeg (&seg)[NSEG], int rows, 
     if (acc == 0x9e3779b9u && sink) sink[threadIdx.x] = (unsigned short)acc;   // keeps the loads alive
 }
 
-#ifndef LAS_KS_SHARE_CU
-#define LAS_KS_SHARE_CU 0        // 1: request only the LDS the kernel uses (timing experiments: lets other kernels share the sweep's CUs)
-#endif
 constexpr int ks_lds(int used) { return LAS_KS_SHARE_CU ? used : 159 * 1024; }   // all but 1 KB (the kernels have 256 B of static LDS): nothing that uses LDS fits next to the sweep
 
+// ------------------------------------------------------------------------------------------------
+// forward sweep with helper waves.  In the kernel above the four compute waves also issue the step's HBM traffic
+// (16 x-projection loads and 24 result stores per lane and step); removing those from the dependent chain is worth
+// 0.4 us per step (measured by ablation: 1.77 -> 1.35 us).  Here waves 4-7 own ALL bulk HBM traffic of the workgroup, a
+// quarter of the rows each: they keep the x-projections of the next steps in flight and hand them over through a
+// 3-slot LDS ring in accumulator order, and they write the previous step's results (activated gates, c, h) from a second
+// LDS ring with coalesced 16-byte stores.  The compute waves touch global memory only for the exchange granules.  One
+// LDS barrier per step still orders everything.  (A single helper wave does not work: its ~80 memory instructions per
+// step take longer than the compute chain, and the barrier then waits for it.)
+// Rows past the end of a ragged batch tile alias the last valid row for their LOADS; they store nothing (round 6).
+// ------------------------------------------------------------------------------------------------
 template <int CELL, int UT, int P, int RB = 16>
 struct HwCfg {
     using C = RnnCfg<CELL, UT, P>;
@@ -676,9 +656,11 @@ __global__ __launch_bounds__(512, 1) void rnn_seq_fwd_hw_kernel(RnnArgs a) {
             co[ii] = row * OP + u;
             cst_ |= (b0 + row < B ? 1u : 0u) << ii;
         }
-        auto gframe = [&](int s) { if (LAS_ABL & 128) s &= 1; if (LAS_ABL & 256) s &= 15; if (LAS_ABL & 1024) s = (s & 15) * 64; return a.gates16 + (long long)(t0 + s * tstep) * 2 * GH; };     // uniform frame bases
-        auto cframe = [&](int s) { if (LAS_ABL & 128) s &= 1; if (LAS_ABL & 256) s &= 15; if (LAS_ABL & 1024) s = (s & 15) * 64; return a.cstate16 + (long long)(t0 + s * tstep) * 2 * H; };
-        auto oframe = [&](int s) { if (LAS_ABL & 128) s &= 1; if (LAS_ABL & 256) s &= 15; if (LAS_ABL & 1024) s = (s & 15) * 64; return a.out16 + (long long)(t0 + s * tstep) * a.ld_out; };
+        // step index of a frame base; the LAS_ABL timing experiments revisit a few frames instead (L2- / TLB-resident operands)
+        auto fstep = [](int s) { if (LAS_ABL & 128) s &= 1; if (LAS_ABL & 256) s &= 15; if (LAS_ABL & 1024) s = (s & 15) * 64; return s; };
+        auto gframe = [&](int s) { return a.gates16 + (long long)(t0 + fstep(s) * tstep) * 2 * GH; };     // uniform frame bases
+        auto cframe = [&](int s) { return a.cstate16 + (long long)(t0 + fstep(s) * tstep) * 2 * H; };
+        auto oframe = [&](int s) { return a.out16 + (long long)(t0 + fstep(s) * tstep) * a.ld_out; };
         auto to_ring = [&](float* xr, const u32x4_t& v, int off) __attribute__((always_inline)) {   // 8 bf16 -> 2 x float4 in LDS
             f4v lo = {__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u)};
             f4v hi = {__uint_as_float(v.z << 16), __uint_as_float(v.z & 0xffff0000u), __uint_as_float(v.w << 16), __uint_as_float(v.w & 0xffff0000u)};
@@ -808,9 +790,6 @@ __global__ __launch_bounds__(512, 1) void rnn_seq_fwd_hw_kernel(RnnArgs a) {
 
     const int gl = RB == 16 ? g : (g & 1), hsel = RB == 16 ? 0 : (g >> 1);
     const int row0 = RB == 16 ? g * 4 : gl * 4 + hsel * 2;     // the lane's rows are row0 + k, k < NV
-    // LDS position of batch row r in the h tile.  RB = 8: rows r and r + 4 are written by the same 32-lane group (ds_write_b16),
-    // and with the pitch the A-fragment reads want (8 dwords mod 16) four positions apart is the same bank -> interleave them
-    auto hpos = [](int r) { return RB == 16 ? r : (((r & 3) << 1) | (r >> 2)); };
     float cst[UTP][NV];
 #pragma unroll
     for (int j = 0; j < UTP; ++j)
@@ -820,21 +799,15 @@ __global__ __launch_bounds__(512, 1) void rnn_seq_fwd_hw_kernel(RnnArgs a) {
 #pragma unroll
     for (int r = 0; r < NV; ++r) rowT[r] = RAGGED ? a.row_T[(b0 + row0 + r) < B ? (b0 + row0 + r) : B - 1] : 0x7fffffff;
     int cur = 0;
-#ifdef LAS_PROF
-    const bool hprof = a.dbg && blockIdx.x == 0 && threadIdx.x == 0;
-    if (hprof) { a.dbg[0] = clock64(); a.dbg[1] = wall_clock64(); }
-#define HSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (hprof && s >= 200 && s < 208) a.dbg[8 + (s - 200) * 8 + (k)] = clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define HSTAMP(k)
-#endif
+    const bool prof = sweep_prof_begin(a.dbg);
     for (int s = 0; s < T; ++s) {
-        HSTAMP(0);
+        SWEEP_STAMP(0);
         const float* xr = xring + (s % 3) * RB * XP;
         float* orr = oring + (s & 1) * RB * OP;
         const unsigned short* hcur = hs + cur * 16 * LDH;
         u16x8_t av[KS];                          // A fragments of h_{t-1} first: the MFMAs wait on nothing else
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) av[ks] = *reinterpret_cast<const u16x8_t*>(&hcur[hpos(c & (RB - 1)) * LDH + ((LAS_ABL & 2) ? 0 : ks) * 32 + g * 8]);
+        for (int ks = 0; ks < KS; ++ks) av[ks] = *reinterpret_cast<const u16x8_t*>(&hcur[h_tile_pos<RB>(c & (RB - 1)) * LDH + ((LAS_ABL & 2) ? 0 : ks) * 32 + g * 8]);
         __builtin_amdgcn_sched_barrier(0);       // all of them in flight before anything else (the compiler otherwise fetches them in pairs)
         float xv[G][UTP][NV];                    // x.W_ih + b from the ring: read under the MFMAs, added after them
 #pragma unroll
@@ -876,7 +849,7 @@ __global__ __launch_bounds__(512, 1) void rnn_seq_fwd_hw_kernel(RnnArgs a) {
 #ifdef LAS_PROF
         asm volatile("s_nop 0" :: "v"(pre[0][0][0]), "v"(pre[G - 1][UTP - 1][NV - 1]));     // MFMA results landed
 #endif
-        HSTAMP(1);
+        SWEEP_STAMP(1);
         unsigned short* hnext = hs + (cur ^ 1) * 16 * LDH;
         const unsigned slot_off = (unsigned)((s & 1) * P) * GPM * 8u;
 #pragma unroll
@@ -918,7 +891,7 @@ __global__ __launch_bounds__(512, 1) void rnn_seq_fwd_hw_kernel(RnnArgs a) {
 #pragma unroll
             for (int r = 0; r < NV; ++r) {
                 float* orow = orr + (row0 + r) * OP;
-                hnext[hpos(row0 + r) * LDH + unit] = hb[r];
+                hnext[h_tile_pos<RB>(row0 + r) * LDH + unit] = hb[r];
                 if (CELL == LAS_CELL_LSTM) {
                     if (LAS_ABL & 8) { orow[ul] = res[r][5]; continue; }
                     orow[ul] = res[r][0]; orow[(G > 1 ? 1 : 0) * UPM + ul] = res[r][1]; orow[(G > 2 ? 2 : 0) * UPM + ul] = res[r][2];
@@ -930,87 +903,23 @@ __global__ __launch_bounds__(512, 1) void rnn_seq_fwd_hw_kernel(RnnArgs a) {
                 }
             }
         }
-        HSTAMP(2);
+        SWEEP_STAMP(2);
         if (P > 1 && s + 1 < T) {       // gather the other members' slices of h_t into the LDS tile
             constexpr int NGT = (P > 1 ? (P - 1) * UTP : 1);
-            if constexpr (RB == 16) {
-            u32x4_t xv[NGT];
-#pragma unroll
-            for (int n = 0; n < NGT; ++n) {
+            std::conditional_t<RB == 16, u32x4_t, u32x2_t> xv[NGT];      // the lane's rows of a partner's unit: one 16-byte (4 rows) or 8-byte (2 rows) granule
+            gather_tagged(xv, [=](int n) {
                 const int m = (pm + 1 + n / UTP) % P;
-                xv[n] = granule16_load(xrs, slot_off + (unsigned)m * GPM * 8u + ((unsigned)(n % UTP) * 256u + tid) * 16u);
-            }
-            int budget = errflag ? 1 : a.spin;
-            for (;;) {
-                bool ok = true;
-#pragma unroll
-                for (int n = 0; n < NGT; ++n) ok &= xv[n].x == (unsigned)(s + 1) && xv[n].w == (unsigned)(s + 1);
-                if (ok) break;
-                if (--budget <= 0) { errflag = 1; break; }
-                __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-                for (int n = 0; n < NGT; ++n) {
-                    if (xv[n].x != (unsigned)(s + 1) || xv[n].w != (unsigned)(s + 1)) {
-                        const int m = (pm + 1 + n / UTP) % P;
-                        xv[n] = granule16_load(xrs, slot_off + (unsigned)m * GPM * 8u + ((unsigned)(n % UTP) * 256u + tid) * 16u);
-                    }
-                }
-            }
-#pragma unroll
-            for (int n = 0; n < NGT; ++n) {
-                const int m = (pm + 1 + n / UTP) % P;
-                const int di = (n % UTP) * 256 + tid;
-                const int l2 = di & 63, wj = di >> 6;
-                const int unit = m * UPM + wj * 16 + (l2 & 15);
-                const int row = (l2 >> 4) * 4;
-                hnext[row * LDH + unit] = (unsigned short)(xv[n].y & 0xffffu);
-                hnext[(row + 1) * LDH + unit] = (unsigned short)(xv[n].y >> 16);
-                hnext[(row + 2) * LDH + unit] = (unsigned short)(xv[n].z & 0xffffu);
-                hnext[(row + 3) * LDH + unit] = (unsigned short)(xv[n].z >> 16);
-            }
-            } else {
-            u32x2_t xv[NGT];
-#pragma unroll
-            for (int n = 0; n < NGT; ++n) {
-                const int m = (pm + 1 + n / UTP) % P;
-                xv[n] = granule8_load(xrs, slot_off + (unsigned)m * GPM * 8u + ((unsigned)(n % UTP) * 256u + tid) * 8u);
-            }
-            int budget = errflag ? 1 : a.spin;
-            for (;;) {
-                bool ok = true;
-#pragma unroll
-                for (int n = 0; n < NGT; ++n) ok &= xv[n].x == (unsigned)(s + 1);
-                if (ok) break;
-                if (--budget <= 0) { errflag = 1; break; }
-                __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-                for (int n = 0; n < NGT; ++n) {
-                    if (xv[n].x != (unsigned)(s + 1)) {
-                        const int m = (pm + 1 + n / UTP) % P;
-                        xv[n] = granule8_load(xrs, slot_off + (unsigned)m * GPM * 8u + ((unsigned)(n % UTP) * 256u + tid) * 8u);
-                    }
-                }
-            }
-#pragma unroll
-            for (int n = 0; n < NGT; ++n) {
-                const int m = (pm + 1 + n / UTP) % P;
-                const int di = (n % UTP) * 256 + tid;
-                const int l2 = di & 63, wj = di >> 6, g2 = l2 >> 4;
-                const int unit = m * UPM + wj * 16 + (l2 & 15);
-                const int row = (g2 & 1) * 4 + (g2 >> 1) * 2;
-                hnext[hpos(row) * LDH + unit] = (unsigned short)(xv[n].y & 0xffffu);
-                hnext[hpos(row + 1) * LDH + unit] = (unsigned short)(xv[n].y >> 16);
-            }
-            }
+                if constexpr (RB == 16) return granule16_load(xrs, slot_off + (unsigned)m * GPM * 8u + ((unsigned)(n % UTP) * 256u + tid) * 16u);
+                else                    return granule8_load(xrs, slot_off + (unsigned)m * GPM * 8u + ((unsigned)(n % UTP) * 256u + tid) * 8u);
+            }, (unsigned)(s + 1), errflag, a.spin);
+            scatter_h_granules<RB, UTP, UPM, LDH, P>(hnext, xv, pm, tid);
         }
-        HSTAMP(3);
+        SWEEP_STAMP(3);
         lds_barrier();
-        HSTAMP(4);
+        SWEEP_STAMP(4);
         cur ^= 1;
     }
-#ifdef LAS_PROF
-    if (hprof) { a.dbg[2] = clock64(); a.dbg[3] = wall_clock64(); }
-#endif
+    sweep_prof_end(a.dbg, prof);
     if (errflag) { if (a.err) a.err[0] = 1; if (a.status) a.status[0] = a.status_code; }
 }
 
@@ -1061,7 +970,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_bf16_kernel(RnnArgs a) {
         gptr[r] = GF(valid ? a.gates16 + ((row * T + t0) * 2 + dir) * GH + u0 : a.sink16 + u0);
         cptr[r] = GF((valid && a.cstate16) ? a.cstate16 + ((row * T + t0) * 2 + dir) * H + u0 : a.sink16 + u0);
         optr[r] = GF(valid ? a.out16 + row * a.obs + (long long)t0 * a.ld_out + dir * H + u0 : a.sink16 + u0);
-        dptr[r] = GCF(valid ? a.dout16 + row * a.dobs + (long long)t0 * a.ld_dout + dir * H + u0 : a.sink16 + u0);
+        dptr[r] = GF(valid ? a.dout16 + row * a.dobs + (long long)t0 * a.ld_dout + dir * H + u0 : a.sink16 + u0);
         gst[r] = valid ? gstep : 0; cst_[r] = valid ? cstep : 0; ost[r] = valid ? ostep : 0; dst[r] = valid ? dstep : 0;
     }
     f32x4_t dhr[UTP];
@@ -1162,7 +1071,10 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_bf16_kernel(RnnArgs a) {
         if (P > 1) {
             constexpr int PER = GPM / 256, NGT = (P > 1 ? (P - 1) * PER : 1);
             unsigned long long xv[NGT];
-            gather_granules<NGT, P, GPM>(xv, xslot, pm, tid, (unsigned)(s + 1), errflag, a.spin);
+            gather_tagged(xv, [=](int n) {
+                const int m = (pm + 1 + n / PER) % P;
+                return __hip_atomic_load(xslot + (size_t)m * GPM + tid + (n % PER) * 256, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }, (unsigned)(s + 1), errflag, a.spin);
 #pragma unroll
             for (int n = 0; n < NGT; ++n) {
                 const int m = (pm + 1 + n / PER) % P;
@@ -1237,12 +1149,9 @@ struct KsCfg {
 // by hsel = lane >> 5): one row x one unit pair per lane instead of two rows, half the loads / stores / transcendentals /
 // granule bytes per step, twice as many CUs per batch.
 // CH: dout arrives in chunks (a.dflag): a separate instantiation -- the kernel sits at the register limit and the plain one must not change
-// PG (round 5, with CH): the sweep PUBLISHES its progress -- dZ leaves with agent-scope (write-through) stores, and every a.pstep steps each
-// member waits for its own stores and writes the step count into a.prog -- so that the layer's weight gradients can follow the sweep window
+// PG (round 5, with CH): the sweep PUBLISHES its progress -- every a.pstep steps each member waits for its own dZ stores, writes the XCD's
+// dirty L2 lines back (one agent-scope release) and stores the step count into a.prog -- so that the layer's weight gradients can follow the sweep window
 // by window on another stream (las_rnn_seq_bwd_db_progress) instead of starting when it ends.  A separate instantiation, like CH.
-#ifndef LAS_PG_SC1_STORES
-#define LAS_PG_SC1_STORES 0
-#endif
 template <int CELL, int UT, int P, int RB, bool CH = false, bool PG = false>
 __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
     static_assert(RB == 16 || RB == 8, "row tile");
@@ -1359,15 +1268,9 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
         }
     int cur = 0;
     int pleft = PG ? a.pstep : 0;                   // steps until the next publication of dZ progress (PG)
-#ifdef LAS_PROF
-    const bool kprof = a.dbg && blockIdx.x == 0 && threadIdx.x == 0;
-    if (kprof) { a.dbg[0] = clock64(); a.dbg[1] = wall_clock64(); }
-#define KSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (kprof && s >= 200 && s < 208) a.dbg[8 + (s - 200) * 8 + (k)] = clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define KSTAMP(k)
-#endif
+    const bool prof = sweep_prof_begin(a.dbg);
     for (int s = 0; s < T; ++s) {
-        KSTAMP(0);
+        SWEEP_STAMP(0);
         unsigned short* dzc = dzs + cur * RB * LDZ;
         unsigned sv_z[G][UTP][2];            // d(pre-activation) of this step as packed pairs (written to HBM after the exchange)
         // ---- gate backward for the own units -> own dG slice in LDS (bf16 pairs) and in registers
@@ -1420,7 +1323,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
                 }
             }
         }
-        KSTAMP(1);
+        SWEEP_STAMP(1);
         gu32* gprev[2];
 #pragma unroll
         for (int rr = 0; rr < NR; ++rr) { gprev[rr] = gptr[rr]; gptr[rr] += gst[rr]; optr[rr] += ost[rr]; dptr[rr] += dst[rr]; if (CELL == LAS_CELL_LSTM) cptr[rr] += cst_[rr]; }
@@ -1448,9 +1351,9 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
                     }
                 }
         }
-        KSTAMP(2);
+        SWEEP_STAMP(2);
         lds_barrier();
-        KSTAMP(3);
+        SWEEP_STAMP(3);
         // ---- partial dh tiles (m, w, j) for every member m:  own dG slice [16 x KP] . W_hh^T rows of those units
         f32x4_t acc[P][UTP];                     // acc[mo]: partial tile of member (pm + mo) % P; acc[0] = own
 #pragma unroll
@@ -1473,7 +1376,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
 #ifdef LAS_PROF
         asm volatile("s_nop 0" :: "v"(acc[0][0][0]), "v"(acc[P - 1][UTP - 1][3]));
 #endif
-        KSTAMP(4);
+        SWEEP_STAMP(4);
         if (s + 1 < T) {
             // ---- reduce-scatter: send the tiles other members own, add the ones they computed for this wave
             // byte offsets into this cluster's exchange buffer (< 2 GB): slot, [dst][src] region, (wave tile, lane) x 16 B
@@ -1490,31 +1393,14 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
                                     f2bf2(acc[mo][j][2], acc[mo][j][3]), local);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            KSTAMP(5);
+            SWEEP_STAMP(5);
             constexpr int NGT = (P - 1) * UTP;
             u32x4_t xv[NGT];
             const unsigned in_off = slot_off + (unsigned)(pm * P) * GPD * 8u + lane_off;
-#pragma unroll
-            for (int n = 0; n < NGT; ++n) {
+            gather_tagged(xv, [=](int n) {
                 const int src = (pm + 1 + n / UTP) % P;
-                xv[n] = granule16_load(xrs, in_off + (unsigned)src * GPD * 8u + (unsigned)(n % UTP) * 1024u);
-            }
-            int budget = errflag ? 1 : a.spin;
-            for (;;) {
-                bool ok = true;
-#pragma unroll
-                for (int n = 0; n < NGT; ++n) ok &= xv[n].x == (unsigned)(s + 1) && xv[n].w == (unsigned)(s + 1);
-                if (ok) break;
-                if (--budget <= 0) { errflag = 1; break; }
-                __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-                for (int n = 0; n < NGT; ++n) {
-                    if (xv[n].x != (unsigned)(s + 1) || xv[n].w != (unsigned)(s + 1)) {
-                        const int src = (pm + 1 + n / UTP) % P;
-                        xv[n] = granule16_load(xrs, in_off + (unsigned)src * GPD * 8u + (unsigned)(n % UTP) * 1024u);
-                    }
-                }
-            }
+                return granule16_load(xrs, in_off + (unsigned)src * GPD * 8u + (unsigned)(n % UTP) * 1024u);
+            }, (unsigned)(s + 1), errflag, a.spin);
 #pragma unroll
             for (int j = 0; j < UTP; ++j)
 #pragma unroll
@@ -1541,10 +1427,12 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
                                    f2bf2(hsel ? acc[mo][j][1] : acc[mo][j][0], hsel ? acc[mo][j][3] : acc[mo][j][2]), local);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            KSTAMP(5);
+            SWEEP_STAMP(5);
             constexpr int NGT = (P - 1) * UTP;
             u32x2_t xv[NGT];
             const unsigned in_off = slot_off + (unsigned)(pm * P) * GPD * 8u + lane_off;
+            // (gather_tagged, on its own text: through the shared function the H = 512 LSTM instances <1, 8, 8, 8, *> grow by about 30
+            //  instructions and one vmcnt(0) wait per step, and that sweep ran 3.15 -> 3.18 ms; profiles/listener_refactor_device_code.txt)
 #pragma unroll
             for (int n = 0; n < NGT; ++n) {
                 const int src = (pm + 1 + n / UTP) % P;
@@ -1579,7 +1467,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
             }
             }
         }
-        KSTAMP(6);
+        SWEEP_STAMP(6);
         // ---- d(pre-activation) of this step to HBM as packed bf16 pairs (never waited on)
 #pragma unroll
         for (int j = 0; j < UTP; ++j)
@@ -1587,13 +1475,9 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
             for (int rr = 0; rr < NR; ++rr)
 #pragma unroll
                 for (int q = 0; q < G; ++q) {
-#if LAS_PG_SC1_STORES
-                    if constexpr (PG) __hip_atomic_store((unsigned*)(gprev[rr] + (q * H + j * 16) / 2), sv_z[q][j][rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else
-#endif
                     gprev[rr][(q * H + j * 16) / 2] = sv_z[q][j][rr];
                 }
-        KSTAMP(7);
+        SWEEP_STAMP(7);
         cur ^= 1;
         if constexpr (PG) {
             if (--pleft == 0 || s + 1 == T) {                        // every a.pstep steps (a countdown: `(s + 1) % a.pstep` was an integer division
@@ -1601,19 +1485,16 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's dZ stores of the steps so far have reached the XCD's L2 ...
                 __builtin_amdgcn_s_barrier();                          // ... and every other wave's of this member
                 if (tid == 0) {
-#if !LAS_PG_SC1_STORES
-                    // plain stores + ONE write-back of the XCD's dirty L2 lines per publication (4-byte agent-scope stores are a fabric write
-                    // each: the sweep ran 1.77 -> 2.09 ms with them)
+                    // plain dZ stores + ONE write-back of the XCD's dirty L2 lines per publication.  Tried: every dZ store agent-scope
+                    // (write-through) instead, no fence here.  Result: a 4-byte agent-scope store is a fabric write each, the sweep ran
+                    // 1.77 -> 2.09 ms
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#endif
                     __hip_atomic_store(a.prog + (size_t)cl * P + pm, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
         }
     }
-#ifdef LAS_PROF
-    if (kprof) { a.dbg[2] = clock64(); a.dbg[3] = wall_clock64(); }
-#endif
+    sweep_prof_end(a.dbg, prof);
     // bias gradient partials of this (tile, direction): sum the rows held by the lane pair and by the four row groups
 #pragma unroll
     for (int q = 0; q < G; ++q)

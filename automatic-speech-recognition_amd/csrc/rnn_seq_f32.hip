@@ -23,9 +23,6 @@
 // Exchange transport, placement handshake, bounded polls and the status word are the speed mode's (rnn_seq_args.h).
 // No atomics; every sum has a fixed order: bit-reproducible.
 #include "rnn_seq_args.h"
-#ifndef LAS_KS_SHARE_CU
-#define LAS_KS_SHARE_CU 0        // 1: timing experiments -- other kernels may share the sweep's CUs (see las_rnn_seq_mf32_run)
-#endif
 
 namespace {
 
@@ -109,16 +106,10 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_mf32_kernel(RnnArgs a) {
     float zl[4], hl[4], cl_ = 0.f;                                              // last step's results, stored one step late
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) zl[nt] = hl[nt] = 0.f;
-#ifdef LAS_PROF
-    const bool fprof = a.dbg && blockIdx.x == 0 && threadIdx.x == 0;
-    if (fprof) { a.dbg[0] = clock64(); a.dbg[1] = wall_clock64(); }
-#define FSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (fprof && s >= 200 && s < 208) a.dbg[8 + (s - 200) * 8 + (k)] = clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define FSTAMP(k)
-#endif
+    const bool prof = sweep_prof_begin(a.dbg);
 
     for (int s = 0; s < T; ++s) {
-        FSTAMP(0);
+        SWEEP_STAMP(0);
         // ---- h_{s-1}: this wave's K quarter of all 16 rows, as published at the end of step s - 1 (slot (s - 1) & 1, tag s)
         float av[KS];
         if (s == 0) {
@@ -127,6 +118,8 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_mf32_kernel(RnnArgs a) {
         } else {
             const unsigned slot_off = (unsigned)(((s - 1) & 1) * P) * GPM * 16u, tag = (unsigned)s;
             u32x4_t xv[KS / 2];
+            // (gather_tagged, on its own text: through the shared function the H = 512 instances park 40 to 50 more values in AGPRs and
+            //  the LSTM sweep at B = 48 ran 4.09 -> 4.34 us per step; profiles/listener_refactor_device_code.txt)
 #pragma unroll
             for (int q = 0; q < KS / 2; ++q) xv[q] = granule16_load(xrs, slot_off + goff[q]);
             int budget = errflag ? 1 : a.spin;
@@ -144,7 +137,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_mf32_kernel(RnnArgs a) {
 #pragma unroll
             for (int q = 0; q < KS / 2; ++q) { av[2 * q] = __uint_as_float(xv[q].y); av[2 * q + 1] = __uint_as_float(xv[q].z); }
         }
-        FSTAMP(1);
+        SWEEP_STAMP(1);
         f32x4_t acc[4];
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) acc[nt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
@@ -182,9 +175,9 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_mf32_kernel(RnnArgs a) {
         for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
             for (int i = 0; i < 4; ++i) part[((w * 4 + nt) * 4 + i) * PT + lk * 16 + li] = acc[nt][i];
-        FSTAMP(2);
+        SWEEP_STAMP(2);
         lds_barrier();
-        FSTAMP(3);
+        SWEEP_STAMP(3);
         // ---- finish the member's elements: pre-activation = x-projection + the four K-quarters, in this order
         float z[4];
 #pragma unroll
@@ -202,7 +195,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_mf32_kernel(RnnArgs a) {
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) hv[nt] = tanh_acc(z[nt]);
         }
-        FSTAMP(4);
+        SWEEP_STAMP(4);
         if (s + 1 < T) {
             // publish: the thread of unit position j with (j & 4) == 0 carries units j and j + 4 of its row (lane + 4 holds the other)
             const unsigned slot_off = (unsigned)((s & 1) * P) * GPM * 16u, tag = (unsigned)(s + 1);
@@ -221,7 +214,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_mf32_kernel(RnnArgs a) {
                 }
             }
         }
-        FSTAMP(5);
+        SWEEP_STAMP(5);
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) { zl[nt] = z[nt]; hl[nt] = hv[nt]; }
         cl_ = cst;
@@ -237,9 +230,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_fwd_mf32_kernel(RnnArgs a) {
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) os[pm * 64 + nt * 16 + ej - ostep] = hl[nt];
     }
-#ifdef LAS_PROF
-    if (fprof) { a.dbg[2] = clock64(); a.dbg[3] = wall_clock64(); }
-#endif
+    sweep_prof_end(a.dbg, prof);
     if (errflag) { if (a.err) a.err[0] = 1; if (a.status) a.status[0] = a.status_code; }
 }
 
@@ -313,12 +304,9 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_mf32_kernel(RnnArgs a) {
         }
     };
     fetch(0, 0, 0, 0, T > 1);
-#ifdef LAS_PROF
-    const bool fprof = a.dbg && blockIdx.x == 0 && threadIdx.x == 0;
-    if (fprof) { a.dbg[0] = clock64(); a.dbg[1] = wall_clock64(); }
-#endif
+    const bool prof = sweep_prof_begin(a.dbg);
     for (int s = 0; s < T; ++s) {
-        FSTAMP(0);
+        SWEEP_STAMP(0);
         float g_[4], d_[TPM];
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) g_[nt] = ng[nt];
@@ -349,9 +337,9 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_mf32_kernel(RnnArgs a) {
         }
         gl += gstep; gs += gsstep; if (CELL == LAS_CELL_LSTM) cl += cstep; ol += ostep; dl += dstep;
         if (s + 1 == T) break;                                                   // the last step's dh has no consumer
-        FSTAMP(1);
+        SWEEP_STAMP(1);
         lds_barrier();
-        FSTAMP(2);
+        SWEEP_STAMP(2);
         // ---- partial dh of ALL units from the member's 64 columns
         float av[16];
         {
@@ -366,7 +354,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_mf32_kernel(RnnArgs a) {
         for (int ks = 0; ks < 16; ++ks)
 #pragma unroll
             for (int x = 0; x < TW; ++x) acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ks], wreg[x][ks], acc[x], 0, 0, 0);
-        FSTAMP(3);
+        SWEEP_STAMP(3);
         const unsigned slot_off = (unsigned)((s & 1) * P) * (unsigned)(P * TPM * 128) * 16u, tag = (unsigned)(s + 1);
         // ---- reduce-scatter: every unit tile goes to the member that owns it (rows 4 lk .. 4 lk + 3, unit li of the tile per lane)
 #pragma unroll
@@ -386,12 +374,14 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_mf32_kernel(RnnArgs a) {
         float sa[TPM], sb[TPM];
 #pragma unroll
         for (int q = 0; q < TPM; ++q) sa[q] = sb[q] = 0.f;
-        FSTAMP(4);
+        SWEEP_STAMP(4);
         if constexpr (P > 1) {
             constexpr int NH = P / 2;                                            // list positions of one thread (the last may not exist)
             u32x4_t xv[NH * TPM];
             const int par = er & 1;
             const unsigned gidx = (unsigned)((er >> 2) * 32 + ((er >> 1) & 1) * 16 + ej);
+            // (gather_tagged's poll, on its own text: list positions past the last partner are preset and never polled, and routed through the
+            //  shared helper that costs the tanh cell's H = 128 instance 3 VGPRs and one wave of occupancy)
 #pragma unroll
             for (int n = 0; n < NH; ++n)
 #pragma unroll
@@ -423,9 +413,9 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_mf32_kernel(RnnArgs a) {
 #pragma unroll
                 for (int q = 0; q < TPM; ++q) { sa[q] += __uint_as_float(xv[n * TPM + q].y); sb[q] += __uint_as_float(xv[n * TPM + q].z); }
         }
-        FSTAMP(5);
+        SWEEP_STAMP(5);
         lds_barrier();                                                           // own[] is complete; dzs may be rewritten
-        FSTAMP(6);
+        SWEEP_STAMP(6);
 #pragma unroll
         for (int q = 0; q < TPM; ++q) {
             // this thread's row: even rows are the granules' first value.  partner lane = the other row of the pair (tid ^ 16)
@@ -437,9 +427,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_mf32_kernel(RnnArgs a) {
             dhr[q] = own[(q * 4 + (er & 3)) * PT + (er >> 2) * 16 + ej] + (se + so);
         }
     }
-#ifdef LAS_PROF
-    if (fprof) { a.dbg[2] = clock64(); a.dbg[3] = wall_clock64(); }
-#endif
+    sweep_prof_end(a.dbg, prof);
     if (errflag) { if (a.err) a.err[0] = 1; if (a.status) a.status[0] = a.status_code; }
 }
 
