@@ -1657,8 +1657,11 @@ static int set_lds(K kern, int bytes) {
 // How a sweep runs (plan_sweep).  The 8-row kernels compact duplicated MFMA rows; of the sweep's modes, the helper-wave kernels alone
 // wait for x-projection chunks, FWD_HW8_RAGGED alone honours row_T, BWD_KS8_CH / _CH_PG alone wait for dout chunks (and publish progress).
 enum SweepPath { SWEEP_BF16, SWEEP_MF32, SWEEP_VALU };       // clustered bf16 MFMA / clustered exact-fp32 MFMA (rnn_seq_f32.hip) / round-1 VALU
-enum SweepKernel { SWEEP_NONE, FWD_PLAIN, FWD_HW16, FWD_HW8, FWD_HW8_RAGGED, BWD_PLAIN, BWD_KS16, BWD_KS8, BWD_KS8_CH, BWD_KS8_CH_PG };
-enum { SWEEP_ROWS = 1, SWEEP_CHUNKS = 2, SWEEP_PROGRESS = 4 };  // plan_sweep's `mode`: what the call asks of its kernel
+// (the values are public: las_rnn_seq_plan_kernel returns them, include/las_hip.h LAS_SWEEP_*)
+enum SweepKernel { SWEEP_NONE = LAS_SWEEP_NONE, FWD_PLAIN = LAS_SWEEP_FWD_PLAIN, FWD_HW16 = LAS_SWEEP_FWD_HW16, FWD_HW8 = LAS_SWEEP_FWD_HW8,
+                   FWD_HW8_RAGGED = LAS_SWEEP_FWD_HW8_RAGGED, BWD_PLAIN = LAS_SWEEP_BWD_PLAIN, BWD_KS16 = LAS_SWEEP_BWD_KS16, BWD_KS8 = LAS_SWEEP_BWD_KS8,
+                   BWD_KS8_CH = LAS_SWEEP_BWD_KS8_CH, BWD_KS8_CH_PG = LAS_SWEEP_BWD_KS8_CH_PG };
+enum { SWEEP_ROWS = LAS_SWEEP_MODE_ROWS, SWEEP_CHUNKS = LAS_SWEEP_MODE_CHUNKS, SWEEP_PROGRESS = LAS_SWEEP_MODE_PROGRESS };  // plan_sweep's `mode`: what the call asks of its kernel
 enum { PACK_FWD = 0, PACK_BWD = 1, PACK_KS = 2 };                // W_hh pack layouts (= SeqPrepJob::kind)
 struct SweepInst;
 struct SweepPlan {
@@ -1800,6 +1803,14 @@ extern "C" int las_rnn_seq_fwd_rows_ok(int cell, int prec, int B, int H, int fla
 extern "C" int las_rnn_seq_bwd_chunks_ok(int cell, int prec, int B, int H, int flags) { return plan_sweep(cell, prec, B, H, flags, true).dout_chunks; }
 extern "C" int las_rnn_seq_bwd_progress_words(int cell, int prec, int B, int H, int flags) {
     return plan_sweep(cell, prec, B, H, flags, true).progress_words;
+}
+extern "C" int las_rnn_seq_plan_kernel(int cell, int prec, int B, int H, int flags, int bwd, int mode, int* P, int* rows_per_tile, int* launches) {
+    const SweepPlan p = plan_sweep(cell, prec, B, H, flags, bwd != 0, mode);
+    const bool none = p.path != SWEEP_BF16 || !p.inst || B <= 0;
+    if (P) *P = none ? 0 : p.P;
+    if (rows_per_tile) *rows_per_tile = none ? 0 : p.rb;
+    if (launches) *launches = none ? 0 : cdiv(cdiv(B, p.rb), p.max_tiles);      // run_bf16's row chunks
+    return none ? SWEEP_NONE : p.kernel;
 }
 
 static int check_common(const char* who, int cell, int prec, int B, int T, int H, const void* gates, const void* w0,

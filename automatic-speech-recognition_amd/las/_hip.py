@@ -161,6 +161,7 @@ _SIGS = {
                                            c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_longlong,
                                            c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "las_rnn_seq_bwd_progress_words": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "las_rnn_seq_plan_kernel": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "las_rnn_seq_bwd_db_progress": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                             c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_longlong,
                                             c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
@@ -857,6 +858,19 @@ def rnn_seq_fwd_chunks_ok(cell, prec, B, H, flags=None):
 
 def rnn_seq_fwd_rows_ok(cell, prec, B, H, flags=None):
     return bool(lib().las_rnn_seq_fwd_rows_ok(cell, prec, B, H, seq_flags if flags is None else flags))
+
+
+# las_rnn_seq_plan_kernel's answers (include/las_hip.h LAS_SWEEP_*) and its `mode` bits
+SWEEP_KERNELS = ("NONE", "FWD_PLAIN", "FWD_HW16", "FWD_HW8", "FWD_HW8_RAGGED", "BWD_PLAIN", "BWD_KS16", "BWD_KS8", "BWD_KS8_CH", "BWD_KS8_CH_PG")
+SWEEP_MODE_ROWS, SWEEP_MODE_CHUNKS, SWEEP_MODE_PROGRESS = 1, 2, 4
+
+
+def rnn_seq_plan_kernel(cell, prec, B, H, flags=None, bwd=False, mode=0):
+    """(kernel name, cluster width, rows per tile, row-chunk launches) of the sweep the library would launch: host arithmetic, no GPU."""
+    P, rb, n = c_int(0), c_int(0), c_int(0)
+    k = int(lib().las_rnn_seq_plan_kernel(cell, prec, B, H, seq_flags if flags is None else flags, int(bool(bwd)), int(mode),
+                                          ctypes.byref(P), ctypes.byref(rb), ctypes.byref(n)))
+    return SWEEP_KERNELS[k], P.value, rb.value, n.value
 
 
 def rnn_seq_prepare(jobs):

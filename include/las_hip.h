@@ -261,6 +261,25 @@ int las_rnn_seq_bwd_chunks_ok(int cell, int prec, int B, int H, int flags);
  * window by window on another stream (las_wait_words_min, las_wgrad_ih_hh_window) instead of starting when it ends -- the bottom layer's are
  * the end-of-step tail of the reference's train step (las/las.py:272-283 can only run behind them). */
 int las_rnn_seq_bwd_progress_words(int cell, int prec, int B, int H, int flags);
+/* Which kernel a sweep of (cell, prec, B, H, flags) launches -- the same plan as the launch reads, pure host arithmetic like the *_ok queries
+ * above; it exists so that tests can name, and assert, the kernel a case runs (as las_speller_last_variant does for the Speller).  bwd: 0 the
+ * forward sweep, 1 BPTT.  mode: what the call asks of its kernel, LAS_SWEEP_MODE_ROWS (las_rnn_seq_fwd_rows), LAS_SWEEP_MODE_CHUNKS
+ * (las_rnn_seq_bwd_db_chunked), LAS_SWEEP_MODE_CHUNKS | LAS_SWEEP_MODE_PROGRESS (las_rnn_seq_bwd_db_progress); a mode the planned kernel does
+ * not serve leaves the kernel as it is (the calls refuse such a configuration: ask the *_ok queries).  Returns LAS_SWEEP_* and fills (each
+ * pointer may be NULL) the cluster width, the batch rows per tile (8 or 16) and the number of row-chunk launches the batch is swept in.
+ * LAS_SWEEP_NONE with zeros: the fp32 paths (parity mode, H outside {64, 128, 256, 512}), or no kernel at the picked width or a narrower one. */
+enum { LAS_SWEEP_NONE = 0,
+       LAS_SWEEP_FWD_PLAIN = 1,       /* plain bf16 MFMA forward, 16-row tiles (P = 1, LAS_SEQ_NO_HELPER_WAVES) */
+       LAS_SWEEP_FWD_HW16 = 2,        /* helper-wave forward, 16-row tiles */
+       LAS_SWEEP_FWD_HW8 = 3,         /* helper-wave forward, 8-row tiles */
+       LAS_SWEEP_FWD_HW8_RAGGED = 4,  /* ... honouring row_T */
+       LAS_SWEEP_BWD_PLAIN = 5,       /* plain bf16 MFMA BPTT (all-gather of dZ), 16-row tiles */
+       LAS_SWEEP_BWD_KS16 = 6,        /* K-split BPTT, 16-row tiles */
+       LAS_SWEEP_BWD_KS8 = 7,         /* K-split BPTT, 8-row tiles */
+       LAS_SWEEP_BWD_KS8_CH = 8,      /* ... waiting for chunks of dout */
+       LAS_SWEEP_BWD_KS8_CH_PG = 9 }; /* ... and publishing its progress */
+enum { LAS_SWEEP_MODE_ROWS = 1, LAS_SWEEP_MODE_CHUNKS = 2, LAS_SWEEP_MODE_PROGRESS = 4 };
+int las_rnn_seq_plan_kernel(int cell, int prec, int B, int H, int flags, int bwd, int mode, int* P, int* rows_per_tile, int* launches);
 int las_rnn_seq_bwd_db_progress(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
                                 const float* whh_bw, int ldw, const void* out, int ld_out, long long out_bstride,
                                 const void* cstate, const void* dout, int ld_dout, long long dout_bstride,

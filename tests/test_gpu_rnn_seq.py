@@ -10,6 +10,7 @@ CASES = [
     ("rnn", 0, 5, 7, 48), ("lstm", 0, 5, 7, 48), ("rnn", 0, 9, 12, 100), ("lstm", 0, 17, 9, 64),
     ("rnn", 1, 5, 7, 64), ("lstm", 1, 5, 7, 64), ("rnn", 1, 20, 33, 128), ("lstm", 1, 20, 33, 128),
     ("rnn", 1, 48, 40, 256), ("lstm", 1, 48, 40, 256), ("lstm", 0, 48, 20, 256), ("rnn", 1, 3, 5, 512), ("lstm", 1, 37, 23, 256), ("lstm", 1, 3, 1, 256),
+    ("lstm", 1, 20, 13, 512), ("rnn", 1, 16, 13, 512),       # the run.sh recipe's listener at its default plan (P = 8); the tanh cell at a full 16-row tile
     # parity mode on the clustered exact-fp32 MFMA sweeps (csrc/rnn_seq_f32.hip: H in {64, 128, 256, 512}; P = G H / 64 members per
     # (direction, 16-row tile): 1 ... 32), ragged last tiles, T = 1, and enough steps to go round the two exchange slots many times
     ("rnn", 0, 7, 9, 64), ("rnn", 0, 6, 10, 128), ("rnn", 0, 20, 15, 256), ("rnn", 0, 19, 8, 512),
