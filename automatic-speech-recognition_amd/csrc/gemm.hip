@@ -1,7 +1,8 @@
 // gemm.hip -- K1/K3/K4 dense contractions + their gradients for the LAS hot path (gfx950).
 //
 // Two arithmetic modes behind one entry point (include/las_hip.h: las_gemm):
-//   LAS_PREC_F32  : exact fp32 FMA chains on the VALU (64x64x16 LDS tile, 4x4 per thread).
+//   LAS_PREC_F32  : exact fp32 FMA chains on the matrix cores (v_mfma_f32_16x16x4_f32: one rounding per product, k-ordered --
+//                   bitwise a per-thread v_fmac loop), 64 x 64 or 128 x 128 tiles, a 64 x 32 skinny form with K slices for M <= 64.
 //   LAS_PREC_BF16 : operands rounded to bf16 while they are staged into LDS, fp32 accumulation on
 //                   the matrix cores (v_mfma_f32_16x16x32_bf16), 64-wide waves, WM x WN waves per
 //                   workgroup, TM x TN MFMA tiles per wave.
@@ -27,6 +28,67 @@ struct GemmArgs {
 };
 
 __device__ __forceinline__ float apply_act(float v, int act) { return act == LAS_ACT_TANH ? tanhf(v) : v; }
+
+// This workgroup's contraction range and operand / output bases: k-chunk bz of a split-K product, or batch entry bz.
+template <typename TI>
+__device__ __forceinline__ void gemm_slice(const GemmArgs& g, int bz, const TI*& A, const TI*& B, float*& C, int& kbeg, int& kend) {
+    A = reinterpret_cast<const TI*>(g.A);
+    B = reinterpret_cast<const TI*>(g.B);
+    C = g.C;
+    kbeg = 0; kend = g.K;
+    if (g.splitk > 1) {
+        kbeg = bz * g.kchunk;
+        kend = min(g.K, kbeg + g.kchunk);
+    } else {
+        A += (long long)bz * g.strideA;
+        B += (long long)bz * g.strideB;
+        C += (long long)bz * g.strideC;
+    }
+}
+
+// C(row, col) = act(alpha acc + bias + beta C).  FAST: the caller read the column's bias once (bcol; 0 without one), tanh_fast; else the
+// bias is read here and the activation is tanhf.
+template <bool FAST>
+__device__ __forceinline__ void gemm_finish(const GemmArgs& g, float* C, int row, int col, float acc, float bcol = 0.f) {
+    float v = g.alpha * acc;
+    if (FAST) v += bcol;
+    else if (g.bias) v += g.bias[col];
+    float* cp = C + (long long)row * g.ldc + col;
+    if (g.beta != 0.f) v += g.beta * (*cp);
+    *cp = FAST ? (g.act == LAS_ACT_TANH ? tanh_fast(v) : v) : apply_act(v, g.act);
+}
+// One output element of a tile: the partial of k-chunk bz when the product is split, else the finished value.
+template <bool FAST>
+__device__ __forceinline__ void gemm_store(const GemmArgs& g, float* C, int bz, int row, int col, float acc, float bcol = 0.f) {
+    if (g.splitk > 1) g.partial[((long long)bz * g.M + row) * g.N + col] = acc;
+    else gemm_finish<FAST>(g, C, row, col, acc, bcol);
+}
+
+// Tile of workgroup L of a 1-D grid (host side: gemm_grid), false for a workgroup of the padding.  Workgroup L runs on XCD L % 8 and
+// each XCD has its own L2:
+//   g.zgroup (split-K / batched products with few output tiles, the weight gradients): ALL tiles of one k-chunk (or batch entry) on ONE
+//     XCD and next to each other in dispatch order, so that the chunk's operand rows are fetched into that XCD's L2 once and shared by
+//     its tiles instead of every tile pulling them from HBM (tried: the plain 3-D order -- it spreads them over 8 L2s; its A/B switch is retired);
+//   ROW_ORDER and a tall output: all column tiles of one row block go to the same XCD back to back, so the row block of A is fetched
+//     into that L2 once instead of once per XCD.  (Only for tall outputs: with fewer than a few row blocks per XCD the plain 2-D order
+//     fills the chip better.)
+// Any other grid is 3-D and (bx, by, bz) stay the block indices.
+template <int BM, int BN, bool ROW_ORDER>
+__device__ __forceinline__ bool gemm_tile(const GemmArgs& g, int& bx, int& by, int& bz) {
+    const int nx = (g.N + BN - 1) / BN, ny = (g.M + BM - 1) / BM;
+    const int L = blockIdx.x, xcd = L & 7, li = L >> 3;
+    if (g.zgroup) {
+        const int nt = nx * ny;
+        bz = xcd + 8 * (li / nt);
+        if (bz >= g.zgroup) return false;
+        const int t = li % nt;
+        by = t / nx; bx = t % nx;
+    } else if (ROW_ORDER && gridDim.y == 1 && g.M > BM) {
+        by = xcd + 8 * (li / nx); bx = li % nx;
+        if (by >= ny) return false;
+    }
+    return true;
+}
 
 // ------------------------------------------------------------------------------------------------
 // generic tile loader: ROWS x 32 (bf16 path) of a strided fp32 operand into registers
@@ -120,6 +182,22 @@ __device__ __forceinline__ void tile_sstore(unsigned short* S, const TileRegs<RO
 // ------------------------------------------------------------------------------------------------
 // bf16 MFMA kernel
 // ------------------------------------------------------------------------------------------------
+// one k-tile (32 k) of a wave's TM x TN tiles: fragments from the [row][k] LDS tiles, then the MFMAs
+template <int TM, int TN>
+__device__ __forceinline__ void bf16_ktile_mfma(f32x4_t (&acc)[TM][TN], const unsigned short* As, const unsigned short* Bs, int wm, int wn, int lane) {
+    u16x8_t a[TM], b[TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+        a[i] = *reinterpret_cast<const u16x8_t*>(&As[((wm * TM + i) * 16 + (lane & 15)) * LDK + (lane >> 4) * 8]);
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+        b[j] = *reinterpret_cast<const u16x8_t*>(&Bs[((wn * TN + j) * 16 + (lane & 15)) * LDK + (lane >> 4) * 8]);
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = mfma_bf16_16x16x32(a[i], b[j], acc[i][j]);
+}
+
 template <int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_bf16_kernel(GemmArgs g) {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16, NT = WM * WN * 64;
@@ -130,18 +208,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_bf16_kernel(GemmArgs g) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w / WN, wn = w % WN;
     const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const float* A = g.A;
-    const float* B = g.B;
-    float* C = g.C;
-    int kbeg = 0, kend = g.K;
-    if (g.splitk > 1) {
-        kbeg = blockIdx.z * g.kchunk;
-        kend = min(g.K, kbeg + g.kchunk);
-    } else {
-        A += (long long)blockIdx.z * g.strideA;
-        B += (long long)blockIdx.z * g.strideB;
-        C += (long long)blockIdx.z * g.strideC;
-    }
+    const float* A; const float* B; float* C; int kbeg, kend;
+    gemm_slice(g, blockIdx.z, A, B, C, kbeg, kend);
 
     f32x4_t acc[TM][TN];
 #pragma unroll
@@ -164,17 +232,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_bf16_kernel(GemmArgs g) {
             tile_gload<BM, NT>(ra, A, g.rsA, g.ksA, m0, k0 + 32, g.M, kend, g.vecA, g.mask_period, g.mask_skip);
             tile_gload<BN, NT>(rb, B, g.rsB, g.ksB, n0, k0 + 32, g.N, kend, g.vecB, 0, 0);
         }
-        u16x8_t a[TM], b[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-            a[i] = *reinterpret_cast<const u16x8_t*>(&As[((wm * TM + i) * 16 + (lane & 15)) * LDK + (lane >> 4) * 8]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-            b[j] = *reinterpret_cast<const u16x8_t*>(&Bs[((wn * TN + j) * 16 + (lane & 15)) * LDK + (lane >> 4) * 8]);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = mfma_bf16_16x16x32(a[i], b[j], acc[i][j]);
+        bf16_ktile_mfma<TM, TN>(acc, As, Bs, wm, wn, lane);
     }
 
     // epilogue: lane holds rows (lane>>4)*4 + r, column lane&15 of each 16x16 tile
@@ -186,17 +244,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_bf16_kernel(GemmArgs g) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = m0 + (wm * TM + i) * 16 + (lane >> 4) * 4 + r;
-                if (row < g.M && col < g.N) {
-                    if (g.splitk > 1) {
-                        g.partial[((long long)blockIdx.z * g.M + row) * g.N + col] = acc[i][j][r];
-                    } else {
-                        float v = g.alpha * acc[i][j][r];
-                        if (g.bias) v += g.bias[col];
-                        float* cp = C + (long long)row * g.ldc + col;
-                        if (g.beta != 0.f) v += g.beta * (*cp);
-                        *cp = apply_act(v, g.act);
-                    }
-                }
+                if (row < g.M && col < g.N) gemm_store<false>(g, C, blockIdx.z, row, col, acc[i][j][r]);
             }
         }
 }
@@ -313,39 +361,11 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_bf16_fast_kernel(GemmArgs g)
     __shared__ __attribute__((aligned(16))) unsigned short lds[2 * (BM + BN) * LDK];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w / WN, wn = w % WN;
-    // XCD-aware tile order: workgroup L runs on XCD L % 8 (each XCD has its own L2).  All column tiles of one row block
-    // go to the same XCD back to back, so the row block of A is fetched into that L2 once instead of once per XCD.
-    // (Only for tall outputs: with fewer than a few row blocks per XCD the plain 2-D order fills the chip better.)
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    if (g.zgroup) {
-        // split-K / batched contractions with few output tiles (the weight gradients): 1-D grid, ALL tiles of one k-chunk (or
-        // batch entry) on ONE XCD and next to each other in dispatch order, so that the chunk's operand rows are fetched into that
-        // XCD's L2 once and shared by its tiles instead of every tile pulling them from HBM (the 3-D order spread them over 8 L2s)
-        const int nx = (g.N + BN - 1) / BN, ny = (g.M + BM - 1) / BM, nt = nx * ny;
-        const int L = blockIdx.x, xcd = L & 7, li = L >> 3;
-        bz = xcd + 8 * (li / nt);
-        if (bz >= g.zgroup) return;
-        const int t = li % nt;
-        by = t / nx; bx = t % nx;
-    } else if (gridDim.y == 1 && g.M > BM) {
-        const int nx = (g.N + BN - 1) / BN, ny = (g.M + BM - 1) / BM;
-        const int L = blockIdx.x, xcd = L & 7, li = L >> 3;
-        by = xcd + 8 * (li / nx); bx = li % nx;
-        if (by >= ny) return;
-    }
+    if (!gemm_tile<BM, BN, true>(g, bx, by, bz)) return;
     const int m0 = by * BM, n0 = bx * BN;
-    const TI* A = reinterpret_cast<const TI*>(g.A);
-    const TI* B = reinterpret_cast<const TI*>(g.B);
-    float* C = g.C;
-    int kbeg = 0, kend = g.K;
-    if (g.splitk > 1) {
-        kbeg = bz * g.kchunk;
-        kend = min(g.K, kbeg + g.kchunk);
-    } else {
-        A += (long long)bz * g.strideA;
-        B += (long long)bz * g.strideB;
-        C += (long long)bz * g.strideC;
-    }
+    const TI* A; const TI* B; float* C; int kbeg, kend;
+    gemm_slice(g, bz, A, B, C, kbeg, kend);
     f32x4_t acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -367,39 +387,19 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_bf16_fast_kernel(GemmArgs g)
             fast_gload<BM, NT, AKC, TI>(ra, A, g.rsA, g.ksA, m0, k0 + 32, g.M, kend);
             fast_gload<BN, NT, BKC, TI>(rb, B, g.rsB, g.ksB, n0, k0 + 32, g.N, kend);
         }
-        u16x8_t a[TM], b[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-            a[i] = *reinterpret_cast<const u16x8_t*>(&As[((wm * TM + i) * 16 + (lane & 15)) * LDK + (lane >> 4) * 8]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-            b[j] = *reinterpret_cast<const u16x8_t*>(&Bs[((wn * TN + j) * 16 + (lane & 15)) * LDK + (lane >> 4) * 8]);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = mfma_bf16_16x16x32(a[i], b[j], acc[i][j]);
+        bf16_ktile_mfma<TM, TN>(acc, As, Bs, wm, wn, lane);
         buf ^= 1;
     }
-    const bool has_bias = g.bias != nullptr, has_beta = g.beta != 0.f, do_tanh = g.act == LAS_ACT_TANH;
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int col = n0 + (wn * TN + j) * 16 + (lane & 15);
-            const float bcol = (has_bias && col < g.N) ? g.bias[col] : 0.f;
+            const float bcol = (g.bias && col < g.N) ? g.bias[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = m0 + (wm * TM + i) * 16 + (lane >> 4) * 4 + r;
-                if (row < g.M && col < g.N) {
-                    if (g.splitk > 1) {
-                        g.partial[((long long)bz * g.M + row) * g.N + col] = acc[i][j][r];
-                    } else {
-                        float v = g.alpha * acc[i][j][r] + bcol;
-                        float* cp = C + (long long)row * g.ldc + col;
-                        if (has_beta) v += g.beta * (*cp);
-                        *cp = do_tanh ? tanh_fast(v) : v;
-                    }
-                }
+                if (row < g.M && col < g.N) gemm_store<true>(g, C, bz, row, col, acc[i][j][r], bcol);
             }
         }
 }
@@ -440,27 +440,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_tr_kernel(GemmArgs g) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w / WN, wn = w % WN;
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    if (g.zgroup) {                                                  // all tiles of one k-chunk / batch entry on one XCD (see the fast kernel)
-        const int nx = g.N / BN, ny = (g.M + BM - 1) / BM, nt = nx * ny;
-        const int L = blockIdx.x, xcd = L & 7, li = L >> 3;
-        bz = xcd + 8 * (li / nt);
-        if (bz >= g.zgroup) return;
-        const int t = li % nt;
-        by = t / nx; bx = t % nx;
-    }
+    if (!gemm_tile<BM, BN, false>(g, bx, by, bz)) return;            // (never the row order: its grid is 3-D or grouped per k-chunk)
     const int m0 = by * BM, n0 = bx * BN;
-    const unsigned short* A = reinterpret_cast<const unsigned short*>(g.A);
-    const unsigned short* B = reinterpret_cast<const unsigned short*>(g.B);
-    float* C = g.C;
-    int kbeg = 0, kend = g.K;
-    if (g.splitk > 1) {
-        kbeg = bz * g.kchunk;
-        kend = min(g.K, kbeg + g.kchunk);
-    } else {
-        A += (long long)bz * g.strideA;
-        B += (long long)bz * g.strideB;
-        C += (long long)bz * g.strideC;
-    }
+    const unsigned short* A; const unsigned short* B; float* C; int kbeg, kend;
+    gemm_slice(g, bz, A, B, C, kbeg, kend);
     f32x4_t acc[4][TNF];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -516,25 +499,17 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_tr_kernel(GemmArgs g) {
             for (int j = 0; j < TNF; ++j) acc[i][j] = mfma_bf16_16x16x32(a[i], b[j], acc[i][j]);
         buf ^= 1;
     }
-    const bool has_bias = g.bias != nullptr, has_beta = g.beta != 0.f, do_tanh = g.act == LAS_ACT_TANH;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < TNF; ++j) {
             const int col = n0 + (wn * TNF + j) * 16 + (lane & 15);
-            const float bcol = has_bias ? g.bias[col] : 0.f;
+            const float bcol = g.bias ? g.bias[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = m0 + (wm * 4 + i) * 16 + (lane >> 4) * 4 + r;
                 if (BM == 64 && row >= g.M) continue;
-                if (g.splitk > 1) {
-                    g.partial[((long long)bz * g.M + row) * g.N + col] = acc[i][j][r];
-                } else {
-                    float v = g.alpha * acc[i][j][r] + bcol;
-                    float* cp = C + (long long)row * g.ldc + col;
-                    if (has_beta) v += g.beta * (*cp);
-                    *cp = do_tanh ? tanh_fast(v) : v;
-                }
+                gemm_store<true>(g, C, bz, row, col, acc[i][j][r], bcol);
             }
         }
 }
@@ -780,40 +755,30 @@ static bool g_tn_tr_on = true;
 #ifdef LAS_DEV   // development builds only (make prof): A/B switch, not part of the shipping library
 extern "C" void las_dev_gemm_tn_tr(int on) { g_tn_tr_on = on != 0; }       // development switch (A/B measurements)
 #endif
-static bool g_f32_valu = false;      // parity-mode products through the round-1 VALU tile loop instead of the exact-fp32 MFMA kernel
-#ifdef LAS_DEV   // development builds only (make prof): A/B switch, not part of the shipping library
-extern "C" void las_dev_gemm_f32_valu(int on) { g_f32_valu = on != 0; }
-#endif
-static bool g_f32_fast_ld = true;    // the exact-fp32 kernels' branch-free tile loader (tile_gload_f32fast)
-#ifdef LAS_DEV   // development builds only (make prof): A/B switch, not part of the shipping library
-extern "C" void las_dev_gemm_f32_fast_ld(int on) { g_f32_fast_ld = on != 0; }
-#endif
-static bool g_zgroup_on = true;
-#ifdef LAS_DEV   // development builds only (make prof): A/B switch, not part of the shipping library
-extern "C" void las_dev_gemm_zgroup(int on) { g_zgroup_on = on != 0; }     // development switch (A/B measurements)
-#endif
+
+// Grid of a kernel that finds its tile with gemm_tile, and g.zgroup: nx x ny tiles, zdim k-chunks / batch entries.
+static dim3 gemm_grid(GemmArgs& g, int nx, int ny, int zdim, bool row_order) {
+    g.zgroup = 0;
+    if (zdim > 1 && nx * ny <= 64) {                      // few tiles per k-chunk / batch entry: group them per XCD, entries padded to 8
+        g.zgroup = zdim;
+        return dim3(nx * ny * ((zdim + 7) / 8 * 8), 1, 1);
+    }
+    if (row_order && ny >= 64 && zdim == 1) return dim3(nx * ((ny + 7) / 8 * 8), 1, 1);   // tall output: row blocks padded to 8, XCD-aware order
+    return dim3(nx, ny, zdim);
+}
 
 template <int WM, int WN, int TM, int TN, typename TI>
-static void launch_fast_t(const GemmArgs& g, int zdim, hipStream_t st) {
+static void launch_fast_t(GemmArgs& g, int zdim, hipStream_t st) {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-    const int nx = cdiv(g.N, BN), ny = cdiv(g.M, BM);
-    const bool xcd_order = ny >= 64 && zdim == 1;        // tall output: 1-D grid, row blocks padded to 8, XCD-aware order
-    dim3 grid(xcd_order ? nx * ((ny + 7) / 8 * 8) : nx, xcd_order ? 1 : ny, zdim), blk(WM * WN * 64);
-    GemmArgs gz = g;
-    gz.zgroup = 0;
-    if (zdim > 1 && nx * ny <= 64 && g_zgroup_on) {      // few tiles per k-chunk / batch entry: group them per XCD (see the kernel)
-        gz.zgroup = zdim;
-        grid = dim3(nx * ny * ((zdim + 7) / 8 * 8), 1, 1);
-    }
-    const GemmArgs& g_ = gz;
+    const dim3 grid = gemm_grid(g, cdiv(g.N, BN), cdiv(g.M, BM), zdim, true), blk(WM * WN * 64);
     const bool akc = g.ksA == 1, bkc = g.ksB == 1;
-    if (akc && bkc)       hipLaunchKernelGGL((gemm_bf16_fast_kernel<WM, WN, TM, TN, true, true, TI>), grid, blk, 0, st, g_);
-    else if (akc && !bkc) hipLaunchKernelGGL((gemm_bf16_fast_kernel<WM, WN, TM, TN, true, false, TI>), grid, blk, 0, st, g_);
-    else if (!akc && bkc) hipLaunchKernelGGL((gemm_bf16_fast_kernel<WM, WN, TM, TN, false, true, TI>), grid, blk, 0, st, g_);
-    else                  hipLaunchKernelGGL((gemm_bf16_fast_kernel<WM, WN, TM, TN, false, false, TI>), grid, blk, 0, st, g_);
+    if (akc && bkc)       hipLaunchKernelGGL((gemm_bf16_fast_kernel<WM, WN, TM, TN, true, true, TI>), grid, blk, 0, st, g);
+    else if (akc && !bkc) hipLaunchKernelGGL((gemm_bf16_fast_kernel<WM, WN, TM, TN, true, false, TI>), grid, blk, 0, st, g);
+    else if (!akc && bkc) hipLaunchKernelGGL((gemm_bf16_fast_kernel<WM, WN, TM, TN, false, true, TI>), grid, blk, 0, st, g);
+    else                  hipLaunchKernelGGL((gemm_bf16_fast_kernel<WM, WN, TM, TN, false, false, TI>), grid, blk, 0, st, g);
 }
 template <int WM, int WN, int TM, int TN>
-static void launch_fast(const GemmArgs& g, int zdim, hipStream_t st) {
+static void launch_fast(GemmArgs& g, int zdim, hipStream_t st) {
     if (g.in_bf16) launch_fast_t<WM, WN, TM, TN, unsigned short>(g, zdim, st);
     else           launch_fast_t<WM, WN, TM, TN, float>(g, zdim, st);
 }
@@ -821,7 +786,7 @@ static void launch_fast(const GemmArgs& g, int zdim, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------
 // exact-fp32 MFMA kernel (parity mode, round 4).  v_mfma_f32_16x16x4_f32 is a k-ordered fp32 fma chain -- one rounding per
 // product, bitwise what a per-thread v_fmac loop gives -- at the VALU's peak rate but from one operand register per lane and
-// with the VALU free for addressing: the 64x64x16 VALU tile loop below it replaced ran at ~10 % of that peak.  Same strided
+// with the VALU free for addressing (tried first, round 1: a 64x64x16 VALU tile loop, 4 x 4 outputs per thread -> ~10 % of that peak; retired).  Same strided
 // operand description as the other kernels (NN / NT / TN, batching, contraction mask, deterministic split-K, fused bias /
 // beta / tanh epilogue), the guarded generic loader, register double buffering: the next k-tile's global loads fly under the
 // 32 x TM x TN MFMAs of the current one.  LDS tiles are k-major ([32][BM + 20] fp32: a lane's A operand is row k0 + (lane >> 4),
@@ -878,12 +843,7 @@ __device__ __forceinline__ void tile_gload_f32fast(TileRegs<ROWS, NT>& r, const 
         }
     }
 }
-#ifndef LAS_SKINNY_KSLICE
-#define LAS_SKINNY_KSLICE 256     // the skinny fp32 product's K slices: K / this many, capped by 512 / column blocks
-#endif
-#ifndef LAS_MF32_PIPE
-#define LAS_MF32_PIPE 1
-#endif
+constexpr int LAS_SKINNY_KSLICE = 256;   // the skinny fp32 product's K slices: K / this many, capped by 512 / column blocks
 template <int ROWS, int NT, int LD, bool IS_A>
 __device__ __forceinline__ void tile_gload_f32(TileRegs<ROWS, NT>& r, const float* __restrict__ X, long long rs, long long ks,
                                                int row0, int k0, int R, int Kend, int vec, int mperiod, int mskip) {
@@ -901,18 +861,8 @@ __global__ __launch_bounds__(256) void gemm_mf32_kernel(GemmArgs g) {
     float* Bs = lds + 32 * PA;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wm = w >> 1, wn = w & 1, li = lane & 15, lk = lane >> 4;
     const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const float* A = g.A;
-    const float* B = g.B;
-    float* C = g.C;
-    int kbeg = 0, kend = g.K;
-    if (g.splitk > 1) {
-        kbeg = blockIdx.z * g.kchunk;
-        kend = min(g.K, kbeg + g.kchunk);
-    } else {
-        A += (long long)blockIdx.z * g.strideA;
-        B += (long long)blockIdx.z * g.strideB;
-        C += (long long)blockIdx.z * g.strideC;
-    }
+    const float* A; const float* B; float* C; int kbeg, kend;
+    gemm_slice(g, blockIdx.z, A, B, C, kbeg, kend);
     f32x4_t acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -924,24 +874,21 @@ __global__ __launch_bounds__(256) void gemm_mf32_kernel(GemmArgs g) {
         tile_gload_f32<BM, NT, LD, true>(ra, A, g.rsA, g.ksA, m0, kbeg, g.M, kend, g.vecA, g.mask_period, g.mask_skip);
         tile_gload_f32<BN, NT, LD, false>(rb, B, g.rsB, g.ksB, n0, kbeg, g.N, kend, g.vecB, 0, 0);
     }
-#ifndef LAS_MF32_ABL
-#define LAS_MF32_ABL 0       // timing experiments: 1 = no global loads after the first tile, 2 = no LDS stores / barriers after the first tile
-#endif
     for (int k0 = kbeg; k0 < kend; k0 += 32) {
-        if (!(LAS_MF32_ABL & 2) || k0 == kbeg) {
         __syncthreads();
         tile_sstore_f32<BM, NT>(As, ra, g.ksA);
         tile_sstore_f32<BN, NT>(Bs, rb, g.ksB);
         __syncthreads();
-        }
-        if (k0 + 32 < kend && !(LAS_MF32_ABL & 1)) {
+        if (k0 + 32 < kend) {
             tile_gload_f32<BM, NT, LD, true>(ra, A, g.rsA, g.ksA, m0, k0 + 32, g.M, kend, g.vecA, g.mask_period, g.mask_skip);
             tile_gload_f32<BN, NT, LD, false>(rb, B, g.rsB, g.ksB, n0, k0 + 32, g.N, kend, g.vecB, 0, 0);
         }
         const float* ap = As + lk * PA + wm * TM * 16 + li;
         const float* bp = Bs + lk * PB + wn * TN * 16 + li;
-#if LAS_MF32_PIPE
-        // the operands of k-step ks + 1 are read while the MFMAs of k-step ks run (two register sets)
+        // the operands of k-step ks + 1 are read while the MFMAs of k-step ks run (two register sets; tried: reading them in the k-step that
+        // uses them -> 3 % slower on the weight-gradient shapes, the same on the others.  Ablation builds of this loop, retired, record in
+        // profiles/r5_f32_gemm_ablation.txt: 76-84 % of the fp32 matrix peak without the global loads after the first k-tile, 72-82 % without
+        // the LDS stores and barriers, 87-91 % without both)
         float a[2][TM], b[2][TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i) a[0][i] = ap[i * 16];
@@ -961,24 +908,10 @@ __global__ __launch_bounds__(256) void gemm_mf32_kernel(GemmArgs g) {
                 for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[ks & 1][j], a[ks & 1][i], acc[i][j], 0, 0, 0);   // (C^T tiles: see the epilogue)
             __builtin_amdgcn_sched_barrier(0);       // keep the next k-step's reads in front of this k-step's MFMAs
         }
-#else
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {             // (k beyond kend was loaded as zeros: whole k-steps always)
-            float a[TM], b[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[i] = ap[ks * 4 * PA + i * 16];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = bp[ks * 4 * PB + j * 16];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[j], a[i], acc[i][j], 0, 0, 0);
-        }
-#endif
     }
     // epilogue.  The products above are issued with the operands swapped (B fragment first): a tile comes out TRANSPOSED, lane (li, lk)
     // holds row li and the four CONSECUTIVE columns 4 lk .. 4 lk + 3 -- one 16-byte store per tile and lane instead of four 4-byte stores
-    // to four rows (round 5; every dot product is the same k-ordered fma chain: bit-identical)
+    // to four rows (round 5; every dot product is the same k-ordered fma chain: bit-identical).  Own text, not gemm_store: four columns at a time.
     const bool cvec = (g.ldc % 4) == 0 && (((uintptr_t)C) & 15) == 0 && (g.N % 4) == 0;
     const bool pvec = (g.N % 4) == 0;
 #pragma unroll
@@ -1034,18 +967,8 @@ __global__ __launch_bounds__(256) void gemm_mf32_skinny_kernel(GemmArgs g) {
     float* Bs = lds + BK * PA;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
     const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const float* A = g.A;
-    const float* B = g.B;
-    float* C = g.C;
-    int kbeg = 0, kend = g.K;
-    if (g.splitk > 1) {                          // K slices over blockIdx.z: 64 column blocks alone leave three quarters of the chip idle
-        kbeg = blockIdx.z * g.kchunk;
-        kend = min(g.K, kbeg + g.kchunk);
-    } else {
-        A += (long long)blockIdx.z * g.strideA;
-        B += (long long)blockIdx.z * g.strideB;
-        C += (long long)blockIdx.z * g.strideC;
-    }
+    const float* A; const float* B; float* C; int kbeg, kend;
+    gemm_slice(g, blockIdx.z, A, B, C, kbeg, kend);          // (split: K slices -- 64 column blocks alone leave three quarters of the chip idle)
     f32x4_t acc[TMS][2];
 #pragma unroll
     for (int i = 0; i < TMS; ++i)
@@ -1103,99 +1026,8 @@ __global__ __launch_bounds__(256) void gemm_mf32_skinny_kernel(GemmArgs g) {
         const int o = ((rl >> 4) * 2 + (cl >> 4)) * 256 + (rl & 15) * 16 + (cl & 15);
         const float sum = ((red[o] + red[TMS * 512 + o]) + red[2 * TMS * 512 + o]) + red[3 * TMS * 512 + o];
         const int row = m0 + rl, col = n0 + cl;
-        if (row < g.M && col < g.N && g.splitk > 1) {
-            g.partial[((long long)blockIdx.z * g.M + row) * g.N + col] = sum;
-        } else if (row < g.M && col < g.N) {
-            float v = g.alpha * sum;
-            if (g.bias) v += g.bias[col];
-            float* cp = C + (long long)row * g.ldc + col;
-            if (g.beta != 0.f) v += g.beta * (*cp);
-            *cp = apply_act(v, g.act);
-        }
+        if (row < g.M && col < g.N) gemm_store<false>(g, C, blockIdx.z, row, col, sum);
     }
-}
-
-// ------------------------------------------------------------------------------------------------
-// fp32 VALU kernel (parity mode)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
-    constexpr int BM = 64, BN = 64, BK = 16;
-    __shared__ float As[BK][BM + 4];
-    __shared__ float Bs[BK][BN + 4];
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const float* A = g.A;
-    const float* B = g.B;
-    float* C = g.C;
-    int kbeg = 0, kend = g.K;
-    if (g.splitk > 1) {
-        kbeg = blockIdx.z * g.kchunk;
-        kend = min(g.K, kbeg + g.kchunk);
-    } else {
-        A += (long long)blockIdx.z * g.strideA;
-        B += (long long)blockIdx.z * g.strideB;
-        C += (long long)blockIdx.z * g.strideC;
-    }
-    float acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-
-    for (int k0 = kbeg; k0 < kend; k0 += BK) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int m, k;
-            if (g.ksA == 1) { k = tid & 15; m = (tid >> 4) + 16 * i; }
-            else            { m = tid & 63; k = (tid >> 6) + 4 * i; }
-            const int gm = m0 + m, gk = k0 + k;
-            float v = 0.f;
-            if (gm < g.M && gk < kend && !(g.mask_period > 0 && (gk % g.mask_period) == g.mask_skip))
-                v = A[(long long)gm * g.rsA + (long long)gk * g.ksA];
-            As[k][m] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int n, k;
-            if (g.ksB == 1) { k = tid & 15; n = (tid >> 4) + 16 * i; }
-            else            { n = tid & 63; k = (tid >> 6) + 4 * i; }
-            const int gn = n0 + n, gk = k0 + k;
-            float v = 0.f;
-            if (gn < g.N && gk < kend) v = B[(long long)gn * g.rsB + (long long)gk * g.ksB];
-            Bs[k][n] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < BK; ++k) {
-            float a[4], b[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = As[k][ty * 4 + i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = Bs[k][tx * 4 + j];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int row = m0 + ty * 4 + i, col = n0 + tx * 4 + j;
-            if (row < g.M && col < g.N) {
-                if (g.splitk > 1) {
-                    g.partial[((long long)blockIdx.z * g.M + row) * g.N + col] = acc[i][j];
-                } else {
-                    float v = g.alpha * acc[i][j];
-                    if (g.bias) v += g.bias[col];
-                    float* cp = C + (long long)row * g.ldc + col;
-                    if (g.beta != 0.f) v += g.beta * (*cp);
-                    *cp = apply_act(v, g.act);
-                }
-            }
-        }
 }
 
 // fixed-order reduction of the split-K partials + epilogue
@@ -1205,20 +1037,15 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmArgs g) {
         const int row = (int)(idx / g.N), col = (int)(idx % g.N);
         float s = 0.f;
         for (int z = 0; z < g.splitk; ++z) s += g.partial[(long long)z * total + idx];
-        float v = g.alpha * s;
-        if (g.bias) v += g.bias[col];
-        float* cp = g.C + (long long)row * g.ldc + col;
-        if (g.beta != 0.f) v += g.beta * (*cp);
-        *cp = apply_act(v, g.act);
+        gemm_finish<false>(g, g.C, row, col, s);
     }
 }
 
 template <int WM, int WN, int TM, int TN>
-static int launch_bf16(const GemmArgs& g, int zdim, hipStream_t st) {
+static void launch_bf16(const GemmArgs& g, int zdim, hipStream_t st) {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     dim3 grid(cdiv(g.N, BN), cdiv(g.M, BM), zdim);
     hipLaunchKernelGGL((gemm_bf16_kernel<WM, WN, TM, TN>), grid, dim3(WM * WN * 64), 0, st, g);
-    return 0;
 }
 
 template <int TM, int TN>
@@ -1250,21 +1077,46 @@ static void launch_mf32_skinny(const GemmArgs& g, int ld, int row_tiles, dim3 gr
     }
 }
 
-// Scratch the deterministic split-K of las_gemm would use for this product if it could have all it wants (never more than
-// LAS_GEMM_WS_CAP: beyond that the split degree is cut to fit, with any workspace): tile counts as in las_gemm_dt below.
-extern "C" size_t las_gemm_workspace_bytes(int prec, int M, int N, int K, int batch) {
-    if (M <= 0 || N <= 0 || batch != 1) return 0;
-    const int b = (M < 128 || N < 128) ? 64 : 128;        // (both precisions; the bf16 48-row tile has one row block like the 64-row one)
+// The deterministic split of a product's contraction, for the launch and for the scratch query alike: `degree` partial [M][N] fp32 slabs
+// (what the scratch is sized by), cut to what fits into `avail` bytes, laid out as splitk chunks of kchunk (whole 32-wide k-tiles).
+//   tall contractions that would leave most of the 256 CUs idle: K >= 2048 and fewer than 256 output tiles -> 512-row chunks, aiming
+//     at 512 workgroups.  The tile edge is 64 below 128 rows or columns, else 128, in both precisions (the bf16 48-row tile has one
+//     row block like the 64-row one);
+//   else the parity mode's skinny products (M <= 64, K >= 512: the Speller's per-step cell products, 64 / 36 column blocks of a
+//     latency-bound K walk): K slices of LAS_SKINNY_KSLICE, at most 512 / column blocks of them.
+// Batched products are not split.  M, N > 0.
+struct GemmSplit { int degree, splitk, kchunk; };
+static GemmSplit gemm_split(int prec, int M, int N, int K, int batch, size_t avail) {
+    GemmSplit r = {1, 1, K};
+    if (batch != 1) return r;
+    const size_t fit = avail / ((size_t)M * N * sizeof(float));
+    const int b = (M < 128 || N < 128) ? 64 : 128;
     const long long tiles = (long long)cdiv(M, b) * cdiv(N, b);
     int s = 1;
-    if (K >= 2048 && tiles < 256) {                        // the tall-contraction rule
+    if (K >= 2048 && tiles < 256) {
         const int want = (int)((512 + tiles - 1) / tiles), maxs = K / 512;
         s = want < maxs ? want : maxs;
+        if ((size_t)s > fit) s = (int)fit;
     }
-    if (s <= 1 && prec == LAS_PREC_F32 && M <= 64 && K >= 512) {       // the parity mode's skinny products: K slices (las_gemm_dt)
+    if (s <= 1 && prec == LAS_PREC_F32 && M <= 64 && K >= 512) {
+        const int want = 512 / cdiv(N, 32);
         s = K / LAS_SKINNY_KSLICE;
-        if (s > 512 / cdiv(N, 32)) s = 512 / cdiv(N, 32);
+        if (s > want) s = want;
+        if ((size_t)s > fit) s = (int)fit;
     }
+    if (s > 1) {
+        r.degree = s;
+        r.kchunk = ((K + s - 1) / s + 31) / 32 * 32;
+        r.splitk = (K + r.kchunk - 1) / r.kchunk;
+    }
+    return r;
+}
+
+// Scratch the deterministic split-K of las_gemm would use for this product if it could have all it wants (never more than
+// LAS_GEMM_WS_CAP: beyond that the split degree is cut to fit, with any workspace).
+extern "C" size_t las_gemm_workspace_bytes(int prec, int M, int N, int K, int batch) {
+    if (M <= 0 || N <= 0) return 0;
+    const int s = gemm_split(prec, M, N, K, batch, ~(size_t)0).degree;
     if (s <= 1) return 0;
     const size_t need = (size_t)s * M * N * sizeof(float);
     return need < LAS_GEMM_WS_CAP ? need : LAS_GEMM_WS_CAP;
@@ -1305,105 +1157,49 @@ extern "C" int las_gemm_dt(int prec, int transA, int transB, int M, int N, int K
     g.vecA = ((lda % 4) == 0) && (((uintptr_t)A & amask) == 0) && ((strideA % 4) == 0);
     g.vecB = ((ldb % 4) == 0) && (((uintptr_t)B & amask) == 0) && ((strideB % 4) == 0);
     g.splitk = 1; g.kchunk = K; g.partial = nullptr;
-    g.in_bf16 = in_dtype == LAS_DT_BF16;
+    g.in_bf16 = in_dtype == LAS_DT_BF16; g.zgroup = 0;
 
     // tile configuration
-    int BM, BN;
     int cfg;
     // branch-free fast path: 16-byte loads legal, k (or row) counts multiples of 4, no contraction mask
     const bool fastA = g.vecA && (g.ksA == 1 ? (K % 4 == 0) : (M % 4 == 0 && M >= 4));
     const bool fastB = g.vecB && (g.ksB == 1 ? (K % 4 == 0) : (N % 4 == 0 && N >= 4));
     const bool fast_ok = prec == LAS_PREC_BF16 && fastA && fastB && a_mask_period == 0 && K > 0;
-    // exact-fp32 kernels: the same conditions select their branch-free loader (1 + A k-contiguous + 2 B k-contiguous; 0 = generic)
-    const int f32_ld = (g_f32_fast_ld && fastA && fastB && a_mask_period == 0 && K > 0) ? 1 + (g.ksA == 1 ? 1 : 0) + (g.ksB == 1 ? 2 : 0) : 0;
-    if (prec == LAS_PREC_F32) { cfg = 0; BM = BN = (M < 128 || N < 128) ? 64 : 128; }    // exact-fp32 MFMA tiles
-    else if (M <= 48 && !(fast_ok && K >= 4096)) { cfg = 3; BM = 48; BN = 64; }   // tall contractions: 64-row fast tiles win
-    else if (M < 128 || N < 128) { cfg = 2; BM = 64; BN = 64; }
-    else                      { cfg = 1; BM = 128; BN = 128; }
-    const long long tiles = (long long)cdiv(M, BM) * cdiv(N, BN);
+    // exact-fp32 kernels: the same conditions select their branch-free loader (1 + A k-contiguous + 2 B k-contiguous; 0 = generic).
+    // (tried: the generic loader for these products too -> 44-57 % of the fp32 matrix peak, see tile_gload_f32fast; its A/B switch is retired)
+    const int f32_ld = (fastA && fastB && a_mask_period == 0 && K > 0) ? 1 + (g.ksA == 1 ? 1 : 0) + (g.ksB == 1 ? 2 : 0) : 0;
+    if (prec == LAS_PREC_F32) cfg = 0;                                             // exact-fp32 MFMA tiles
+    else if (M <= 48 && !(fast_ok && K >= 4096)) cfg = 3;                          // 48 x 64; tall contractions: 64-row fast tiles win
+    else if (M < 128 || N < 128) cfg = 2;                                          // 64 x 64
+    else cfg = 1;                                                                  // 128 x 128
 
-    // deterministic split-K for tall contractions that would leave most of the 256 CUs idle
-    if (batch == 1 && ws && K >= 2048 && tiles < 256) {
-        int want = (int)((512 + tiles - 1) / tiles);
-        int maxs = K / 512;
-        int s = want < maxs ? want : maxs;
-        while (s > 1 && (size_t)s * M * N * sizeof(float) > ws_bytes) --s;
-        if (s > 1) {
-            int kchunk = ((K + s - 1) / s + 31) / 32 * 32;
-            s = (K + kchunk - 1) / kchunk;
-            g.splitk = s; g.kchunk = kchunk; g.partial = (float*)ws;
-        }
-    }
-    // parity mode, skinny products (the Speller's per-step cell products): 64 / 36 column blocks of a latency-bound K walk -> K slices
-    if (prec == LAS_PREC_F32 && !g_f32_valu && M <= 64 && batch == 1 && ws && g.splitk == 1 && K >= 512) {
-        const int blocks = cdiv(N, 32);
-        int s = K / LAS_SKINNY_KSLICE, want = 512 / blocks;
-        if (s > want) s = want;
-        while (s > 1 && (size_t)s * M * N * sizeof(float) > ws_bytes) --s;
-        if (s > 1) {
-            const int kchunk = ((K + s - 1) / s + 31) / 32 * 32;
-            g.splitk = (K + kchunk - 1) / kchunk; g.kchunk = kchunk; g.partial = (float*)ws;
-        }
-    }
+    const GemmSplit sp = gemm_split(prec, M, N, K, batch, ws ? ws_bytes : 0);
+    if (sp.splitk > 1) { g.splitk = sp.splitk; g.kchunk = sp.kchunk; g.partial = (float*)ws; }
     const int zdim = g.splitk > 1 ? g.splitk : batch;
 
-    if (K == 0 && g.splitk == 1) {
-        // empty contraction: C = act(beta*C + bias); run the kernel with no k-tiles
-    }
     LAS_ARG(!g.in_bf16 || (fast_ok && cfg != 3) || (fast_ok && M <= 48),
             "las_gemm: bf16 operands are served by the branch-free path only (aligned pitches, K / row counts multiples of 4, no mask)");
-    if (g.in_bf16 && cfg == 3) { cfg = 2; BM = 64; BN = 64; }
+    if (g.in_bf16 && cfg == 3) cfg = 2;
     // weight-gradient form (both operands k-strided bf16, whole 128 x 128 tiles, 16-byte aligned rows): LDS-transposing kernel
     const bool tn_al = g_tn_tr_on && fast_ok && g.in_bf16 && g.ksA != 1 && g.ksB != 1 && N % 128 == 0 &&
                        lda % 8 == 0 && ldb % 8 == 0 && strideA % 8 == 0 && strideB % 8 == 0 && (((uintptr_t)A | (uintptr_t)B) & 15) == 0;
     const bool tn_tr = tn_al && cfg == 1 && M % 128 == 0;
     const bool tn_tr64 = tn_al && cfg == 2 && M <= 64 && M % 8 == 0 && batch == 1;     // (a first layer's dW_ih; one row block)
-    if (fast_ok && (cfg == 1 || cfg == 2)) {
-        if (tn_tr64) {
-            const int nx = N / 128;
-            GemmArgs gz = g;
-            gz.zgroup = 0;
-            dim3 grid(nx, 1, zdim);
-            if (zdim > 1 && nx <= 64 && g_zgroup_on) {
-                gz.zgroup = zdim;
-                grid = dim3(nx * ((zdim + 7) / 8 * 8), 1, 1);
-            }
-            hipLaunchKernelGGL(gemm_tn_tr_kernel<64>, grid, dim3(256), 0, st, gz);
-        }
-        else if (tn_tr) {
-            const int nx = N / 128, ny = M / 128;
-            GemmArgs gz = g;
-            gz.zgroup = 0;
-            dim3 grid(nx, ny, zdim);
-            if (zdim > 1 && nx * ny <= 64 && g_zgroup_on) {
-                gz.zgroup = zdim;
-                grid = dim3(nx * ny * ((zdim + 7) / 8 * 8), 1, 1);
-            }
-            hipLaunchKernelGGL(gemm_tn_tr_kernel<128>, grid, dim3(256), 0, st, gz);
-        }
-        else if (cfg == 1) launch_fast<2, 2, 4, 4>(g, zdim, st);
-        else          launch_fast<2, 2, 2, 2>(g, zdim, st);
-        LAS_LAUNCHED();
-        if (g.splitk > 1) {
-            int nb = cdiv((long long)M * N, 256);
-            if (nb > 2048) nb = 2048;
-            hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(nb), dim3(256), 0, st, g);
-            LAS_LAUNCHED();
-        }
-        return 0;
+    if (fast_ok && tn_tr64) {
+        const dim3 grid = gemm_grid(g, N / 128, 1, zdim, false);
+        hipLaunchKernelGGL(gemm_tn_tr_kernel<64>, grid, dim3(256), 0, st, g);
+    } else if (fast_ok && tn_tr) {
+        const dim3 grid = gemm_grid(g, N / 128, M / 128, zdim, false);
+        hipLaunchKernelGGL(gemm_tn_tr_kernel<128>, grid, dim3(256), 0, st, g);
     }
-    switch (cfg) {
-        case 0: {
-            dim3 grid(cdiv(N, BN), cdiv(M, BM), zdim);
-            if (g_f32_valu) hipLaunchKernelGGL(gemm_f32_kernel, dim3(cdiv(N, 64), cdiv(M, 64), zdim), dim3(256), 0, st, g);
-            else if (M <= 64) launch_mf32_skinny(g, f32_ld, cdiv(M, 16), dim3(cdiv(N, 32), 1, zdim), st);
-            else if (BM == 128) launch_mf32<4, 4>(g, f32_ld, grid, st);
-            else launch_mf32<2, 2>(g, f32_ld, grid, st);
-        } break;
-        case 1: launch_bf16<2, 2, 4, 4>(g, zdim, st); break;
-        case 2: launch_bf16<2, 2, 2, 2>(g, zdim, st); break;
-        default: launch_bf16<1, 4, 3, 1>(g, zdim, st); break;
-    }
+    else if (fast_ok && cfg == 1) launch_fast<2, 2, 4, 4>(g, zdim, st);
+    else if (fast_ok && cfg == 2) launch_fast<2, 2, 2, 2>(g, zdim, st);
+    else if (cfg == 1) launch_bf16<2, 2, 4, 4>(g, zdim, st);
+    else if (cfg == 2) launch_bf16<2, 2, 2, 2>(g, zdim, st);
+    else if (cfg == 3) launch_bf16<1, 4, 3, 1>(g, zdim, st);
+    else if (M <= 64) launch_mf32_skinny(g, f32_ld, cdiv(M, 16), dim3(cdiv(N, 32), 1, zdim), st);
+    else if (M < 128 || N < 128) launch_mf32<2, 2>(g, f32_ld, dim3(cdiv(N, 64), cdiv(M, 64), zdim), st);
+    else launch_mf32<4, 4>(g, f32_ld, dim3(cdiv(N, 128), cdiv(M, 128), zdim), st);
     LAS_LAUNCHED();
     if (g.splitk > 1) {
         int nb = cdiv((long long)M * N, 256);

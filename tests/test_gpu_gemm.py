@@ -30,6 +30,9 @@ CASES = [
     (512, 1024, 3000, 1, 0), (128, 30, 512, 0, 0), (48, 2048, 1152, 0, 0), (48, 1152, 2048, 0, 1),
     (39, 256, 2500, 1, 0), (7, 5, 3, 0, 0), (1, 128, 64, 0, 0), (200, 200, 33, 1, 1),
     (33, 100, 300, 0, 0), (64, 96, 130, 1, 0), (17, 40, 260, 0, 1), (48, 30, 512, 0, 0),       # M <= 64: the parity mode's skinny exact-fp32 MFMA kernel
+    # 65 row blocks (no multiple of 8: padding workgroups return), ragged last one: the bf16 fast kernel's XCD-aware 1-D tile order,
+    # at 64-row tiles with a column tail, and at 128-row tiles with a k-contiguous B
+    (4100, 72, 36, 0, 0), (8200, 130, 40, 0, 1),
 ]
 
 
