@@ -90,6 +90,13 @@ class SeqPrepareDesc(ctypes.Structure):
                 ("flags", c_int), ("ws", c_void_p), ("ws_bytes", c_size_t)]
 
 
+class FrontendArgs(ctypes.Structure):
+    """include/las_hip.h las_frontend_args"""
+    _fields_ = [("samples", c_void_p), ("samples_i16", c_int), ("ld_samples", c_longlong), ("n_samples", c_void_p), ("n_samples_host", POINTER(c_int))] + \
+               [(n, c_int) for n in ("n", "Tmax", "fl", "step", "feat_type", "feat_dim", "num_filters", "cmvn")] + \
+               [("twiddle", c_void_p), ("fb", c_void_p), ("fb_range", c_void_p), ("dct", c_void_p), ("out", c_void_p), ("ws", c_void_p), ("ws_bytes", c_size_t)]
+
+
 _SIGS = {
     "las_version": (c_int, []),
     "las_rnn_seq_prepare": (c_int, [POINTER(SeqPrepareDesc), c_int, c_void_p]),
@@ -194,6 +201,8 @@ _SIGS = {
     "las_input_release": (c_int, [c_void_p, c_int]),
     "las_input_records": (c_longlong, [c_void_p]),
     "las_input_close": (None, [c_void_p]),
+    "las_frontend_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "las_frontend": (c_int, [POINTER(FrontendArgs), c_void_p]),
 }
 
 

@@ -94,6 +94,8 @@ _EXTRA = [
     (("--ctc_decode_weight",), float, 0.0, "Weight of the CTC prefix scores in joint CTC-attention beam search (needs --ctc True; 0: attention "
                                            "(+ LM) scores only).  A candidate scores logit + weight * (CTC prefix score gain)."),
     (("--lm_dir",), str, "lang/output/", "Output directory of train_lm.py (result.json, vocab.json, models) for --apply_lm."),
+    (("--frontend",), str, "cpu", "Feature extraction of preprocess.py: cpu = the float64 numpy restatement, gpu = the HIP front end "
+                                  "(las.frontend.FeatureExtractor, fp32)."),
 ]
 
 

@@ -131,7 +131,10 @@ class BeamSearch(object):
     def _get_encode(self, sess, audio, audiolen):
         dev = self._las._device()
         with torch.no_grad():
-            a = torch.as_tensor(np.asarray(audio), dtype=torch.float32, device=dev)
+            if torch.is_tensor(audio):       # a device-resident cube (las.frontend): no host round trip
+                a = audio.to(device=dev, dtype=torch.float32).contiguous()
+            else:
+                a = torch.as_tensor(np.asarray(audio), dtype=torch.float32, device=dev)
             h, _, enc_len = self.listener(a, np.asarray(audiolen), encoder=self.args.enc_type.lower(), is_training=False)
         return h, enc_len
 
@@ -172,6 +175,8 @@ class BeamSearch(object):
                 es.wait_stream(main)         #  stream -- they are issued while the current batch's search steps are queued on it)
                 first_launch[0] = False
             with torch.cuda.stream(es):
+                if callable(xs_list):        # a deferred batch (transcribe.py: the front end's extraction): made here, on the encoders' stream
+                    xs_list = xs_list()
                 pre = self._run_encoders(sess, xs_list)
             ev = torch.cuda.Event()
             ev.record(es)
@@ -223,7 +228,9 @@ class BeamSearch(object):
         """The encoders of a batch of utterances on the CURRENT stream, without waiting for the device (the encoded lengths are host
         values): -> (encs [per utterance: [1, T'_u, Hd] views], enc_lens, dec_steps, h_one, ctc_lp).  ctc_lp: the CTC head's class-major
         log-probabilities [n, V + 1, max T'_u] when ctc_decode_weight > 0, else None.  decode_batch's first phase; decode_batches runs it
-        for the NEXT batch on a second stream under the search of the current one."""
+        for the NEXT batch on a second stream under the search of the current one.
+        An utterance's audio is a host array or a device tensor (FeatureExtractor's cube rows); device tensors are stacked and padded
+        on the device, with the values the host path would upload."""
         a = self.args
         dev = self._las._device()
         n = len(xs_list)
@@ -237,10 +244,18 @@ class BeamSearch(object):
             al = np.asarray(audiolen).reshape(-1)
             groups.setdefault((tuple(np.shape(audio)[1:]), float(al[0])), []).append(u)
             dec_steps.append(int(al[0] * a.convert_rate))                                       # las/beam_search.py:78
+        on_dev = [torch.is_tensor(x[0]) for x in xs_list]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError('the utterances of one batch are all host arrays or all device tensors')
+        on_dev = all(on_dev)
+
         def encode_group(us):
             # utterances of the SAME shape and length share one encoder launch: every row of the encoder is computed
             # independently of the other rows, so this is exactly the one-at-a-time result (unlike padding, see above)
-            audio = np.concatenate([np.asarray(xs_list[u][0]) for u in us], 0)
+            if on_dev:
+                audio = xs_list[us[0]][0] if len(us) == 1 else torch.cat([xs_list[u][0] for u in us], 0)
+            else:
+                audio = np.concatenate([np.asarray(xs_list[u][0]) for u in us], 0)
             audiolen = np.concatenate([np.asarray(xs_list[u][1]).reshape(-1)[:1] for u in us], 0)
             h, enc_len = self._get_encode(sess, audio, audiolen)
             el = torch.as_tensor(enc_len).reshape(-1).cpu().tolist()       # (one read-back, not one per utterance)
@@ -263,9 +278,14 @@ class BeamSearch(object):
             # exactly as alone); the products in between are row-wise.  Every real frame equals the one-at-a-time result.
             lens = [int(np.shape(x[0])[1]) for x in xs_list]
             Tmax = max(lens)
-            audio = np.zeros((n, Tmax) + tuple(np.shape(xs_list[0][0])[2:]), np.float32)
-            for u, x in enumerate(xs_list):
-                audio[u, :lens[u]] = np.asarray(x[0])[0]
+            if on_dev:
+                audio = torch.zeros((n, Tmax) + tuple(np.shape(xs_list[0][0])[2:]), dtype=torch.float32, device=dev)
+                for u, x in enumerate(xs_list):
+                    audio[u, :lens[u]] = x[0][0]
+            else:
+                audio = np.zeros((n, Tmax) + tuple(np.shape(xs_list[0][0])[2:]), np.float32)
+                for u, x in enumerate(xs_list):
+                    audio[u, :lens[u]] = np.asarray(x[0])[0]
             audiolen = np.concatenate([np.asarray(x[1]).reshape(-1)[:1] for x in xs_list], 0)
             L.ROW_T[0] = torch.tensor(lens, dtype=torch.int32, device=dev)
             try:

@@ -8,7 +8,9 @@ speechpy.processing.cmvn, speechpy.feature.extract_derivative_feature; unpinned 
 rectangular window, 512-point power spectrum / fft_length, 40 triangular mel filters from 300 Hz -- speechpy's
 `low_freq or 300` turns the default 0 into 300 -- log, orthonormal DCT-II, c0 replaced by log frame energy; CMVN with
 variance normalisation and eps 2^-30; derivatives over a +-2 window taken ALONG THE FEATURE AXIS exactly as speechpy's
-`derivative_extraction` pads and slides along axis 1).  Offline CPU work, not on the hot path."""
+`derivative_extraction` pads and slides along axis 1).  This file is the float64 STATEMENT of the arithmetic:
+csrc/frontend.hip evaluates the same steps on the device for a batch of utterances (las.frontend.FeatureExtractor; transcribe.py feeds
+the search from it, `--frontend gpu` writes this entry point's dumps through it) and is tested against the functions below."""
 import math
 import os
 import string
@@ -157,6 +159,27 @@ def process_audios(audio_path, args):
     return feats, featlen
 
 
+def process_audios_gpu(audio_path, args, batch=64):
+    """process_audios through the device front end: `batch` utterances per las_frontend call (files of one sample rate, which must
+    be args.sample_rate: the kernels' tables are built for it), the same lists of float32 arrays"""
+    from las.frontend import FeatureExtractor
+    fe = FeatureExtractor(args)
+    feats, featlen = [], []
+    for c0 in range(0, len(audio_path), batch):
+        waves = []
+        for p in audio_path[c0:c0 + batch]:
+            audio, fs = read_audio(p)
+            if fs != fe.fs:
+                raise ValueError("%s is sampled at %d Hz, --sample_rate is %d (no resampling)" % (p, fs, fe.fs))
+            waves.append(audio)
+        cube, lens = fe.extract(waves)
+        cube = cube.cpu().numpy()
+        for u, t in enumerate(lens):
+            feats.append(cube[u, :t].copy())
+            featlen.append(int(t))
+    return feats, featlen
+
+
 def process_texts(texts, tokenizer):
     """reference preprocess.py:93-108: strip punctuation, encode with EOS."""
     tokens, tokenlen = [], []
@@ -178,7 +201,8 @@ def data_preparation(libri_path):
         for line in open(tp[0]).readlines():
             line_ = line.split(" ")
             base = path + "/" + line_[0]
-            audio_path.append(base + (".wav" if os.path.exists(base + ".wav") else ".flac"))
+            ext = next((e for e in (".wav", ".npy") if os.path.exists(base + e)), ".flac")       # (.npy: raw 16 kHz samples, read_audio)
+            audio_path.append(base + ext)
             texts.append(line[len(line_[0]) + 1:-1].replace("'", ""))
     return texts, audio_path
 
@@ -188,13 +212,15 @@ def main():
     from las.arguments import parse_args
     from utils.tokenizer import CharEncoder, SubwordEncoder
     args = parse_args()
+    if args.frontend not in ("cpu", "gpu"):
+        raise ValueError("--frontend is cpu or gpu (got %s)" % args.frontend)
     tokenizer = CharEncoder() if args.unit.lower() == "char" else SubwordEncoder(args.subword_dir)
     os.makedirs(args.feat_dir, exist_ok=True)
     for split, path in (("train-100", args.train_100hr_corpus_dir), ("dev", args.dev_data_dir), ("test", args.test_data_dir)):
         if not os.path.isdir(path):
             continue
         texts, audio_path = data_preparation(path)
-        feats, featlen = process_audios(audio_path, args)
+        feats, featlen = (process_audios_gpu if args.frontend == "gpu" else process_audios)(audio_path, args)
         tokens, tokenlen = process_texts(texts, tokenizer)
         joblib.dump(feats, os.path.join(args.feat_dir, "%s-feats.pkl" % split))
         np.save(os.path.join(args.feat_dir, "%s-featlen.npy" % split), np.asarray(featlen))

@@ -1,0 +1,104 @@
+"""transcribe.py -- from audio to text: .wav / .npy files -> one hypothesis per line.
+
+    python transcribe.py [model / checkpoint / LM / CTC flags of decode.py] a.wav b.wav ...
+    python transcribe.py --synthetic True            (random weights, generated noise "audio": runs with no data)
+
+The files are read with preprocess.read_audio (.flac needs `soundfile`), `--decode_batch` of them at a time go through the device front
+end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip) and stay on the device for BeamSearch.decode_batches:
+the extraction and the encoders of batch k+1 run under the search of batch k.  The reference has no such entry point (its decode.py reads
+the feature dumps of preprocess.py); the model side is decode.py's."""
+import logging
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from las import layers, variables                                  # noqa: E402
+from las.arguments import build_parser                             # noqa: E402
+from las.beam_search import BeamSearch                             # noqa: E402
+from las.frontend import FeatureExtractor                          # noqa: E402
+from las.las import LAS, Listener, Speller                         # noqa: E402
+from las.utils import convert_idx_to_string                        # noqa: E402
+from preprocess import read_audio                                  # noqa: E402
+from utils.tokenizer import CharEncoder, SubwordEncoder            # noqa: E402
+
+
+def synthetic_audio(n, fs, seed):
+    """n noise "recordings" of 1-3 s (broadband, so every mel band is populated)"""
+    rng = np.random.RandomState(seed)
+    return [(0.1 * rng.randn(int(fs * rng.uniform(1.0, 3.0)))).astype(np.float32) for _ in range(n)]
+
+
+def main(argv=None):
+    import torch
+    from decode import load_lm, restore_lm
+    parser = build_parser()
+    parser.add_argument("audio", nargs="*", help=".wav / .npy files to transcribe")
+    args = parser.parse_args(argv)
+    logging.basicConfig(stream=sys.stderr, format='%(asctime)s %(levelname)s:%(message)s', level=logging.INFO, datefmt='%I:%M:%S')
+    if not args.synthetic and not args.audio:
+        parser.error("no audio files (or --synthetic True)")
+    if not args.cmvn:
+        raise ValueError("the Listener takes the CMVN'd cube [T, feat_dim, 3]: transcribe with --cmvn True")
+    tokenizer = CharEncoder() if args.unit.lower() == "char" else SubwordEncoder(args.subword_dir)
+    args.vocab_size = tokenizer.get_vocab_size()
+    id_to_token, token_to_id = tokenizer.id_to_token, tokenizer.token_to_id
+    layers.set_cell(args.cell)
+    layers.set_precision(args.dtype)
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    variables.reset_default_store(device=dev, seed=args.seed)
+    las = LAS(args, Listener, Speller, token_to_id)
+    lm = result = None
+    if args.apply_lm:
+        st = variables.default_store()
+        if args.synthetic and not os.path.exists(os.path.join(args.lm_dir, "result.json")):
+            from lang.char_rnn_model import CharRNN
+            lm = CharRNN(False, 1, 1, 28, 512, embedding_size=0, num_layers=2, store=st)
+        else:
+            lm, result = load_lm(args.lm_dir, st)
+        lm.params()
+    las.build_variables()
+    bs = BeamSearch(args, las, token_to_id, lm)
+    if not args.synthetic:
+        logging.info("LAS restored: {}".format(bs.restore_las(None, args.save_dir, args.restore_epoch)))
+        if result is not None:
+            restore_lm(lm, result['best_model'])
+    fe = FeatureExtractor(args, device=dev)
+    if args.synthetic:
+        count = args.max_steps if args.max_steps >= 0 else 8
+        waves = synthetic_audio(count, args.sample_rate, args.seed + 2)
+    else:
+        waves = None
+        count = len(args.audio)
+    nb = max(1, int(args.decode_batch))
+
+    def load(i):
+        if waves is not None:
+            return waves[i]
+        audio, fs = read_audio(args.audio[i])
+        if fs != args.sample_rate:
+            raise ValueError("%s is sampled at %d Hz, --sample_rate is %d (no resampling)" % (args.audio[i], fs, args.sample_rate))
+        if audio.ndim != 1:
+            raise ValueError("%s has %d channels: mono recordings only" % (args.audio[i], audio.shape[1]))
+        return audio
+
+    def batches():
+        for c0 in range(0, count, nb):
+            chunk = [load(i) for i in range(c0, min(c0 + nb, count))]          # (host work: file reads)
+
+            def make(chunk=chunk):
+                # called by decode_batches on the encoders' stream: one upload + three launches, the cube never leaves the device
+                cube, lens = fe.extract(chunk)
+                return [(cube[u:u + 1, :lens[u]], lens[u:u + 1]) for u in range(len(chunk))]
+            yield make
+
+    for results in bs.decode_batches(None, batches()):
+        for beam_states in results:
+            print(convert_idx_to_string(beam_states[-1].token_ids[1:], id_to_token, args.unit))
+    sys.stdout.flush()
+
+
+if __name__ == "__main__":
+    main()

@@ -726,6 +726,38 @@ int las_input_release(void* reader, int slot);
 long long las_input_records(void* reader);                       /* records parsed so far */
 void las_input_close(void* reader);
 
+/* ------------------------------------------------------------------------------------------
+ * K12  audio front end: waveform -> feature cube (preprocess.py:71-86: speechpy.feature.mfcc / mfe at :71-80,
+ * speechpy.processing.cmvn(variance_normalization=True) at :84, speechpy.feature.extract_derivative_feature at :85), for a batch
+ * of n utterances of different lengths in one call.  Arithmetic of the restatement in this build's preprocess.py:
+ *   frames    T_u = floor((n_u - fl) / step) frames of fl <= 512 samples every `step` samples, rectangular window, no padding of the
+ *             signal (the last full frame is dropped, as speechpy does)
+ *   spectrum  frame zero-padded to 512, real FFT, P[k] = |X[k]|^2 / 512 (k = 0..256); frame energy = sum_k P[k]
+ *   mel       P . fb^T in fp32 over each filter's non-zero bins; an exact 0 (filter output or energy) becomes 2^-52
+ *   mfcc      logf, orthonormal DCT-II (table dct [feat_dim, num_filters]), coefficient 0 replaced by log(energy)
+ *   fbank     the filter outputs as they are (feat_dim == num_filters; no log, as the reference)
+ *   cmvn != 0 per utterance and column: mean over its T_u frames, ddof-0 standard deviation of the mean-subtracted column (two
+ *             fixed-order passes, in double over the fp32 features), x = (x - mean) / (std + 2^-30); then derivative_extraction twice, window 2, ALONG THE FEATURE
+ *             AXIS with edge padding (the reference's quirk).  out fp32 [n, Tmax, feat_dim, 3], zeros behind T_u.
+ *   cmvn == 0 out fp32 [n, Tmax, feat_dim]: the raw features, zeros behind T_u.
+ * The tables are the caller's (built in double, rounded to fp32): twiddle [257][2] = (cos, -sin)(2 pi k / 512); fb [num_filters, 257];
+ * fb_range int32 [num_filters][2] = first and last non-zero bin of each filter (first > last: an empty filter); dct (mfcc only).
+ * samples: fp32 or int16 (samples_i16: value / 32767, what read_audio does to 16-bit files) [n, ld_samples]; n_samples int32 [n] on
+ * the device, n_samples_host the same values on the host (what the entry validates: fl <= n_u <= ld_samples, 1 <= T_u <= Tmax).
+ * No atomics: two calls on the same inputs give the same bits.  ws >= las_frontend_workspace_bytes(n, Tmax, feat_dim, cmvn).
+ */
+enum { LAS_FEAT_MFCC = 0, LAS_FEAT_FBANK = 1 };
+typedef struct las_frontend_args {
+    const void* samples; int samples_i16; long long ld_samples;
+    const int* n_samples; const int* n_samples_host;
+    int n, Tmax, fl, step, feat_type, feat_dim, num_filters, cmvn;
+    const float* twiddle; const float* fb; const int* fb_range; const float* dct;
+    float* out;
+    void* ws; size_t ws_bytes;
+} las_frontend_args;
+size_t las_frontend_workspace_bytes(int n, int Tmax, int feat_dim, int cmvn);
+int las_frontend(const las_frontend_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
