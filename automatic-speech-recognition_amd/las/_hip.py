@@ -97,6 +97,13 @@ class FrontendArgs(ctypes.Structure):
                [("twiddle", c_void_p), ("fb", c_void_p), ("fb_range", c_void_p), ("dct", c_void_p), ("out", c_void_p), ("ws", c_void_p), ("ws_bytes", c_size_t)]
 
 
+class ResampleArgs(ctypes.Structure):
+    """include/las_hip.h las_resample_args"""
+    _fields_ = [("in_", c_void_p), ("in_i16", c_int), ("ld_in", c_longlong), ("n_in", c_void_p), ("n_in_host", POINTER(c_int)),
+                ("n", c_int), ("L", c_int), ("M", c_int), ("W", c_int), ("table", c_void_p), ("gain", c_void_p), ("out", c_void_p),
+                ("ld_out", c_longlong), ("n_out", c_void_p)]
+
+
 _SIGS = {
     "las_version": (c_int, []),
     "las_rnn_seq_prepare": (c_int, [POINTER(SeqPrepareDesc), c_int, c_void_p]),
@@ -203,10 +210,13 @@ _SIGS = {
     "las_input_close": (None, [c_void_p]),
     "las_frontend_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "las_frontend": (c_int, [POINTER(FrontendArgs), c_void_p]),
+    "las_resample_out_len": (c_longlong, [c_longlong, c_int, c_int]),
+    "las_resample_tile": (c_int, [c_int, c_int, c_int]),
+    "las_resample": (c_int, [POINTER(ResampleArgs), c_void_p]),
 }
 
 
-ABI_VERSION = 600      # include/las_hip.h LAS_HIP_ABI_VERSION
+ABI_VERSION = 601      # include/las_hip.h LAS_HIP_ABI_VERSION
 
 
 def declared_symbols():

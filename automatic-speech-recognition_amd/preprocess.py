@@ -140,11 +140,66 @@ def read_audio(path):
     return sf.read(path)
 
 
-def process_audios(audio_path, args):
-    """reference preprocess.py:50-91.  Returns (feats: list of float32 [L, feat_dim, 3] (or [L, feat_dim] without --cmvn), featlen)."""
+RESAMPLE_ROLLOFF, RESAMPLE_ZEROS, RESAMPLE_BETA = 0.92, 24, 10.0
+SPEEDS = (0.9, 1.1)                                              # reference preprocess.py:160
+
+
+def resample_table(fs_in, fs_out):
+    """The band-limited resampler's polyphase table (float64): (L, M, W, h [L, 2W]).  fs_out / fs_in = L / M in lowest terms; the
+    filter is a sinc cut at c = 0.92 x the narrower band's Nyquist under a Kaiser window (beta 10) of 24 zero crossings a side, i.e.
+    W = ceil(24 / c) input samples.  Row p holds the 2W taps of an output that falls p / L of a sample behind input sample n0: tap i
+    weighs x[n0 - W + 1 + i], at distance d = p / L + (W - 1) - i.  Every row is divided by its sum (a constant stays constant)."""
+    fs_in, fs_out = int(fs_in), int(fs_out)
+    if fs_in < 1 or fs_out < 1:
+        raise ValueError("sample rates are positive (got %d -> %d)" % (fs_in, fs_out))
+    g = math.gcd(fs_in, fs_out)
+    L, M = fs_out // g, fs_in // g
+    c = RESAMPLE_ROLLOFF * min(1.0, L / M)
+    W = int(math.ceil(RESAMPLE_ZEROS / c))
+    d = np.arange(L, dtype=float)[:, None] / L + (W - 1) - np.arange(2 * W, dtype=float)[None, :]
+    u = d * c / RESAMPLE_ZEROS
+    inside = np.abs(u) < 1
+    kaiser = np.where(inside, np.i0(RESAMPLE_BETA * np.sqrt(np.where(inside, 1 - u * u, 0.0))) / np.i0(RESAMPLE_BETA), 0.0)
+    h = c * np.sinc(c * d) * kaiser
+    return L, M, W, h / h.sum(1, keepdims=True)
+
+
+def resample_out_len(n, L, M):
+    return (int(n) * L + M - 1) // M                             # ceil(n L / M), in integers
+
+
+def resample(x, fs_in, fs_out, gain=1.0):
+    """x (1-D, float64) from fs_in to fs_out: ceil(n L / M) samples, y[m] = gain * sum_i x[n0 - W + 1 + i] h[p, i] with
+    n0 = (m M) // L, p = (m M) % L and x zero outside the recording.  Equal rates: gain * x, unfiltered."""
+    x = np.asarray(x, dtype=float)
+    if x.ndim != 1:
+        raise ValueError("a waveform is a 1-D array (got shape %s)" % (x.shape,))
+    if int(fs_in) == int(fs_out):
+        return gain * x
+    L, M, W, h = resample_table(fs_in, fs_out)
+    n_out = resample_out_len(len(x), L, M)
+    xp = np.concatenate([np.zeros(W - 1), x, np.zeros(W + 1)])    # xp[k] = x[k - W + 1]
+    y = np.empty(n_out)
+    taps = np.arange(2 * W, dtype=np.int64)[None, :]
+    for m0 in range(0, n_out, 8192):                             # (blocks: the gathered [outputs, taps] matrix stays small)
+        mM = np.arange(m0, min(m0 + 8192, n_out), dtype=np.int64) * M
+        y[m0:m0 + len(mM)] = np.sum(xp[(mM // L)[:, None] + taps] * h[mM % L], axis=1)
+    return gain * y
+
+
+def speed_perturb(x, fs, speed, gain=1.0):
+    """sox's `speed s`: the recording declared to be at fs * s Hz, resampled back to fs (0.9 at 16 kHz: 14400 -> 16000)"""
+    return resample(x, int(round(fs * speed)), fs, gain)
+
+
+def process_audios(audio_path, args, speed=1.0):
+    """reference preprocess.py:50-91.  Returns (feats: list of float32 [L, feat_dim, 3] (or [L, feat_dim] without --cmvn), featlen).
+    speed != 1: every recording through speed_perturb first (the reference's speed augmentation, without the audio files between)."""
     feats, featlen = [], []
     for p in audio_path:
         audio, fs = read_audio(p)
+        if speed != 1.0:
+            audio = speed_perturb(audio, fs, speed)
         if args.feat_type == 'mfcc':
             feat = mfcc(audio, fs, frame_length=args.frame_length / 1000, frame_stride=args.frame_step / 1000, num_cepstral=args.feat_dim)
         elif args.feat_type == 'fbank':
@@ -159,20 +214,20 @@ def process_audios(audio_path, args):
     return feats, featlen
 
 
-def process_audios_gpu(audio_path, args, batch=64):
-    """process_audios through the device front end: `batch` utterances per las_frontend call (files of one sample rate, which must
-    be args.sample_rate: the kernels' tables are built for it), the same lists of float32 arrays"""
+def process_audios_gpu(audio_path, args, batch=64, speed=1.0):
+    """process_audios through the device front end: `batch` utterances per las_frontend call, the same lists of float32 arrays.  The
+    kernels' tables are built for args.sample_rate: a file at another rate is resampled to it on the device (las_resample), and so is
+    every file when speed != 1 (speed_perturb's arithmetic in fp32)"""
     from las.frontend import FeatureExtractor
     fe = FeatureExtractor(args)
     feats, featlen = [], []
     for c0 in range(0, len(audio_path), batch):
-        waves = []
+        waves, rates = [], []
         for p in audio_path[c0:c0 + batch]:
             audio, fs = read_audio(p)
-            if fs != fe.fs:
-                raise ValueError("%s is sampled at %d Hz, --sample_rate is %d (no resampling)" % (p, fs, fe.fs))
             waves.append(audio)
-        cube, lens = fe.extract(waves)
+            rates.append(int(fs))
+        cube, lens = fe.extract(waves, rate=rates, speed=speed)
         cube = cube.cpu().numpy()
         for u, t in enumerate(lens):
             feats.append(cube[u, :t].copy())
@@ -220,13 +275,20 @@ def main():
         if not os.path.isdir(path):
             continue
         texts, audio_path = data_preparation(path)
-        feats, featlen = (process_audios_gpu if args.frontend == "gpu" else process_audios)(audio_path, args)
+        process = process_audios_gpu if args.frontend == "gpu" else process_audios
+        feats, featlen = process(audio_path, args)
         tokens, tokenlen = process_texts(texts, tokenizer)
         joblib.dump(feats, os.path.join(args.feat_dir, "%s-feats.pkl" % split))
         np.save(os.path.join(args.feat_dir, "%s-featlen.npy" % split), np.asarray(featlen))
         np.save(os.path.join(args.feat_dir, "%s-%ss.npy" % (split, args.unit)), np.asarray(tokens, dtype=object), allow_pickle=True)
         np.save(os.path.join(args.feat_dir, "%s-%slen.npy" % (split, args.unit)), tokenlen)
         print("%s: %d utterances -> %s" % (split, len(feats), args.feat_dir))
+        if args.augmentation and "train" in split:               # reference preprocess.py:157-167, straight from the recordings
+            for s in SPEEDS:
+                feats, featlen = process(audio_path, args, speed=s)
+                joblib.dump(feats, os.path.join(args.feat_dir, "speed_%s-feats.pkl" % s))
+                np.save(os.path.join(args.feat_dir, "speed_%s-featlen.npy" % s), np.asarray(featlen))
+                print("speed_%s: %d utterances -> %s" % (s, len(feats), args.feat_dir))
 
 
 if __name__ == "__main__":

@@ -2,9 +2,11 @@
 
     python transcribe.py [model / checkpoint / LM / CTC flags of decode.py] a.wav b.wav ...
     python transcribe.py --synthetic True            (random weights, generated noise "audio": runs with no data)
+    python transcribe.py --synthetic True a.wav ...  (random weights on the given files: the audio path without a checkpoint)
 
 The files are read with preprocess.read_audio (.flac needs `soundfile`), `--decode_batch` of them at a time go through the device front
-end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip) and stay on the device for BeamSearch.decode_batches:
+end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip; a file at another rate than --sample_rate is resampled
+on the device first, csrc/resample.hip) and stay on the device for BeamSearch.decode_batches:
 the extraction and the encoders of batch k+1 run under the search of batch k.  The reference has no such entry point (its decode.py reads
 the feature dumps of preprocess.py); the model side is decode.py's."""
 import logging
@@ -66,7 +68,7 @@ def main(argv=None):
         if result is not None:
             restore_lm(lm, result['best_model'])
     fe = FeatureExtractor(args, device=dev)
-    if args.synthetic:
+    if args.synthetic and not args.audio:
         count = args.max_steps if args.max_steps >= 0 else 8
         waves = synthetic_audio(count, args.sample_rate, args.seed + 2)
     else:
@@ -76,21 +78,20 @@ def main(argv=None):
 
     def load(i):
         if waves is not None:
-            return waves[i]
+            return waves[i], args.sample_rate
         audio, fs = read_audio(args.audio[i])
-        if fs != args.sample_rate:
-            raise ValueError("%s is sampled at %d Hz, --sample_rate is %d (no resampling)" % (args.audio[i], fs, args.sample_rate))
         if audio.ndim != 1:
             raise ValueError("%s has %d channels: mono recordings only" % (args.audio[i], audio.shape[1]))
-        return audio
+        return audio, int(fs)
 
     def batches():
         for c0 in range(0, count, nb):
             chunk = [load(i) for i in range(c0, min(c0 + nb, count))]          # (host work: file reads)
 
             def make(chunk=chunk):
-                # called by decode_batches on the encoders' stream: one upload + three launches, the cube never leaves the device
-                cube, lens = fe.extract(chunk)
+                # called by decode_batches on the encoders' stream: one upload + three launches (one more per sample rate that is not
+                # --sample_rate), the cube never leaves the device
+                cube, lens = fe.extract([w for w, _ in chunk], rate=[fs for _, fs in chunk])
                 return [(cube[u:u + 1, :lens[u]], lens[u:u + 1]) for u in range(len(chunk))]
             yield make
 

@@ -37,7 +37,7 @@ enum { LAS_ACT_NONE = 0, LAS_ACT_TANH = 1 };
 enum { LAS_ATT_ADD = 0, LAS_ATT_LOC = 1 };      /* las/las.py:44-49 */
 enum { LAS_DT_F32 = 0, LAS_DT_BF16 = 1 };       /* element type of a tensor in HBM (see las_gemm_kk) */
 
-#define LAS_HIP_ABI_VERSION 600      /* bumped whenever an argument struct or a signature changes: las_version() of a library
+#define LAS_HIP_ABI_VERSION 601      /* bumped whenever an argument struct or a signature changes: las_version() of a library
                                         built from another header differs, and the Python loader refuses it */
 int         las_version(void);
 const char* las_last_error(void);
@@ -757,6 +757,33 @@ typedef struct las_frontend_args {
 } las_frontend_args;
 size_t las_frontend_workspace_bytes(int n, int Tmax, int feat_dim, int cmvn);
 int las_frontend(const las_frontend_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K13  band-limited resampler in front of las_frontend: a batch of n waveforms from one sample rate to another (fs_out / fs_in =
+ * L / M in lowest terms), with a per-utterance gain in the same pass.  sox's `speed s` is this with fs_in = fs * s (the reference's
+ * augmentation, preprocess.py:157-167 through utils/augmentation.py).  The arithmetic is preprocess.resample's, in fp32:
+ *   n_out[u] = ceil(n_in[u] * L / M);  output m reads n0 = (m M) / L, phase p = (m M) % L (64-bit products) and is
+ *   out[u, m] = gain[u] * sum_{i = 0 .. 2W-1} x[u, n0 - W + 1 + i] * table[p, i],  x zero outside [0, n_in[u]),
+ *   ONE fmaf chain over the taps in ascending order: a row gives the bits it gives alone, and the same bits on every run.
+ * table [L, 2W] is the caller's (preprocess.resample_table in double, rounded to fp32), 8-byte aligned.  L == M == 1 is the gain-only path
+ * out = gain * in (one rounding; with gain NULL a bit copy of fp32 input; table may be NULL).
+ * One launch on `stream`, no atomics, no synchronisation.  Every element of out [n, ld_out] is written, zeros behind n_out[u].
+ * The entry validates on the host before it launches: 1 <= n <= 65535, 1 <= L, M <= 2^20, 1 <= W, 2W <= 1024, L * 2W <= 2^20,
+ * a workgroup's input span (tile - 1) M / L + 1 + 2W fits its staging buffer (las_resample_tile > 0),
+ * 1 <= n_in_host[u] <= ld_in, las_resample_out_len(n_in_host[u], L, M) <= ld_out <= INT32_MAX.
+ */
+typedef struct las_resample_args {
+    const void* in; int in_i16; long long ld_in;      /* [n, ld_in] fp32 or int16 (value / 32767, as las_frontend) */
+    const int* n_in; const int* n_in_host;            /* samples per row, device and host copies */
+    int n, L, M, W;                                   /* K = 2W taps */
+    const float* table;                               /* [L, 2W] fp32, device, 8-byte aligned */
+    const float* gain;                                /* [n] fp32 on the device, or NULL = 1 */
+    float* out; long long ld_out;                     /* [n, ld_out] fp32; every element written, zeros behind n_out[u] */
+    int* n_out;                                       /* [n] int32 on the device, or NULL */
+} las_resample_args;
+long long las_resample_out_len(long long n_in, int L, int M);     /* ceil(n_in * L / M); < 0 for bad arguments */
+int las_resample_tile(int L, int M, int W);           /* consecutive outputs of one utterance a workgroup owns; <= 0: ratio refused */
+int las_resample(const las_resample_args* args, void* stream);
 
 #ifdef __cplusplus
 }
