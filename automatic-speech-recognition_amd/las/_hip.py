@@ -104,6 +104,12 @@ class ResampleArgs(ctypes.Structure):
                 ("ld_out", c_longlong), ("n_out", c_void_p)]
 
 
+class SpecAugArgs(ctypes.Structure):
+    """include/las_hip.h las_specaug_args"""
+    _fields_ = [("in_", c_void_p), ("out", c_void_p), ("plan", c_void_p), ("plan_host", POINTER(c_int)), ("ldp", c_int)] + \
+               [(n, c_int) for n in ("B", "Tmax", "F", "C", "mF", "mT")]
+
+
 _SIGS = {
     "las_version": (c_int, []),
     "las_rnn_seq_prepare": (c_int, [POINTER(SeqPrepareDesc), c_int, c_void_p]),
@@ -213,10 +219,12 @@ _SIGS = {
     "las_resample_out_len": (c_longlong, [c_longlong, c_int, c_int]),
     "las_resample_tile": (c_int, [c_int, c_int, c_int]),
     "las_resample": (c_int, [POINTER(ResampleArgs), c_void_p]),
+    "las_specaug_tile": (c_int, []),
+    "las_specaug": (c_int, [POINTER(SpecAugArgs), c_void_p]),
 }
 
 
-ABI_VERSION = 601      # include/las_hip.h LAS_HIP_ABI_VERSION
+ABI_VERSION = 602      # include/las_hip.h LAS_HIP_ABI_VERSION
 
 
 def declared_symbols():

@@ -96,6 +96,14 @@ _EXTRA = [
     (("--lm_dir",), str, "lang/output/", "Output directory of train_lm.py (result.json, vocab.json, models) for --apply_lm."),
     (("--frontend",), str, "cpu", "Feature extraction of preprocess.py: cpu = the float64 numpy restatement, gpu = the HIP front end "
                                   "(las.frontend.FeatureExtractor, fp32)."),
+    # SpecAugment in training (las.specaug, csrc/specaug.hip): off by default
+    (("--spec_augment",), str2bool, False, "Warp and mask the feature cube of every train step on the device (SpecAugment)."),
+    (("--specaug_time_warp",), int, 80, "SpecAugment: maximum time warp distance W in frames (0: no warp)."),
+    (("--specaug_freq_masks",), int, 2, "SpecAugment: number of frequency masks."),
+    (("--specaug_freq_width",), int, -1, "SpecAugment: maximum frequency mask width in bins (-1: max(1, feat_dim // 3), the paper's 27 of 80)."),
+    (("--specaug_time_masks",), int, 2, "SpecAugment: number of time masks."),
+    (("--specaug_time_width",), int, 100, "SpecAugment: maximum time mask width in frames."),
+    (("--specaug_time_ratio",), float, 1.0, "SpecAugment: a time mask covers at most this share of the utterance's frames."),
 ]
 
 

@@ -639,6 +639,7 @@ class LAS:
         self._warned_recover = False
         self.recovered_steps = 0  # steps re-run after a time-out status (tests / logs)
         self.last_out = None      # what the newest train step returned -- of its RE-RUN when the step was lost and recovered
+        self.specaug = None       # las.specaug.SpecAugment, built by the first train step under --spec_augment True
 
     # -- helpers -----------------------------------------------------------------------------------
     @staticmethod
@@ -851,6 +852,17 @@ class LAS:
             # the Speller's host-side preparation: token schedule, encoder lengths, masks
             prep = self.speller.prepare(audio.shape[0], self.listener.output_length(audiolen, enc_type), dec_steps, dev, y,
                                         True, coins, sampled)
+        if getattr(self.args, "spec_augment", False):
+            # SpecAugment on the launch stream in front of the Listener.  The plan is drawn from (seed, global step) alone and `_recent`
+            # holds the RAW batch, so a re-run of this step warps and masks as this run does.  Data parallel: rank r holds rows
+            # [r B, (r + 1) B) of the global batch (equal shards), the rows train_stacked gives shard r of the concatenation
+            if self.specaug is None:
+                from las.specaug import SpecAugment
+                self.specaug = SpecAugment(self.args)
+            rank, world = (self.dp.rank, self.dp.world) if self.dp is not None else (0, 1)
+            with _hip.roctx_range("specaug"):
+                audio = self.specaug(audio.contiguous(), audiolen, step=st.global_step, row0=rank * audio.shape[0],
+                                     rows_global=world * audio.shape[0])
         with _hip.roctx_range("listener fwd"):
             h, enc_state, enc_len = self.listener(audio, audiolen, enc_type)              # is_training default True
         _hip.join_chain_stream()

@@ -37,7 +37,7 @@ enum { LAS_ACT_NONE = 0, LAS_ACT_TANH = 1 };
 enum { LAS_ATT_ADD = 0, LAS_ATT_LOC = 1 };      /* las/las.py:44-49 */
 enum { LAS_DT_F32 = 0, LAS_DT_BF16 = 1 };       /* element type of a tensor in HBM (see las_gemm_kk) */
 
-#define LAS_HIP_ABI_VERSION 601      /* bumped whenever an argument struct or a signature changes: las_version() of a library
+#define LAS_HIP_ABI_VERSION 602      /* bumped whenever an argument struct or a signature changes: las_version() of a library
                                         built from another header differs, and the Python loader refuses it */
 int         las_version(void);
 const char* las_last_error(void);
@@ -784,6 +784,32 @@ typedef struct las_resample_args {
 long long las_resample_out_len(long long n_in, int L, int M);     /* ceil(n_in * L / M); < 0 for bad arguments */
 int las_resample_tile(int L, int M, int W);           /* consecutive outputs of one utterance a workgroup owns; <= 0: ratio refused */
 int las_resample(const las_resample_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K14  SpecAugment (Park et al., 2019) on the feature cube in front of the Listener: one piecewise-linear time warp, mF frequency
+ * masks and mT time masks per utterance.  The entry APPLIES a plan and draws nothing (las/specaug.py draws on the host).
+ *   in, out  fp32 [B, Tmax, F, C], contiguous, 4-byte aligned; they must not overlap (refused on the host).
+ *   plan     int32 [B, ldp] on the device, plan_host the same values on the host (what the entry validates); ldp a multiple of 4,
+ *            >= 4 + 2 (mF + mT).  Row b = {len, w0, w, 0, (f0, fw) x mF, (t0, tw) x mT}.
+ * Time warp (w == 0: none): output frames [0, w0 + w] read source [0, w0], output frames [w0 + w, len - 1] read source [w0, len - 1].
+ * The source position of output frame t is an exact rational in 32-bit integers: on the left i0 = (t w0) / (w0 + w), r = (t w0) %
+ * (w0 + w); on the right i0 = w0 + ((t - w0 - w) (len - 1 - w0)) / (len - 1 - w0 - w), r the remainder.  frac = r / den is ONE fp32
+ * division and the value is fmaf(frac, x[i0 + 1] - x[i0], x[i0]); with r == 0 it is a bit copy of x[i0] and x[i0 + 1] is not read (so a
+ * row with w == 0 is a bit copy).  Masked elements -- frames [t0, t0 + tw) of a time mask, bins [f0, f0 + fw) of a frequency mask in
+ * every channel, frames t >= len -- are +0.0f by a select: the source is not read there, a NaN underneath does not survive.
+ * Zero-width masks do nothing.  One launch on `stream`, no atomics, no synchronisation; every element of out is written; a row gives
+ * the bits it gives alone, whatever the tile (las_specaug_tile frames per workgroup) and the batch.
+ * Validated on the host before the launch: 1 <= B <= 65535, 1 <= Tmax <= 32768, F, C >= 1, Tmax F C <= INT32_MAX, mF, mT <= 16, ldp;
+ * per row 0 <= len <= Tmax; w == 0 or both segments non-empty (1 <= w0, 1 <= w0 + w, w0 + w <= len - 2, w0 <= len - 2); masks inside
+ * [0, F] and [0, len].
+ */
+typedef struct las_specaug_args {
+    const float* in; float* out;                      /* [B, Tmax, F, C] fp32 */
+    const int* plan; const int* plan_host; int ldp;   /* [B, ldp] int32, device and host copies */
+    int B, Tmax, F, C, mF, mT;
+} las_specaug_args;
+int las_specaug_tile(void);                           /* consecutive frames of one utterance a workgroup owns */
+int las_specaug(const las_specaug_args* args, void* stream);
 
 #ifdef __cplusplus
 }
