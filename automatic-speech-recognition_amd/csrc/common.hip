@@ -118,7 +118,7 @@ extern "C" int las_occupy(const int* stop, int* resident, int n, int lds, int vg
 }
 
 // Stream-ordered wait until EVERY one of n device words has reached `need` (the progress words of a BPTT sweep that publishes how far its
-// d(pre-activation) has reached memory: las_rnn_seq_bwd_db_progress).  A CORRECTNESS dependency, unlike las_wait_announce: work enqueued
+// d(pre-activation) has reached memory: las_rnn_seq_args' progress).  A CORRECTNESS dependency, unlike las_wait_announce: work enqueued
 // behind it reads what the words vouch for, so a time-out (max_us on the 100 MHz clock) stores `code` into status[0] -- the step is then
 // invalid and las_clip_adam skips it.
 __global__ __launch_bounds__(256) void wait_words_min_kernel(const int* words, int n, int need, long long max_ticks, int* status, int code) {

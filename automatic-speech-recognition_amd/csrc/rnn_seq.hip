@@ -523,7 +523,7 @@ __device__ __forceinline__ void l2_warmer(const WarmSeg (&seg)[NSEG], int rows, 
         if (xflag) {       // chunked x-projection: a line must never be touched before the chunk that writes it is complete (a stale
                            // copy in this XCD's L2 would be what the cluster reads later)
             int have = __hip_atomic_load(xflag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-            if (have < 1) have = 1;                // chunk 0 is complete by stream order (las_rnn_seq_fwd_chunked's precondition)
+            if (have < 1) have = 1;                // chunk 0 is complete by stream order (x_chunk_flag's precondition)
             const int th = (T + 1) / 2;
             if (have * xsc < th && to > have * xsc - 1) to = have * xsc - 1;      // (second half: every chunk is complete by then)
         }
@@ -1151,7 +1151,7 @@ struct KsCfg {
 // CH: dout arrives in chunks (a.dflag): a separate instantiation -- the kernel sits at the register limit and the plain one must not change
 // PG (round 5, with CH): the sweep PUBLISHES its progress -- every a.pstep steps each member waits for its own dZ stores, writes the XCD's
 // dirty L2 lines back (one agent-scope release) and stores the step count into a.prog -- so that the layer's weight gradients can follow the sweep window
-// by window on another stream (las_rnn_seq_bwd_db_progress) instead of starting when it ends.  A separate instantiation, like CH.
+// by window on another stream (las_rnn_seq_args' progress) instead of starting when it ends.  A separate instantiation, like CH.
 template <int CELL, int UT, int P, int RB, bool CH = false, bool PG = false>
 __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
     static_assert(RB == 16 || RB == 8, "row tile");
@@ -1232,7 +1232,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
         for (int rr = 0; rr < 2; ++rr) { dcc[j][rr][0] = 0.f; dcc[j][rr][1] = 0.f; }
     }
     constexpr int NG = CELL == LAS_CELL_LSTM ? 4 : 1;
-    // chunked dout (las_rnn_seq_bwd_db_chunked): the frame of step st may be read once the chunk of its producer row is complete
+    // chunked dout (las_rnn_seq_args' dout_chunk_flag): the frame of step st may be read once the chunk of its producer row is complete
     int dhave = 1;                           // chunk 0: produced in front of this launch in stream order (no flag launch on the chain)
     auto wait_dout = [&](int st) __attribute__((always_inline)) {
         if constexpr (!CH) return;
@@ -1657,7 +1657,7 @@ static int set_lds(K kern, int bytes) {
 // How a sweep runs (plan_sweep).  The 8-row kernels compact duplicated MFMA rows; of the sweep's modes, the helper-wave kernels alone
 // wait for x-projection chunks, FWD_HW8_RAGGED alone honours row_T, BWD_KS8_CH / _CH_PG alone wait for dout chunks (and publish progress).
 enum SweepPath { SWEEP_BF16, SWEEP_MF32, SWEEP_VALU };       // clustered bf16 MFMA / clustered exact-fp32 MFMA (rnn_seq_f32.hip) / round-1 VALU
-// (the values are public: las_rnn_seq_plan_kernel returns them, include/las_hip.h LAS_SWEEP_*)
+// (the values are public: las_rnn_seq_plan returns them, include/las_hip.h LAS_SWEEP_*)
 enum SweepKernel { SWEEP_NONE = LAS_SWEEP_NONE, FWD_PLAIN = LAS_SWEEP_FWD_PLAIN, FWD_HW16 = LAS_SWEEP_FWD_HW16, FWD_HW8 = LAS_SWEEP_FWD_HW8,
                    FWD_HW8_RAGGED = LAS_SWEEP_FWD_HW8_RAGGED, BWD_PLAIN = LAS_SWEEP_BWD_PLAIN, BWD_KS16 = LAS_SWEEP_BWD_KS16, BWD_KS8 = LAS_SWEEP_BWD_KS8,
                    BWD_KS8_CH = LAS_SWEEP_BWD_KS8_CH, BWD_KS8_CH_PG = LAS_SWEEP_BWD_KS8_CH_PG };
@@ -1673,10 +1673,10 @@ struct SweepPlan {
     int pack;                // PACK_*
     bool warm;               // warmer workgroups, in every launch that leaves room for them
     int max_tiles;           // row tiles per launch (a larger batch is swept in row chunks)
-    bool x_chunks;           // las_rnn_seq_fwd_chunks_ok
-    bool rows;               // las_rnn_seq_fwd_rows_ok
-    bool dout_chunks;        // las_rnn_seq_bwd_chunks_ok
-    int progress_words;      // las_rnn_seq_bwd_progress_words
+    bool x_chunks;           // what the planned kernel serves (las_rnn_seq_plan_info): x-projection chunks,
+    bool rows;               // rows of different lengths,
+    bool dout_chunks;        // chunks of dout,
+    int progress_words;      // progress words (their number)
 };
 
 // One launch of KERN with LDS bytes of dynamic LDS.  KERN is a template argument so that the attribute is set once per kernel (every
@@ -1798,30 +1798,26 @@ static SweepPlan plan_sweep(int cell, int prec, int B, int H, int flags, bool bw
     return p;
 }
 
-extern "C" int las_rnn_seq_fwd_chunks_ok(int cell, int prec, int B, int H, int flags) { return plan_sweep(cell, prec, B, H, flags, false).x_chunks; }
-extern "C" int las_rnn_seq_fwd_rows_ok(int cell, int prec, int B, int H, int flags) { return plan_sweep(cell, prec, B, H, flags, false).rows; }
-extern "C" int las_rnn_seq_bwd_chunks_ok(int cell, int prec, int B, int H, int flags) { return plan_sweep(cell, prec, B, H, flags, true).dout_chunks; }
-extern "C" int las_rnn_seq_bwd_progress_words(int cell, int prec, int B, int H, int flags) {
-    return plan_sweep(cell, prec, B, H, flags, true).progress_words;
-}
-extern "C" int las_rnn_seq_plan_kernel(int cell, int prec, int B, int H, int flags, int bwd, int mode, int* P, int* rows_per_tile, int* launches) {
+extern "C" int las_rnn_seq_plan(int cell, int prec, int B, int H, int flags, int bwd, int mode, las_rnn_seq_plan_info* out) {
+    LAS_ARG(out, "las_rnn_seq_plan: null out");
     const SweepPlan p = plan_sweep(cell, prec, B, H, flags, bwd != 0, mode);
-    const bool none = p.path != SWEEP_BF16 || !p.inst || B <= 0;
-    if (P) *P = none ? 0 : p.P;
-    if (rows_per_tile) *rows_per_tile = none ? 0 : p.rb;
-    if (launches) *launches = none ? 0 : cdiv(cdiv(B, p.rb), p.max_tiles);      // run_bf16's row chunks
-    return none ? SWEEP_NONE : p.kernel;
+    *out = las_rnn_seq_plan_info{};
+    if (p.path == SWEEP_BF16 && p.inst && B > 0) {
+        out->kernel = p.kernel; out->P = p.P; out->rows_per_tile = p.rb;
+        out->launches = cdiv(cdiv(B, p.rb), p.max_tiles);      // run_bf16's row chunks
+    }
+    out->x_chunks = p.x_chunks; out->rows = p.rows; out->dout_chunks = p.dout_chunks; out->progress_words = p.progress_words;
+    return 0;
 }
 
-static int check_common(const char* who, int cell, int prec, int B, int T, int H, const void* gates, const void* w0,
-                        const void* w1, int ldw, const void* out, int ld_out, const void* cstate) {
-    LAS_ARG(cell == LAS_CELL_RNN || cell == LAS_CELL_LSTM, "%s: bad cell %d", who, cell);
-    LAS_ARG(prec == LAS_PREC_F32 || prec == LAS_PREC_BF16, "%s: bad prec %d", who, prec);
-    LAS_ARG(B > 0 && T > 0 && H > 0 && H <= 256 * F32_UPT, "%s: bad dims B=%d T=%d H=%d", who, B, T, H);
-    const int G = cell == LAS_CELL_LSTM ? 4 : 1;
-    LAS_ARG(gates && w0 && w1 && out, "%s: null pointer", who);
-    LAS_ARG(ldw >= G * H && ld_out >= 2 * H, "%s: leading dimension too small", who);
-    LAS_ARG(cell == LAS_CELL_RNN || cstate, "%s: lstm needs cstate", who);
+static int check_common(const char* who, const las_rnn_seq_args& s) {
+    LAS_ARG(s.cell == LAS_CELL_RNN || s.cell == LAS_CELL_LSTM, "%s: bad cell %d", who, s.cell);
+    LAS_ARG(s.prec == LAS_PREC_F32 || s.prec == LAS_PREC_BF16, "%s: bad prec %d", who, s.prec);
+    LAS_ARG(s.B > 0 && s.T > 0 && s.H > 0 && s.H <= 256 * F32_UPT, "%s: bad dims B=%d T=%d H=%d", who, s.B, s.T, s.H);
+    const int G = s.cell == LAS_CELL_LSTM ? 4 : 1;
+    LAS_ARG(s.gates && s.whh_fw && s.whh_bw && s.out, "%s: null pointer", who);
+    LAS_ARG(s.ldw >= G * s.H && s.ld_out >= 2 * s.H, "%s: leading dimension too small", who);
+    LAS_ARG(s.cell == LAS_CELL_RNN || s.cstate, "%s: lstm needs cstate", who);
     return 0;
 }
 
@@ -1918,176 +1914,108 @@ extern "C" int las_rnn_seq_prepare(const las_seq_prepare_desc* descs, int n, voi
     return 0;
 }
 
-static void seq_common_args(RnnArgs& a, int flags, int* status, int code) {
-    a.row_T = nullptr;
-    a.dbg = nullptr; a.xbuf = nullptr; a.xcc = nullptr; a.bpart = nullptr; a.force_agent = 0; a.err = nullptr; a.sink = nullptr;
-    a.ncl = a.ncl_pad = 0; a.ks_packed = 0; a.no_helpers = 0; a.rb = 16;
-    a.warm = (flags & LAS_SEQ_NO_WARMERS) ? 0 : 1;
-    a.xflag = nullptr; a.xsc = 0; a.dflag = nullptr; a.dcp = 0; a.dTq = 0; a.dshift = 0; a.prog = nullptr; a.pstep = 0;
-    const int lg = (flags >> 16) & 0x1f;                    // LAS_SEQ_SPIN_LOG2(n): bound of the exchange spins = 2^n polls
-    a.spin = lg ? (1 << lg) : LAS_SPIN_BUDGET_DEFAULT;
-    a.status = status; a.status_code = code;
-    a.announce = (flags >> 21) & 0x3ff;
-}
-
 extern "C" int las_rnn_seq_io_dtype(int cell, int prec, int H) {
     (void)cell;
     return (prec == LAS_PREC_BF16 && mfma_shape_ok(H)) ? LAS_DT_BF16 : LAS_DT_F32;
 }
 
-static void bind_tensors(RnnArgs& a, void* gates, void* out, void* cstate, const void* dout) {
-    a.gates = (float*)gates; a.out = (float*)out; a.cstate = (float*)cstate; a.dout = (const float*)dout;
-    a.gates16 = (unsigned short*)gates; a.out16 = (unsigned short*)out; a.cstate16 = (unsigned short*)cstate;
-    a.dout16 = (const unsigned short*)dout; a.sink16 = nullptr;
-}
-
-extern "C" int las_rnn_seq_fwd(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                               const float* whh_bw, int ldw, void* out, int ld_out, long long out_bstride,
-                               void* cstate, float forget_bias, int flags, int* status, void* ws, size_t ws_bytes, void* stream) {
-    return las_rnn_seq_fwd_chunked(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate, forget_bias, flags,
-                                   status, nullptr, 0, ws, ws_bytes, stream);
-}
-
-static int rnn_seq_fwd_impl(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                            const float* whh_bw, int ldw, void* out, int ld_out, long long out_bstride,
-                            void* cstate, float forget_bias, int flags, int* status, const int* chunk_flag, int chunk_steps,
-                            const int* row_T, void* ws, size_t ws_bytes, void* stream);
-extern "C" int las_rnn_seq_fwd_chunked(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                                       const float* whh_bw, int ldw, void* out, int ld_out, long long out_bstride,
-                                       void* cstate, float forget_bias, int flags, int* status, const int* chunk_flag, int chunk_steps,
-                                       void* ws, size_t ws_bytes, void* stream) {
-    return rnn_seq_fwd_impl(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate, forget_bias, flags, status,
-                            chunk_flag, chunk_steps, nullptr, ws, ws_bytes, stream);
-}
-extern "C" int las_rnn_seq_fwd_rows(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                                    const float* whh_bw, int ldw, void* out, int ld_out, long long out_bstride,
-                                    void* cstate, float forget_bias, int flags, int* status, const int* row_T,
-                                    void* ws, size_t ws_bytes, void* stream) {
-    LAS_ARG(row_T, "las_rnn_seq_fwd_rows: null row_T");
-    return rnn_seq_fwd_impl(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate, forget_bias, flags, status,
-                            nullptr, 0, row_T, ws, ws_bytes, stream);
-}
-static int rnn_seq_fwd_impl(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                            const float* whh_bw, int ldw, void* out, int ld_out, long long out_bstride,
-                            void* cstate, float forget_bias, int flags, int* status, const int* chunk_flag, int chunk_steps,
-                            const int* row_T, void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = check_common("las_rnn_seq_fwd", cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, cstate)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    RnnArgs a;
-    a.B = B; a.T = T; a.H = H; a.whh[0] = whh_fw; a.whh[1] = whh_bw; a.ldw = ldw;
-    a.ld_out = ld_out; a.obs = out_bstride;
-    bind_tensors(a, gates, out, cstate, nullptr);
-    a.ld_dout = 0; a.dobs = 0; a.fb = forget_bias; a.wpack = ws;
-    seq_common_args(a, flags, status, LAS_SEQ_STATUS_FWD_TIMEOUT);
-    const SweepPlan p = plan_sweep(cell, prec, B, H, flags, false, row_T ? SWEEP_ROWS : 0);
-    LAS_ARG(!chunk_flag || (chunk_steps > 0 && p.x_chunks),
-            "las_rnn_seq_fwd_chunked: this configuration is not served by the kernel that waits for x-projection chunks");
-    a.xflag = chunk_flag; a.xsc = chunk_steps;
-    a.row_T = row_T;
-    LAS_ARG(!row_T || p.rows, "las_rnn_seq_fwd_rows: rows of different lengths are served by the 8-row "
-            "helper-wave kernel only (speed mode, clustered, the whole batch in one launch): ask las_rnn_seq_fwd_rows_ok");
+// What both passes hand their kernels: the call's tensors, as the fp32 and as the bf16 (speed mode) kernels see them -- one family is
+// used per launch -- and the switches in `flags`.  Every mode is off (zero); run_bf16 adds the workspace's regions.
+static RnnArgs sweep_args(const las_rnn_seq_args& s, int timeout_code) {
+    RnnArgs a{};
+    a.B = s.B; a.T = s.T; a.H = s.H; a.whh[0] = s.whh_fw; a.whh[1] = s.whh_bw; a.ldw = s.ldw;
+    a.gates = (float*)s.gates; a.out = (float*)s.out; a.cstate = (float*)s.cstate; a.dout = (const float*)s.dout;
+    a.gates16 = (unsigned short*)s.gates; a.out16 = (unsigned short*)s.out; a.cstate16 = (unsigned short*)s.cstate;
+    a.dout16 = (const unsigned short*)s.dout;
+    a.ld_out = s.ld_out; a.obs = s.out_bstride; a.ld_dout = s.ld_dout; a.dobs = s.dout_bstride; a.fb = s.forget_bias; a.wpack = s.ws;
+    a.rb = 16;
+    a.warm = (s.flags & LAS_SEQ_NO_WARMERS) ? 0 : 1;
+    const int lg = (s.flags >> 16) & 0x1f;                  // LAS_SEQ_SPIN_LOG2(n): bound of the exchange spins = 2^n polls
+    a.spin = lg ? (1 << lg) : LAS_SPIN_BUDGET_DEFAULT;
+    a.status = s.status; a.status_code = timeout_code;
+    a.announce = (s.flags >> 21) & 0x3ff;
 #ifdef LAS_PROF
     if (const char* e = getenv("LAS_DBG_PTR")) a.dbg = (long long*)strtoull(e, nullptr, 0);   // development build only
 #endif
+    return a;
+}
+
+// bf16 path: `ws` is the workspace the header documents (las_rnn_seq_workspace_bytes), not only the part that this batch's layout
+// reaches (run_bf16's own check) -- no caller that sizes it with the query is refused by one check and served by the other
+static int check_bf16_ws(const las_rnn_seq_args& s) {
+    const size_t need = las_rnn_seq_workspace_bytes(s.cell, s.prec, s.H, s.B);
+    LAS_ARG(s.ws && s.ws_bytes >= need, "las_rnn_seq: workspace too small (%zu < %zu)", s.ws_bytes, need);
+    return 0;
+}
+
+extern "C" int las_rnn_seq_fwd(const las_rnn_seq_args* sp, void* stream) {
+    LAS_ARG(sp, "las_rnn_seq_fwd: null argument struct");
+    const las_rnn_seq_args& s = *sp;
+    if (int rc = check_common("las_rnn_seq_fwd", s)) return rc;
+    LAS_ARG(!s.dout && !s.ld_dout && !s.dout_bstride && !s.dbias_fw && !s.dbias_bw && !s.dout_chunk_flag && !s.dout_chunk_rows &&
+            !s.dout_rows && !s.progress && !s.progress_steps, "las_rnn_seq_fwd: a BPTT-only field (dout .. progress_steps) is set");
+    LAS_ARG(!s.row_T || !s.x_chunk_flag, "las_rnn_seq_fwd: row_T and x_chunk_flag exclude each other");
+    hipStream_t st = (hipStream_t)stream;
+    RnnArgs a = sweep_args(s, LAS_SEQ_STATUS_FWD_TIMEOUT);
+    const SweepPlan p = plan_sweep(s.cell, s.prec, s.B, s.H, s.flags, false, s.row_T ? SWEEP_ROWS : 0);
+    LAS_ARG(!s.x_chunk_flag || (s.x_chunk_steps > 0 && p.x_chunks),
+            "las_rnn_seq_fwd: this configuration is not served by the kernel that waits for x-projection chunks: ask las_rnn_seq_plan's x_chunks");
+    a.xflag = s.x_chunk_flag; a.xsc = s.x_chunk_steps;
+    a.row_T = s.row_T;
+    LAS_ARG(!s.row_T || p.rows, "las_rnn_seq_fwd: rows of different lengths are served by the 8-row "
+            "helper-wave kernel only (speed mode, clustered, the whole batch in one launch): ask las_rnn_seq_plan's rows");
     if (p.path == SWEEP_BF16) {
-        LAS_ARG(ld_out % 4 == 0 && out_bstride % 4 == 0 && (((uintptr_t)gates | (uintptr_t)out | (uintptr_t)cstate) & 15) == 0,
+        LAS_ARG(s.ld_out % 4 == 0 && s.out_bstride % 4 == 0 && (((uintptr_t)s.gates | (uintptr_t)s.out | (uintptr_t)s.cstate) & 15) == 0,
                 "las_rnn_seq_fwd: bf16 tensors must be 16-byte aligned with pitches that are multiples of 4");
-        if (int rc = run_bf16(p, cell, a, whh_fw, whh_bw, ldw, ws, ws_bytes, flags, st)) return rc;
+        if (int rc = check_bf16_ws(s)) return rc;
+        if (int rc = run_bf16(p, s.cell, a, s.whh_fw, s.whh_bw, s.ldw, s.ws, s.ws_bytes, s.flags, st)) return rc;
     } else if (p.path == SWEEP_MF32) {
-        return las_rnn_seq_mf32_run(false, cell, a, ws, ws_bytes, flags, st);
+        return las_rnn_seq_mf32_run(false, s.cell, a, s.ws, s.ws_bytes, s.flags, st);
     } else {
-        const size_t lds = (size_t)H * F32_BT * sizeof(float);
-        dim3 grid(cdiv(B, F32_BT), 2);
-        if (cell == LAS_CELL_LSTM) hipLaunchKernelGGL(rnn_seq_fwd_f32_kernel<LAS_CELL_LSTM>, grid, dim3(256), lds, st, a);
-        else                       hipLaunchKernelGGL(rnn_seq_fwd_f32_kernel<LAS_CELL_RNN>, grid, dim3(256), lds, st, a);
+        const size_t lds = (size_t)s.H * F32_BT * sizeof(float);
+        dim3 grid(cdiv(s.B, F32_BT), 2);
+        if (s.cell == LAS_CELL_LSTM) hipLaunchKernelGGL(rnn_seq_fwd_f32_kernel<LAS_CELL_LSTM>, grid, dim3(256), lds, st, a);
+        else                         hipLaunchKernelGGL(rnn_seq_fwd_f32_kernel<LAS_CELL_RNN>, grid, dim3(256), lds, st, a);
     }
     LAS_LAUNCHED();
     return 0;
 }
 
-extern "C" int las_rnn_seq_bwd(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                               const float* whh_bw, int ldw, const void* out, int ld_out, long long out_bstride,
-                               const void* cstate, const void* dout, int ld_dout, long long dout_bstride,
-                               float forget_bias, int flags, int* status, void* ws, size_t ws_bytes, void* stream) {
-    return las_rnn_seq_bwd_db(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate, dout, ld_dout,
-                              dout_bstride, forget_bias, nullptr, nullptr, flags, status, ws, ws_bytes, stream);
-}
-
-extern "C" int las_rnn_seq_bwd_db(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                                  const float* whh_bw, int ldw, const void* out, int ld_out, long long out_bstride,
-                                  const void* cstate, const void* dout, int ld_dout, long long dout_bstride,
-                                  float forget_bias, float* dbias_fw, float* dbias_bw, int flags, int* status,
-                                  void* ws, size_t ws_bytes, void* stream) {
-    return las_rnn_seq_bwd_db_chunked(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate, dout, ld_dout,
-                                      dout_bstride, forget_bias, dbias_fw, dbias_bw, flags, status, nullptr, 0, 0, ws, ws_bytes, stream);
-}
-
-static int rnn_seq_bwd_db_impl(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                               const float* whh_bw, int ldw, const void* out, int ld_out, long long out_bstride,
-                               const void* cstate, const void* dout, int ld_dout, long long dout_bstride,
-                               float forget_bias, float* dbias_fw, float* dbias_bw, int flags, int* status,
-                               const int* chunk_flag, int chunk_rows, int n_rows, int* progress, int progress_steps,
-                               void* ws, size_t ws_bytes, void* stream);
-extern "C" int las_rnn_seq_bwd_db_chunked(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                                          const float* whh_bw, int ldw, const void* out, int ld_out, long long out_bstride,
-                                          const void* cstate, const void* dout, int ld_dout, long long dout_bstride,
-                                          float forget_bias, float* dbias_fw, float* dbias_bw, int flags, int* status,
-                                          const int* chunk_flag, int chunk_rows, int n_rows, void* ws, size_t ws_bytes, void* stream) {
-    return rnn_seq_bwd_db_impl(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate, dout, ld_dout, dout_bstride,
-                               forget_bias, dbias_fw, dbias_bw, flags, status, chunk_flag, chunk_rows, n_rows, nullptr, 0, ws, ws_bytes, stream);
-}
-extern "C" int las_rnn_seq_bwd_db_progress(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                                           const float* whh_bw, int ldw, const void* out, int ld_out, long long out_bstride,
-                                           const void* cstate, const void* dout, int ld_dout, long long dout_bstride,
-                                           float forget_bias, float* dbias_fw, float* dbias_bw, int flags, int* status,
-                                           const int* chunk_flag, int chunk_rows, int n_rows, int* progress, int progress_steps,
-                                           void* ws, size_t ws_bytes, void* stream) {
-    LAS_ARG(chunk_flag && progress && progress_steps > 0 && las_rnn_seq_bwd_progress_words(cell, prec, B, H, flags) > 0,
-            "las_rnn_seq_bwd_db_progress: needs a chunked upstream gradient and a configuration the progress-publishing kernel serves");
-    return rnn_seq_bwd_db_impl(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate, dout, ld_dout, dout_bstride,
-                               forget_bias, dbias_fw, dbias_bw, flags, status, chunk_flag, chunk_rows, n_rows, progress, progress_steps, ws, ws_bytes, stream);
-}
-static int rnn_seq_bwd_db_impl(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                               const float* whh_bw, int ldw, const void* out, int ld_out, long long out_bstride,
-                               const void* cstate, const void* dout, int ld_dout, long long dout_bstride,
-                               float forget_bias, float* dbias_fw, float* dbias_bw, int flags, int* status,
-                               const int* chunk_flag, int chunk_rows, int n_rows, int* progress, int progress_steps,
-                               void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = check_common("las_rnn_seq_bwd", cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, cstate)) return rc;
-    LAS_ARG(dout && ld_dout >= 2 * H, "las_rnn_seq_bwd: bad dout");
-    LAS_ARG(prec != LAS_PREC_BF16 || !mfma_shape_ok(H) ||
-            (ld_out % 4 == 0 && out_bstride % 4 == 0 && ld_dout % 4 == 0 && dout_bstride % 4 == 0 &&
-             (((uintptr_t)gates | (uintptr_t)out | (uintptr_t)cstate | (uintptr_t)dout) & 15) == 0),
+extern "C" int las_rnn_seq_bwd(const las_rnn_seq_args* sp, void* stream) {
+    LAS_ARG(sp, "las_rnn_seq_bwd: null argument struct");
+    const las_rnn_seq_args& s = *sp;
+    if (int rc = check_common("las_rnn_seq_bwd", s)) return rc;
+    LAS_ARG(!s.row_T && !s.x_chunk_flag && !s.x_chunk_steps, "las_rnn_seq_bwd: a forward-only field (x_chunk_flag, x_chunk_steps, row_T) is set");
+    const int B = s.B, T = s.T, H = s.H, G = s.cell == LAS_CELL_LSTM ? 4 : 1;
+    LAS_ARG(s.dout && s.ld_dout >= 2 * H, "las_rnn_seq_bwd: bad dout");
+    LAS_ARG(s.prec != LAS_PREC_BF16 || !mfma_shape_ok(H) ||
+            (s.ld_out % 4 == 0 && s.out_bstride % 4 == 0 && s.ld_dout % 4 == 0 && s.dout_bstride % 4 == 0 &&
+             (((uintptr_t)s.gates | (uintptr_t)s.out | (uintptr_t)s.cstate | (uintptr_t)s.dout) & 15) == 0),
             "las_rnn_seq_bwd: bf16 tensors must be 16-byte aligned with pitches that are multiples of 4");
     hipStream_t st = (hipStream_t)stream;
-    const int G = cell == LAS_CELL_LSTM ? 4 : 1;
-    RnnArgs a;
-    a.B = B; a.T = T; a.H = H; a.whh[0] = whh_fw; a.whh[1] = whh_bw; a.ldw = ldw;
-    a.ld_out = ld_out; a.obs = out_bstride;
-    bind_tensors(a, gates, const_cast<void*>(out), const_cast<void*>(cstate), dout);
-    a.ld_dout = ld_dout; a.dobs = dout_bstride; a.fb = forget_bias; a.wpack = ws;
-    seq_common_args(a, flags, status, LAS_SEQ_STATUS_BWD_TIMEOUT);
-    const SweepPlan p = plan_sweep(cell, prec, B, H, flags, true, (chunk_flag ? SWEEP_CHUNKS : 0) | (progress ? SWEEP_PROGRESS : 0));
-    LAS_ARG(!chunk_flag || (chunk_rows > 0 && (chunk_rows & (chunk_rows - 1)) == 0 && (n_rows == T || n_rows == (T + 1) / 2) &&
-                            p.dout_chunks),
-            "las_rnn_seq_bwd_db_chunked: bad chunk geometry, or a configuration the chunk-aware kernel does not serve");
-    a.dflag = chunk_flag; a.dTq = n_rows; a.dshift = (chunk_flag && n_rows != T) ? 1 : 0;
-    for (int c = chunk_rows; c > 1; c >>= 1) ++a.dcp;
-    a.prog = progress; a.pstep = progress_steps;
-#ifdef LAS_PROF
-    if (const char* e = getenv("LAS_DBG_PTR")) a.dbg = (long long*)strtoull(e, nullptr, 0);   // development build only
-#endif
+    RnnArgs a = sweep_args(s, LAS_SEQ_STATUS_BWD_TIMEOUT);
+    const SweepPlan p = plan_sweep(s.cell, s.prec, B, H, s.flags, true, (s.dout_chunk_flag ? SWEEP_CHUNKS : 0) | (s.progress ? SWEEP_PROGRESS : 0));
+    LAS_ARG(!s.progress || (s.dout_chunk_flag && s.progress_steps > 0 && p.progress_words > 0),
+            "las_rnn_seq_bwd: progress needs a chunked upstream gradient and a configuration the progress-publishing kernel serves: "
+            "ask las_rnn_seq_plan's progress_words");
+    LAS_ARG(!s.dout_chunk_flag || (s.dout_chunk_rows > 0 && (s.dout_chunk_rows & (s.dout_chunk_rows - 1)) == 0 &&
+                                   (s.dout_rows == T || s.dout_rows == (T + 1) / 2) && p.dout_chunks),
+            "las_rnn_seq_bwd: bad chunk geometry, or a configuration the chunk-aware kernel does not serve: ask las_rnn_seq_plan's dout_chunks");
+    a.dflag = s.dout_chunk_flag; a.dTq = s.dout_rows; a.dshift = (s.dout_chunk_flag && s.dout_rows != T) ? 1 : 0;
+    for (int c = s.dout_chunk_rows; c > 1; c >>= 1) ++a.dcp;
+    a.prog = s.progress; a.pstep = s.progress_steps;
     const bool bf = p.path == SWEEP_BF16;
     if (bf) {
+        if (int rc = check_bf16_ws(s)) return rc;
         int db_done = 0;
-        if (int rc = run_bf16(p, cell, a, whh_fw, whh_bw, ldw, ws, ws_bytes, flags, st, dbias_fw, dbias_bw, &db_done)) return rc;
+        if (int rc = run_bf16(p, s.cell, a, s.whh_fw, s.whh_bw, s.ldw, s.ws, s.ws_bytes, s.flags, st, s.dbias_fw, s.dbias_bw, &db_done)) return rc;
         if (db_done) return 0;
     } else if (p.path == SWEEP_MF32) {
-        if (int rc = las_rnn_seq_mf32_run(true, cell, a, ws, ws_bytes, flags, st)) return rc;
+        if (int rc = las_rnn_seq_mf32_run(true, s.cell, a, s.ws, s.ws_bytes, s.flags, st)) return rc;
     } else {
-        LAS_ARG(ws && ws_bytes >= (size_t)2 * G * H * H * sizeof(float), "las_rnn_seq_bwd: workspace too small");
-        hipLaunchKernelGGL(transpose_whh_kernel, dim3(cdiv(2LL * G * H * H, 256 * 4)), dim3(256), 0, st, whh_fw, whh_bw, ldw,
-                           H, G * H, (float*)ws);
+        LAS_ARG(s.ws && s.ws_bytes >= (size_t)2 * G * H * H * sizeof(float), "las_rnn_seq_bwd: workspace too small");
+        hipLaunchKernelGGL(transpose_whh_kernel, dim3(cdiv(2LL * G * H * H, 256 * 4)), dim3(256), 0, st, s.whh_fw, s.whh_bw, s.ldw,
+                           H, G * H, (float*)s.ws);
         LAS_LAUNCHED();
         const size_t lds = (size_t)G * H * F32_BT * sizeof(float);
         if (lds > 64 * 1024) {
@@ -2096,16 +2024,16 @@ static int rnn_seq_bwd_db_impl(int cell, int prec, int B, int T, int H, void* ga
             LAS_ARG(a1 == 0 && a2 == 0 && lds <= 159 * 1024, "las_rnn_seq_bwd: H too large for the fp32 kernel");
         }
         dim3 grid(cdiv(B, F32_BT), 2);
-        if (cell == LAS_CELL_LSTM) hipLaunchKernelGGL(rnn_seq_bwd_f32_kernel<LAS_CELL_LSTM>, grid, dim3(256), lds, st, a);
-        else                       hipLaunchKernelGGL(rnn_seq_bwd_f32_kernel<LAS_CELL_RNN>, grid, dim3(256), lds, st, a);
+        if (s.cell == LAS_CELL_LSTM) hipLaunchKernelGGL(rnn_seq_bwd_f32_kernel<LAS_CELL_LSTM>, grid, dim3(256), lds, st, a);
+        else                         hipLaunchKernelGGL(rnn_seq_bwd_f32_kernel<LAS_CELL_RNN>, grid, dim3(256), lds, st, a);
     }
     LAS_LAUNCHED();
     // kernels that do not accumulate the bias gradient themselves: column sums of the finished d(pre-activation)
     for (int d = 0; d < 2; ++d) {
-        float* db = d ? dbias_bw : dbias_fw;
+        float* db = d ? s.dbias_bw : s.dbias_fw;
         if (!db) continue;
-        const void* gd = bf ? (const void*)((const unsigned short*)gates + (size_t)d * G * H) : (const void*)((const float*)gates + (size_t)d * G * H);
-        if (int rc = las_colsum_dt(gd, bf ? LAS_DT_BF16 : LAS_DT_F32, B * T, G * H, 2 * G * H, 1.f, db, ws, ws_bytes, stream)) return rc;
+        const void* gd = bf ? (const void*)((const unsigned short*)s.gates + (size_t)d * G * H) : (const void*)((const float*)s.gates + (size_t)d * G * H);
+        if (int rc = las_colsum_dt(gd, bf ? LAS_DT_BF16 : LAS_DT_F32, B * T, G * H, 2 * G * H, 1.f, db, s.ws, s.ws_bytes, stream)) return rc;
     }
     return 0;
 }

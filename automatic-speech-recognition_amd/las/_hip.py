@@ -4,6 +4,7 @@ This is the only place the Python host code touches native code.  There is NO fa
 shared library is missing or a call fails, a RuntimeError is raised (the product path never
 routes through the CPU oracle).
 """
+import collections
 import ctypes
 import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t,
@@ -90,6 +91,23 @@ class SeqPrepareDesc(ctypes.Structure):
                 ("flags", c_int), ("ws", c_void_p), ("ws_bytes", c_size_t)]
 
 
+class RnnSeqArgs(ctypes.Structure):
+    """include/las_hip.h las_rnn_seq_args"""
+    _fields_ = [(n, c_int) for n in ("cell", "prec", "B", "T", "H")] + \
+               [("gates", c_void_p), ("whh_fw", c_void_p), ("whh_bw", c_void_p), ("ldw", c_int),
+                ("out", c_void_p), ("ld_out", c_int), ("out_bstride", c_longlong), ("cstate", c_void_p),
+                ("forget_bias", c_float), ("flags", c_int), ("status", c_void_p), ("ws", c_void_p), ("ws_bytes", c_size_t),
+                ("x_chunk_flag", c_void_p), ("x_chunk_steps", c_int), ("row_T", c_void_p),
+                ("dout", c_void_p), ("ld_dout", c_int), ("dout_bstride", c_longlong), ("dbias_fw", c_void_p), ("dbias_bw", c_void_p),
+                ("dout_chunk_flag", c_void_p), ("dout_chunk_rows", c_int), ("dout_rows", c_int),
+                ("progress", c_void_p), ("progress_steps", c_int)]
+
+
+class RnnSeqPlanInfo(ctypes.Structure):
+    """include/las_hip.h las_rnn_seq_plan_info"""
+    _fields_ = [(n, c_int) for n in ("kernel", "P", "rows_per_tile", "launches", "x_chunks", "rows", "dout_chunks", "progress_words")]
+
+
 class FrontendArgs(ctypes.Structure):
     """include/las_hip.h las_frontend_args"""
     _fields_ = [("samples", c_void_p), ("samples_i16", c_int), ("ld_samples", c_longlong), ("n_samples", c_void_p), ("n_samples_host", POINTER(c_int))] + \
@@ -133,16 +151,11 @@ _SIGS = {
     "las_tanh_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "las_rnn_seq_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "las_rnn_seq_io_dtype": (c_int, [c_int, c_int, c_int]),
+    "las_rnn_seq_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(RnnSeqPlanInfo)]),
+    "las_rnn_seq_fwd": (c_int, [POINTER(RnnSeqArgs), c_void_p]),
+    "las_rnn_seq_bwd": (c_int, [POINTER(RnnSeqArgs), c_void_p]),
     "las_colsum_dt": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "las_tanh_bwd_dt": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "las_rnn_seq_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                c_void_p, c_int, c_longlong, c_void_p, c_float, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "las_rnn_seq_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_longlong,
-                                c_float, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "las_rnn_seq_bwd_db": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                   c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_longlong,
-                                   c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "las_speller_workspace_bytes": (c_size_t, [c_int] * 10),
     "las_speller_act_save_bytes": (c_size_t, [c_int] * 5),
     "las_speller_fwd": (c_int, [POINTER(SpellerFwdArgs), c_void_p]),
@@ -176,24 +189,9 @@ _SIGS = {
     "las_occupy": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "las_gemm_kk_frames": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p, c_longlong,
                                    c_void_p, c_int, c_longlong, c_void_p, c_int, c_void_p, c_longlong, c_void_p]),
-    "las_rnn_seq_bwd_chunks_ok": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "las_rnn_seq_bwd_db_chunked": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                           c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_longlong,
-                                           c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "las_rnn_seq_bwd_progress_words": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "las_rnn_seq_plan_kernel": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
-    "las_rnn_seq_bwd_db_progress": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                            c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_longlong,
-                                            c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "las_wait_words_min": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "las_wgrad_ih_hh_window": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "las_rnn_seq_fwd_rows_ok": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "las_rnn_seq_fwd_rows": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_longlong,
-                                     c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "las_rnn_seq_fwd_chunks_ok": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "las_rnn_seq_fwd_chunked": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                        c_longlong, c_void_p, c_float, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "las_lstm_pointwise": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "las_lstm_pointwise_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "las_lstm_cell_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -224,7 +222,7 @@ _SIGS = {
 }
 
 
-ABI_VERSION = 602      # include/las_hip.h LAS_HIP_ABI_VERSION
+ABI_VERSION = 603      # include/las_hip.h LAS_HIP_ABI_VERSION
 
 
 def declared_symbols():
@@ -521,10 +519,6 @@ def wgrad_ih_hh_window(x, ldx, I, out, ld_out, out_bstride, gates, lddz, B, T, H
 def wait_words_min(words, n, need, max_us=50000):
     """stream-ordered wait until every one of words[0:n] is >= need; a time-out marks the step invalid through the status word (code 2)"""
     check(lib().las_wait_words_min(p(words), int(n), int(need), int(max_us), p(status_word(words.device)), 2, stream()), "las_wait_words_min")
-
-
-def rnn_seq_bwd_progress_words(cell, prec, B, H, flags=None):
-    return int(lib().las_rnn_seq_bwd_progress_words(cell, prec, B, H, seq_flags if flags is None else flags))
 
 
 def skinny_pack(W, K, N, ldw=None, row0=0):
@@ -876,25 +870,39 @@ def set_word(word, value):
     check(lib().las_set_word(p(word), int(value), stream()), "las_set_word")
 
 
+# las_rnn_seq_plan's kernels (include/las_hip.h LAS_SWEEP_*) and its `mode` bits
+SWEEP_KERNELS = ("NONE", "FWD_PLAIN", "FWD_HW16", "FWD_HW8", "FWD_HW8_RAGGED", "BWD_PLAIN", "BWD_KS16", "BWD_KS8", "BWD_KS8_CH", "BWD_KS8_CH_PG")
+SWEEP_MODE_ROWS, SWEEP_MODE_CHUNKS, SWEEP_MODE_PROGRESS = 1, 2, 4
+SweepPlan = collections.namedtuple("SweepPlan", [n for n, _ in RnnSeqPlanInfo._fields_])
+
+
+def rnn_seq_plan(cell, prec, B, H, flags=None, bwd=False, mode=0):
+    """las_rnn_seq_plan: the sweep the library would launch (kernel: its SWEEP_KERNELS name) and what it serves; host arithmetic, no GPU."""
+    info = RnnSeqPlanInfo()
+    check(lib().las_rnn_seq_plan(cell, prec, B, H, seq_flags if flags is None else flags, int(bool(bwd)), int(mode), ctypes.byref(info)),
+          "las_rnn_seq_plan")
+    return SweepPlan(*(getattr(info, n) for n in SweepPlan._fields))._replace(kernel=SWEEP_KERNELS[info.kernel])
+
+
 def rnn_seq_fwd_chunks_ok(cell, prec, B, H, flags=None):
-    return bool(lib().las_rnn_seq_fwd_chunks_ok(cell, prec, B, H, seq_flags if flags is None else flags))
+    return bool(rnn_seq_plan(cell, prec, B, H, flags).x_chunks)
 
 
 def rnn_seq_fwd_rows_ok(cell, prec, B, H, flags=None):
-    return bool(lib().las_rnn_seq_fwd_rows_ok(cell, prec, B, H, seq_flags if flags is None else flags))
+    return bool(rnn_seq_plan(cell, prec, B, H, flags).rows)
 
 
-# las_rnn_seq_plan_kernel's answers (include/las_hip.h LAS_SWEEP_*) and its `mode` bits
-SWEEP_KERNELS = ("NONE", "FWD_PLAIN", "FWD_HW16", "FWD_HW8", "FWD_HW8_RAGGED", "BWD_PLAIN", "BWD_KS16", "BWD_KS8", "BWD_KS8_CH", "BWD_KS8_CH_PG")
-SWEEP_MODE_ROWS, SWEEP_MODE_CHUNKS, SWEEP_MODE_PROGRESS = 1, 2, 4
+def rnn_seq_bwd_chunks_ok(cell, prec, B, H, flags=None):
+    return bool(rnn_seq_plan(cell, prec, B, H, flags, bwd=True).dout_chunks)
+
+
+def rnn_seq_bwd_progress_words(cell, prec, B, H, flags=None):
+    return rnn_seq_plan(cell, prec, B, H, flags, bwd=True).progress_words
 
 
 def rnn_seq_plan_kernel(cell, prec, B, H, flags=None, bwd=False, mode=0):
-    """(kernel name, cluster width, rows per tile, row-chunk launches) of the sweep the library would launch: host arithmetic, no GPU."""
-    P, rb, n = c_int(0), c_int(0), c_int(0)
-    k = int(lib().las_rnn_seq_plan_kernel(cell, prec, B, H, seq_flags if flags is None else flags, int(bool(bwd)), int(mode),
-                                          ctypes.byref(P), ctypes.byref(rb), ctypes.byref(n)))
-    return SWEEP_KERNELS[k], P.value, rb.value, n.value
+    """(kernel name, cluster width, rows per tile, row-chunk launches) of the sweep the library would launch"""
+    return tuple(rnn_seq_plan(cell, prec, B, H, flags, bwd, mode)[:4])
 
 
 def rnn_seq_prepare(jobs):
@@ -909,72 +917,52 @@ def rnn_seq_prepare(jobs):
     check(lib().las_rnn_seq_prepare(arr, len(jobs), stream()), "las_rnn_seq_prepare")
 
 
-def rnn_seq_fwd(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate,
-                forget_bias=1.0, wf_off=0, wb_off=0, flags=None, chunk_flag=None, chunk_steps=0, row_T=None, prepared_ws=None):
-    """prepared_ws: a workspace rnn_seq_prepare has prepared for exactly this sweep (LAS_SEQ_PREPARED: no pack launch in front of it)."""
-    require_gpu(gates, whh_fw, whh_bw, out, cstate)
-    _check_io(cell, prec, H, gates, out, cstate)
+def _rnn_seq_args(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate, forget_bias, wf_off, wb_off, flags, prepared_ws):
+    """the fields of las_rnn_seq_args both passes fill (wf_off / wb_off: element offsets of W_hh; every mode off)"""
     ws = rnn_seq_ws(cell, prec, H, B, gates.device) if prepared_ws is None else prepared_ws
     fl = (seq_flags if flags is None else flags) | (SEQ_PREPARED if prepared_ws is not None else 0)
+    return RnnSeqArgs(cell=cell, prec=prec, B=B, T=T, H=H, gates=gates.data_ptr(), whh_fw=whh_fw.data_ptr() + 4 * wf_off,
+                      whh_bw=whh_bw.data_ptr() + 4 * wb_off, ldw=ldw, out=out.data_ptr(), ld_out=ld_out, out_bstride=out_bstride,
+                      cstate=None if cstate is None else cstate.data_ptr(), forget_bias=forget_bias, flags=fl,
+                      status=status_word(gates.device).data_ptr(), ws=ws.data_ptr(), ws_bytes=ws.numel())
+
+
+def rnn_seq_fwd(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate,
+                forget_bias=1.0, wf_off=0, wb_off=0, flags=None, chunk_flag=None, chunk_steps=0, row_T=None, prepared_ws=None):
+    """chunk_flag / chunk_steps: the x-projection is still being produced in chunks (las_rnn_seq_args x_chunk_flag); row_T: rows of
+    different lengths.  prepared_ws: a workspace rnn_seq_prepare has prepared for exactly this sweep (LAS_SEQ_PREPARED: no pack launch
+    in front of it)."""
+    require_gpu(gates, whh_fw, whh_bw, out, cstate, row_T)
+    _check_io(cell, prec, H, gates, out, cstate)
+    a = _rnn_seq_args(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate, forget_bias, wf_off, wb_off, flags, prepared_ws)
     if row_T is not None:
-        require_gpu(row_T)
         assert chunk_flag is None and row_T.dtype == torch.int32 and row_T.numel() == B
-        with _timed("rnn_seq_fwd_rows[T=%d,H=%d]" % (T, H)):
-            check(lib().las_rnn_seq_fwd_rows(cell, prec, B, T, H, p(gates), c_void_p(whh_fw.data_ptr() + 4 * wf_off),
-                                             c_void_p(whh_bw.data_ptr() + 4 * wb_off), ldw, p(out), ld_out, out_bstride,
-                                             p(cstate), forget_bias, fl, p(status_word(gates.device)), p(row_T),
-                                             p(ws), ws.numel(), stream()), "las_rnn_seq_fwd_rows")
-        return
+        a.row_T = row_T.data_ptr()
     if chunk_flag is not None:
-        with _timed("rnn_seq_fwd[T=%d,H=%d]" % (T, H)):
-            check(lib().las_rnn_seq_fwd_chunked(cell, prec, B, T, H, p(gates), c_void_p(whh_fw.data_ptr() + 4 * wf_off),
-                                                c_void_p(whh_bw.data_ptr() + 4 * wb_off), ldw, p(out), ld_out, out_bstride,
-                                                p(cstate), forget_bias, fl, p(status_word(gates.device)), p(chunk_flag), chunk_steps,
-                                                p(ws), ws.numel(), stream()), "las_rnn_seq_fwd_chunked")
-        return
-    with _timed("rnn_seq_fwd[T=%d,H=%d]" % (T, H)):
-        check(lib().las_rnn_seq_fwd(cell, prec, B, T, H, p(gates), c_void_p(whh_fw.data_ptr() + 4 * wf_off),
-                                    c_void_p(whh_bw.data_ptr() + 4 * wb_off), ldw, p(out), ld_out, out_bstride,
-                                    p(cstate), forget_bias, fl, p(status_word(gates.device)), p(ws), ws.numel(), stream()),
-              "las_rnn_seq_fwd")
-
-
-def rnn_seq_bwd_chunks_ok(cell, prec, B, H, flags=None):
-    return bool(lib().las_rnn_seq_bwd_chunks_ok(cell, prec, B, H, seq_flags if flags is None else flags))
+        a.x_chunk_flag, a.x_chunk_steps = chunk_flag.data_ptr(), chunk_steps
+    with _timed("rnn_seq_fwd%s[T=%d,H=%d]" % ("_rows" if row_T is not None else "", T, H)):
+        check(lib().las_rnn_seq_fwd(ctypes.byref(a), stream()), "las_rnn_seq_fwd")
 
 
 def rnn_seq_bwd(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate,
                 dout, ld_dout, dout_bstride, forget_bias=1.0, wf_off=0, wb_off=0, db_fw=None, db_bw=None, flags=None,
                 chunk_flag=None, chunk_rows=0, n_rows=0, prepared_ws=None, progress=None, progress_steps=0):
     """db_fw / db_bw: optional [G*H] bias-gradient tensors, accumulated (+=) by the sweep itself.
-    chunk_flag / chunk_rows / n_rows: dout is still being produced in chunks (las_rnn_seq_bwd_db_chunked)."""
+    chunk_flag / chunk_rows / n_rows: dout is still being produced in chunks (las_rnn_seq_args dout_chunk_flag); progress /
+    progress_steps: the chunked sweep publishes its progress."""
     require_gpu(gates, whh_fw, whh_bw, out, cstate, dout)
     _check_io(cell, prec, H, gates, out, cstate, dout)
-    ws = rnn_seq_ws(cell, prec, H, B, gates.device) if prepared_ws is None else prepared_ws
-    fl = (seq_flags if flags is None else flags) | (SEQ_PREPARED if prepared_ws is not None else 0)
-    fl |= next_announce() << 21                    # LAS_SEQ_ANNOUNCE: status_word[1] = this number once the sweep is resident
+    a = _rnn_seq_args(cell, prec, B, T, H, gates, whh_fw, whh_bw, ldw, out, ld_out, out_bstride, cstate, forget_bias, wf_off, wb_off, flags, prepared_ws)
+    a.flags |= next_announce() << 21               # LAS_SEQ_ANNOUNCE: status_word[1] = this number once the sweep is resident
     _announce[0] += 1
-    if chunk_flag is not None and progress is not None:
-        with _timed("rnn_seq_bwd[T=%d,H=%d]" % (T, H)):
-            check(lib().las_rnn_seq_bwd_db_progress(cell, prec, B, T, H, p(gates), c_void_p(whh_fw.data_ptr() + 4 * wf_off),
-                                                    c_void_p(whh_bw.data_ptr() + 4 * wb_off), ldw, p(out), ld_out, out_bstride,
-                                                    p(cstate), p(dout), ld_dout, dout_bstride, forget_bias, p(db_fw), p(db_bw),
-                                                    fl, p(status_word(gates.device)), p(chunk_flag), chunk_rows, n_rows,
-                                                    p(progress), int(progress_steps), p(ws), ws.numel(), stream()), "las_rnn_seq_bwd_db_progress")
-        return
+    a.dout, a.ld_dout, a.dout_bstride = dout.data_ptr(), ld_dout, dout_bstride
+    a.dbias_fw, a.dbias_bw = (None if t is None else t.data_ptr() for t in (db_fw, db_bw))
     if chunk_flag is not None:
-        with _timed("rnn_seq_bwd[T=%d,H=%d]" % (T, H)):
-            check(lib().las_rnn_seq_bwd_db_chunked(cell, prec, B, T, H, p(gates), c_void_p(whh_fw.data_ptr() + 4 * wf_off),
-                                                   c_void_p(whh_bw.data_ptr() + 4 * wb_off), ldw, p(out), ld_out, out_bstride,
-                                                   p(cstate), p(dout), ld_dout, dout_bstride, forget_bias, p(db_fw), p(db_bw),
-                                                   fl, p(status_word(gates.device)), p(chunk_flag), chunk_rows, n_rows,
-                                                   p(ws), ws.numel(), stream()), "las_rnn_seq_bwd_db_chunked")
-        return
+        a.dout_chunk_flag, a.dout_chunk_rows, a.dout_rows = chunk_flag.data_ptr(), chunk_rows, n_rows
+        if progress is not None:
+            a.progress, a.progress_steps = progress.data_ptr(), int(progress_steps)
     with _timed("rnn_seq_bwd[T=%d,H=%d]" % (T, H)):
-        check(lib().las_rnn_seq_bwd_db(cell, prec, B, T, H, p(gates), c_void_p(whh_fw.data_ptr() + 4 * wf_off),
-                                       c_void_p(whh_bw.data_ptr() + 4 * wb_off), ldw, p(out), ld_out, out_bstride,
-                                       p(cstate), p(dout), ld_dout, dout_bstride, forget_bias, p(db_fw), p(db_bw),
-                                       fl, p(status_word(gates.device)), p(ws), ws.numel(), stream()), "las_rnn_seq_bwd_db")
+        check(lib().las_rnn_seq_bwd(ctypes.byref(a), stream()), "las_rnn_seq_bwd")
 
 
 SPELLER_FAMILIES = ((1, "loop"), (2, "pf_rows"), (4, "bf_rows"), (8, "f32_rows"), (16, "skinny_cell0"), (32, "loc"), (64, "skinny_upper_cells"), (128, "wide"))

@@ -273,7 +273,7 @@ class BeamSearch(object):
                   _hip.rnn_seq_io_dtype(cellid, prec, H_enc) == torch.bfloat16 and _hip.rnn_seq_fwd_rows_ok(cellid, prec, n, H_enc))
         if ragged:
             # ONE encoder pass over all utterances although their lengths differ (the reference feeds them one at a time, unpadded):
-            # the forward sweeps take the rows' frame counts (las_rnn_seq_fwd_rows: a row's state and outputs are zero behind its last
+            # the forward sweeps take the rows' frame counts (las_rnn_seq_args' row_T: a row's state and outputs are zero behind its last
             # frame, so its backward direction starts from the zero state at ITS last frame and an odd length pairs with a zero frame,
             # exactly as alone); the products in between are row-wise.  Every real frame equals the one-at-a-time result.
             lens = [int(np.shape(x[0])[1]) for x in xs_list]

@@ -118,7 +118,7 @@ _XCHUNK = {}          # data_ptr of a dense + tanh output (pBLSTMLayer, forward)
 _PARAMS = {}          # hand-over of the leaf parameter objects to the autograd node being built (same thread, immediate)
 import os
 ROW_T = [None]        # inference over a batch of utterances of DIFFERENT lengths: int32 [B] device tensor of the current layer's frames per row
-                      # (set around the listener call by BeamSearch.decode_batch; the pyramid layers halve it) -- las_rnn_seq_fwd_rows
+                      # (set around the listener call by BeamSearch.decode_batch; the pyramid layers halve it) -- las_rnn_seq_args' row_T
 XPROJ_CHUNK_STEPS = int(os.environ.get("LAS_XPROJ_CHUNK", "64"))     # 0: the whole x-projection before the sweep
 DENSE_CHUNK_MAX_ROWS = 64
 DENSE_CHUNKS = os.environ.get("LAS_DENSE_CHUNK", "1") != "0"         # the dense + tanh in front of a chunked x-projection follows the same chunks
@@ -148,7 +148,7 @@ def _xproj_chunk_steps(B, T, H, cell):
     """Sweep steps per time chunk of a layer's x-projection hand-over (0: the whole projection before the sweep)."""
     cs = XPROJ_CHUNK_STEPS
     if ROW_T[0] is not None:
-        return 0                                     # rows of different lengths (inference): whole x-projection, las_rnn_seq_fwd_rows
+        return 0                                     # rows of different lengths (inference): whole x-projection, las_rnn_seq_fwd with row_T
     if cs and T >= 4 * cs and _hip.rnn_seq_fwd_chunks_ok(_cellid(cell), _hip.PREC_BF16, B, H):
         return cs
     return 0
@@ -456,7 +456,7 @@ _PROG = 512          # progress words of a BPTT sweep that publishes how far its
 
 
 def _progress_words(dev, n):
-    """n zeroed device words for las_rnn_seq_bwd_db_progress (zeroed with the flag ring by begin_step; by a fill otherwise)"""
+    """n zeroed device words for las_rnn_seq_args' progress (zeroed with the flag ring by begin_step; by a fill otherwise)"""
     ring = _flag_ring(dev)
     w = ring[0][_RING:_RING + n]
     if len(ring) > 3 and ring[3]:

@@ -37,7 +37,7 @@ enum { LAS_ACT_NONE = 0, LAS_ACT_TANH = 1 };
 enum { LAS_ATT_ADD = 0, LAS_ATT_LOC = 1 };      /* las/las.py:44-49 */
 enum { LAS_DT_F32 = 0, LAS_DT_BF16 = 1 };       /* element type of a tensor in HBM (see las_gemm_kk) */
 
-#define LAS_HIP_ABI_VERSION 602      /* bumped whenever an argument struct or a signature changes: las_version() of a library
+#define LAS_HIP_ABI_VERSION 603      /* bumped whenever an argument struct or a signature changes: las_version() of a library
                                         built from another header differs, and the Python loader refuses it */
 int         las_version(void);
 const char* las_last_error(void);
@@ -158,7 +158,7 @@ int las_tanh_bwd_dt(const void* Y, int y_dt, int ldy, const void* dY, int dy_dt,
  *   LAS_SEQ_F32_VALU         LAS_PREC_F32: the round-1 VALU kernels (one workgroup per (direction, 8 rows), W_hh streamed from L2)
  *                            instead of the clustered exact-fp32 MFMA kernels (csrc/rnn_seq_f32.hip) -- tests cross-check the two
  *   LAS_SEQ_P(p)             cluster width override (1, 2, 4, 8 workgroups per (direction, 16-row tile)); a width with no kernel falls
- *                            back to the next narrower one, and the las_rnn_seq_*_ok / _progress_words queries describe the width that runs
+ *                            back to the next narrower one, and las_rnn_seq_plan describes the width that runs
  *   LAS_SEQ_SPIN_LOG2(n)     bound of every exchange spin = 2^n polls (default 2^22)
  *   LAS_SEQ_PREPARED         NOT a development switch: `ws` was prepared by las_rnn_seq_prepare (below) for these weights, this cell / H /
  *                            direction of the pass / flags and a batch >= B, and no sweep has used it since -- the launch then skips its own
@@ -171,7 +171,7 @@ enum { LAS_SEQ_AGENT_GRANULES = 1, LAS_SEQ_NO_KSPLIT = 2, LAS_SEQ_NO_HELPER_WAVE
        LAS_SEQ_F32_VALU = 32, LAS_SEQ_PREPARED = 64 };
 #define LAS_SEQ_P(p) (((p) & 0xf) << 8)
 #define LAS_SEQ_SPIN_LOG2(n) (((n) & 0x1f) << 16)
-/* LAS_SEQ_ANNOUNCE(n), n in 1..1023 (las_rnn_seq_bwd*, clustered kernels): `status` then points to TWO ints and the launch
+/* LAS_SEQ_ANNOUNCE(n), n in 1..1023 (las_rnn_seq_bwd, clustered kernels): `status` then points to TWO ints and the launch
  * stores n into status[1] as soon as its first cluster is resident on the device -- see las_wait_word. */
 #define LAS_SEQ_ANNOUNCE(n) (((n) & 0x3ff) << 21)
 enum { LAS_SEQ_STATUS_OK = 0, LAS_SEQ_STATUS_FWD_TIMEOUT = 1, LAS_SEQ_STATUS_BWD_TIMEOUT = 2 };
@@ -187,7 +187,7 @@ size_t las_rnn_seq_workspace_bytes(int cell, int prec, int H, int B);
  * (layer, pass) pairs in ONE launch -- once per optimiser step, off the dependency chain -- each into a workspace of its own
  * (las_rnn_seq_workspace_bytes(cell, LAS_PREC_BF16, H, B)); the sweep that then gets such a workspace together with LAS_SEQ_PREPARED in
  * `flags` launches nothing but its persistent kernel.  A prepared workspace serves ONE sweep (the exchange state is dirty afterwards) with
- * the same cell / H / flags / direction of the pass (bwd = 0: las_rnn_seq_fwd*, 1: las_rnn_seq_bwd*) and any batch B' <= B.
+ * the same cell / H / flags / direction of the pass (bwd = 0: las_rnn_seq_fwd, 1: las_rnn_seq_bwd) and any batch B' <= B.
  * whh_fw / whh_bw: as for las_rnn_seq_fwd.  Only LAS_PREC_BF16 shapes (H in {64,128,256,512}).  `descs` is HOST memory. */
 typedef struct las_seq_prepare_desc {
     const float* whh_fw; const float* whh_bw; int ldw;
@@ -199,75 +199,13 @@ int las_rnn_seq_prepare(const las_seq_prepare_desc* descs, int n, void* stream);
  * shape (prec = LAS_PREC_BF16 and H in {64,128,256,512}), else LAS_DT_F32 (parity mode, or a speed-mode shape that falls
  * back to the fp32 VALU sweep).  The caller allocates those tensors -- and makes the K1 product write them -- accordingly. */
 int las_rnn_seq_io_dtype(int cell, int prec, int H);
-int las_rnn_seq_fwd(int cell, int prec, int B, int T, int H, void* gates,
-                    const float* whh_fw, const float* whh_bw, int ldw,
-                    void* out, int ld_out, long long out_bstride, void* cstate,
-                    float forget_bias, int flags, int* status, void* ws, size_t ws_bytes, void* stream);
-/* las_rnn_seq_fwd for an x-projection that is still being computed: `gates` is filled in time chunks of `chunk_steps` sweep steps,
- * chunk k = frames [k*cs, (k+1)*cs) and [T-(k+1)*cs, T-k*cs) of every utterance (both ends of the sequence first: the forward
- * direction consumes t = 0, 1, .., the backward direction t = T-1, T-2, ..), e.g. by las_gemm_kk_frames launches on ANOTHER
- * stream, each followed by las_set_word(chunk_flag, k+1).  The sweep reads a frame only after *chunk_flag has reached its chunk
- * (bounded wait -> LAS_SEQ_STATUS_FWD_TIMEOUT).  Chunk 0 must be complete IN STREAM ORDER in front of this call (produced on `stream`,
- * or on a stream `stream` has waited for): the sweep never waits for it and the value of *chunk_flag only matters from 2 on -- no
- * flag launch is needed between chunk 0's product and the sweep (round 5).  Only the helper-wave kernel
- * supports this: ask las_rnn_seq_fwd_chunks_ok first.  chunk_flag = NULL: las_rnn_seq_fwd. */
-int las_rnn_seq_fwd_chunks_ok(int cell, int prec, int B, int H, int flags);
-int las_rnn_seq_fwd_chunked(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                            const float* whh_bw, int ldw, void* out, int ld_out, long long out_bstride,
-                            void* cstate, float forget_bias, int flags, int* status, const int* chunk_flag, int chunk_steps,
-                            void* ws, size_t ws_bytes, void* stream);
-/* las_rnn_seq_fwd for a batch whose rows have DIFFERENT lengths (beam search encodes utterances the reference feeds one at a time,
- * unpadded -- its encoder has no length mask): row_T [B] device ints, row_T[b] <= T frames of row b.  At frames t >= row_T[b] the row's
- * state and outputs are forced to ZERO: the backward direction reaches the row's last real frame with the zero state of an unpadded run,
- * the forward direction's real frames come first, and the zero pad frame is the one the pyramid appends to an odd-length utterance --
- * every real frame equals the one-utterance-at-a-time result.  Served by the 8-row helper-wave kernel (las_rnn_seq_fwd_rows_ok). */
-int las_rnn_seq_fwd_rows_ok(int cell, int prec, int B, int H, int flags);
-int las_rnn_seq_fwd_rows(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                         const float* whh_bw, int ldw, void* out, int ld_out, long long out_bstride,
-                         void* cstate, float forget_bias, int flags, int* status, const int* row_T,
-                         void* ws, size_t ws_bytes, void* stream);
-/* C = act(A . B^T + bias) like las_gemm_kk, restricted to the frames [lo0, lo0+nlo) and [hi0, hi0+nhi) of every utterance of
- * [nb, T, *] tensors A and C (row pitches lda / ldc per frame); las_set_word: stream-ordered store of a device word. */
-int las_gemm_kk_frames(int nb, int T, int lo0, int nlo, int hi0, int nhi, int N, int K, const void* A, long long lda,
-                       const void* B, long long ldb, void* C, int c_dtype, long long ldc, const float* bias, int act,
-                       const void* y_tanh, long long ldy, void* stream);       /* y_tanh as in las_gemm_kk_tanhgrad (may be NULL) */
-int las_set_word(int* word, int value, void* stream);
-
-int las_rnn_seq_bwd(int cell, int prec, int B, int T, int H, void* gates,
-                    const float* whh_fw, const float* whh_bw, int ldw,
-                    const void* out, int ld_out, long long out_bstride, const void* cstate,
-                    const void* dout, int ld_dout, long long dout_bstride,
-                    float forget_bias, int flags, int* status, void* ws, size_t ws_bytes, void* stream);
-/* Same, and additionally accumulates (+=) the bias gradients of the two directions, dbias_fw / dbias_bw [G*H] fp32 (either
- * may be NULL) = column sums of d(pre-activation) over all B*T frames (the bias of the TF cell kernel, las/layers.py:31).
- * The cluster BPTT kernel sums them in fp32 registers while it sweeps (before the bf16 rounding of the stored gradient). */
-int las_rnn_seq_bwd_db(int cell, int prec, int B, int T, int H, void* gates,
-                       const float* whh_fw, const float* whh_bw, int ldw,
-                       const void* out, int ld_out, long long out_bstride, const void* cstate,
-                       const void* dout, int ld_dout, long long dout_bstride,
-                       float forget_bias, float* dbias_fw, float* dbias_bw, int flags, int* status,
-                       void* ws, size_t ws_bytes, void* stream);
-/* las_rnn_seq_bwd_db for an upstream gradient `dout` that is still being computed: dout [B, Tp, 2H] is the input gradient of the
- * dense layer above, whose rows are pyramid frame pairs (n_rows = ceil(T/2)) or single frames (n_rows = T); it is filled in chunks
- * of `chunk_rows` (a power of two) of those rows from both ends of the sequence (chunk k = rows [k*c, (k+1)*c) and
- * [n_rows-(k+1)*c, n_rows-k*c) of every utterance), e.g. by las_gemm_kk_frames launches on another stream each followed by
- * las_set_word(chunk_flag, k+1).  The sweep reads a frame of dout only after *chunk_flag has reached the chunk of its row
- * (bounded wait -> LAS_SEQ_STATUS_BWD_TIMEOUT); chunk 0 must be complete in stream order in front of this call and is never waited for.  Only the 8-row K-split cluster kernel supports it (las_rnn_seq_bwd_chunks_ok). */
-int las_rnn_seq_bwd_chunks_ok(int cell, int prec, int B, int H, int flags);
-/* ... and a sweep that PUBLISHES ITS PROGRESS (round 5): d(pre-activation) leaves the sweep with agent-scope (write-through) stores, and every
- * progress_steps sweep steps -- and at the end -- member m of cluster c stores the number of steps whose dZ has reached memory into
- * progress[c * P + m] (las_rnn_seq_bwd_progress_words(...) caller-zeroed ints; 0 = the configuration has no such kernel).  After s steps the
- * forward direction's dZ exists for frames [T - s, T), the backward direction's for [0, s): the layer's weight gradients can follow the sweep
- * window by window on another stream (las_wait_words_min, las_wgrad_ih_hh_window) instead of starting when it ends -- the bottom layer's are
- * the end-of-step tail of the reference's train step (las/las.py:272-283 can only run behind them). */
-int las_rnn_seq_bwd_progress_words(int cell, int prec, int B, int H, int flags);
-/* Which kernel a sweep of (cell, prec, B, H, flags) launches -- the same plan as the launch reads, pure host arithmetic like the *_ok queries
- * above; it exists so that tests can name, and assert, the kernel a case runs (as las_speller_last_variant does for the Speller).  bwd: 0 the
- * forward sweep, 1 BPTT.  mode: what the call asks of its kernel, LAS_SWEEP_MODE_ROWS (las_rnn_seq_fwd_rows), LAS_SWEEP_MODE_CHUNKS
- * (las_rnn_seq_bwd_db_chunked), LAS_SWEEP_MODE_CHUNKS | LAS_SWEEP_MODE_PROGRESS (las_rnn_seq_bwd_db_progress); a mode the planned kernel does
- * not serve leaves the kernel as it is (the calls refuse such a configuration: ask the *_ok queries).  Returns LAS_SWEEP_* and fills (each
- * pointer may be NULL) the cluster width, the batch rows per tile (8 or 16) and the number of row-chunk launches the batch is swept in.
- * LAS_SWEEP_NONE with zeros: the fp32 paths (parity mode, H outside {64, 128, 256, 512}), or no kernel at the picked width or a narrower one. */
+/* Which kernel a sweep of (cell, prec, B, H, flags) launches and what that kernel serves -- the same plan as the launch reads, pure host
+ * arithmetic; callers ask it before they use a mode of las_rnn_seq_args, and tests name, and assert, the kernel a case runs (as
+ * las_speller_last_variant does for the Speller).  bwd: 0 the forward sweep, 1 BPTT.  mode: what the call asks of its kernel,
+ * LAS_SWEEP_MODE_ROWS (row_T set), LAS_SWEEP_MODE_CHUNKS (dout_chunk_flag set), LAS_SWEEP_MODE_CHUNKS | LAS_SWEEP_MODE_PROGRESS (progress
+ * set as well); it only picks `kernel`'s variant, and a mode the planned kernel does not serve leaves the kernel as it is (the calls
+ * refuse such a configuration: read x_chunks / rows / dout_chunks / progress_words first).  LAS_SWEEP_NONE with zeros: the fp32 paths
+ * (parity mode, H outside {64, 128, 256, 512}), or no kernel at the picked width or a narrower one. */
 enum { LAS_SWEEP_NONE = 0,
        LAS_SWEEP_FWD_PLAIN = 1,       /* plain bf16 MFMA forward, 16-row tiles (P = 1, LAS_SEQ_NO_HELPER_WAVES) */
        LAS_SWEEP_FWD_HW16 = 2,        /* helper-wave forward, 16-row tiles */
@@ -279,18 +217,75 @@ enum { LAS_SWEEP_NONE = 0,
        LAS_SWEEP_BWD_KS8_CH = 8,      /* ... waiting for chunks of dout */
        LAS_SWEEP_BWD_KS8_CH_PG = 9 }; /* ... and publishing its progress */
 enum { LAS_SWEEP_MODE_ROWS = 1, LAS_SWEEP_MODE_CHUNKS = 2, LAS_SWEEP_MODE_PROGRESS = 4 };
-int las_rnn_seq_plan_kernel(int cell, int prec, int B, int H, int flags, int bwd, int mode, int* P, int* rows_per_tile, int* launches);
-int las_rnn_seq_bwd_db_progress(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                                const float* whh_bw, int ldw, const void* out, int ld_out, long long out_bstride,
-                                const void* cstate, const void* dout, int ld_dout, long long dout_bstride,
-                                float forget_bias, float* dbias_fw, float* dbias_bw, int flags, int* status,
-                                const int* chunk_flag, int chunk_rows, int n_rows, int* progress, int progress_steps,
-                                void* ws, size_t ws_bytes, void* stream);
-int las_rnn_seq_bwd_db_chunked(int cell, int prec, int B, int T, int H, void* gates, const float* whh_fw,
-                               const float* whh_bw, int ldw, const void* out, int ld_out, long long out_bstride,
-                               const void* cstate, const void* dout, int ld_dout, long long dout_bstride,
-                               float forget_bias, float* dbias_fw, float* dbias_bw, int flags, int* status,
-                               const int* chunk_flag, int chunk_rows, int n_rows, void* ws, size_t ws_bytes, void* stream);
+typedef struct las_rnn_seq_plan_info {
+    int kernel;              /* LAS_SWEEP_* */
+    int P;                   /* cluster width */
+    int rows_per_tile;       /* batch rows per tile (8 or 16) */
+    int launches;            /* row-chunk launches the batch is swept in */
+    int x_chunks;            /* forward: 1 = the kernel waits for x-projection chunks (x_chunk_flag); only the helper-wave kernels do */
+    int rows;                /* forward: 1 = rows of different lengths are served (row_T); only the 8-row helper-wave kernel does */
+    int dout_chunks;         /* BPTT: 1 = the kernel waits for chunks of dout (dout_chunk_flag); only the 8-row K-split cluster kernel does */
+    int progress_words;      /* BPTT: ints `progress` must hold, one per cluster member; 0 = the configuration has no progress-publishing kernel */
+} las_rnn_seq_plan_info;
+int las_rnn_seq_plan(int cell, int prec, int B, int H, int flags, int bwd, int mode, las_rnn_seq_plan_info* out);
+
+/* One sweep: las_rnn_seq_fwd reads the first two groups of fields, las_rnn_seq_bwd the first and the third.  A zero / NULL field switches
+ * its mode off; a field of the other pass's group must be zero / NULL (refused otherwise, as is every combination named below).  The
+ * struct is HOST memory and is read before the call returns. */
+typedef struct las_rnn_seq_args {
+    int cell, prec, B, T, H;
+    void* gates; const float* whh_fw; const float* whh_bw; int ldw;         /* BPTT overwrites gates with d(pre-activation) */
+    void* out; int ld_out; long long out_bstride; void* cstate;             /* written by the forward sweep, read by BPTT */
+    float forget_bias; int flags; int* status;
+    void* ws; size_t ws_bytes;                                              /* las_rnn_seq_workspace_bytes */
+    /* ---- forward only ----
+     * x_chunk_flag: the x-projection is still being computed.  `gates` is filled in time chunks of x_chunk_steps (> 0) sweep steps, chunk
+     * k = frames [k*cs, (k+1)*cs) and [T-(k+1)*cs, T-k*cs) of every utterance (both ends of the sequence first: the forward direction
+     * consumes t = 0, 1, .., the backward direction t = T-1, T-2, ..), e.g. by las_gemm_kk_frames launches on ANOTHER stream, each
+     * followed by las_set_word(x_chunk_flag, k+1).  The sweep reads a frame only after *x_chunk_flag has reached its chunk (bounded wait
+     * -> LAS_SEQ_STATUS_FWD_TIMEOUT).  Chunk 0 must be complete IN STREAM ORDER in front of this call (produced on `stream`, or on a
+     * stream `stream` has waited for): the sweep never waits for it and the value of *x_chunk_flag only matters from 2 on -- no flag
+     * launch is needed between chunk 0's product and the sweep (round 5).  Needs las_rnn_seq_plan's x_chunks; not together with row_T. */
+    const int* x_chunk_flag; int x_chunk_steps;
+    /* row_T: a batch whose rows have DIFFERENT lengths (beam search encodes utterances the reference feeds one at a time, unpadded -- its
+     * encoder has no length mask): row_T [B] device ints, row_T[b] <= T frames of row b.  At frames t >= row_T[b] the row's state and
+     * outputs are forced to ZERO: the backward direction reaches the row's last real frame with the zero state of an unpadded run, the
+     * forward direction's real frames come first, and the zero pad frame is the one the pyramid appends to an odd-length utterance --
+     * every real frame equals the one-utterance-at-a-time result.  Needs las_rnn_seq_plan's rows. */
+    const int* row_T;
+    /* ---- BPTT only ----
+     * dout: gradient w.r.t. out, addressed like out with ld_dout (>= 2H) and dout_bstride. */
+    const void* dout; int ld_dout; long long dout_bstride;
+    /* dbias_fw / dbias_bw (either may be NULL): the sweep additionally accumulates (+=) the bias gradients of the two directions, [G*H]
+     * fp32 = column sums of d(pre-activation) over all B*T frames (the bias of the TF cell kernel, las/layers.py:31).  The cluster BPTT
+     * kernel sums them in fp32 registers while it sweeps (before the bf16 rounding of the stored gradient). */
+    float* dbias_fw; float* dbias_bw;
+    /* dout_chunk_flag: the upstream gradient is still being computed.  dout [B, Tp, 2H] is the input gradient of the dense layer above,
+     * whose rows are pyramid frame pairs (dout_rows = ceil(T/2)) or single frames (dout_rows = T); it is filled in chunks of
+     * dout_chunk_rows (a power of two) of those rows from both ends of the sequence (chunk k = rows [k*c, (k+1)*c) and
+     * [dout_rows-(k+1)*c, dout_rows-k*c) of every utterance), e.g. by las_gemm_kk_frames launches on another stream each followed by
+     * las_set_word(dout_chunk_flag, k+1).  The sweep reads a frame of dout only after *dout_chunk_flag has reached the chunk of its row
+     * (bounded wait -> LAS_SEQ_STATUS_BWD_TIMEOUT); chunk 0 must be complete in stream order in front of this call and is never waited
+     * for.  Needs las_rnn_seq_plan's dout_chunks. */
+    const int* dout_chunk_flag; int dout_chunk_rows, dout_rows;
+    /* progress (with dout_chunk_flag only; round 5): the sweep PUBLISHES ITS PROGRESS.  d(pre-activation) leaves the sweep with
+     * agent-scope (write-through) stores, and every progress_steps (> 0) sweep steps -- and at the end -- member m of cluster c stores the
+     * number of steps whose dZ has reached memory into progress[c * P + m] (las_rnn_seq_plan's progress_words caller-zeroed device ints,
+     * P its cluster width).  After s steps the forward direction's dZ exists for frames [T - s, T), the backward direction's for [0, s):
+     * the layer's weight gradients can follow the sweep window by window on another stream (las_wait_words_min, las_wgrad_ih_hh_window)
+     * instead of starting when it ends -- the bottom layer's are the end-of-step tail of the reference's train step (las/las.py:272-283
+     * can only run behind them). */
+    int* progress; int progress_steps;
+} las_rnn_seq_args;
+int las_rnn_seq_fwd(const las_rnn_seq_args* a, void* stream);
+int las_rnn_seq_bwd(const las_rnn_seq_args* a, void* stream);
+
+/* C = act(A . B^T + bias) like las_gemm_kk, restricted to the frames [lo0, lo0+nlo) and [hi0, hi0+nhi) of every utterance of
+ * [nb, T, *] tensors A and C (row pitches lda / ldc per frame); las_set_word: stream-ordered store of a device word. */
+int las_gemm_kk_frames(int nb, int T, int lo0, int nlo, int hi0, int nhi, int N, int K, const void* A, long long lda,
+                       const void* B, long long ldb, void* C, int c_dtype, long long ldc, const float* bias, int act,
+                       const void* y_tanh, long long ldy, void* stream);       /* y_tanh as in las_gemm_kk_tanhgrad (may be NULL) */
+int las_set_word(int* word, int value, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K4-K7  Speller: the whole decode loop of Speller.__call__ (las/las.py:72-143) with
@@ -483,7 +478,7 @@ int las_wait_word(const int* word, int value, int max_us, void* stream);
 /* ... for the announcement word itself (status[1] of LAS_SEQ_ANNOUNCE): passes once the word HAS REACHED n in the cyclic order of
  * 1..1023 -- also when later sweeps have announced themselves meanwhile (a hold enqueued late must not sit out its bound). */
 int las_wait_announce(const int* word, int n, int max_us, void* stream);
-/* Stream-ordered wait until EVERY one of n device words is >= need (las_rnn_seq_bwd_db_progress' progress words).  Unlike las_wait_announce this
+/* Stream-ordered wait until EVERY one of n device words is >= need (las_rnn_seq_args' progress words).  Unlike las_wait_announce this
  * is a correctness dependency: on a time-out (max_us) `code` is stored into status[0] (may be NULL) -- the step is invalid, las_clip_adam skips it. */
 int las_wait_words_min(const int* words, int n, int need, int max_us, int* status, int code, void* stream);
 /* Diagnostics (round 5): a "foreign" kernel that stays RESIDENT -- n workgroups of 256 threads (workgroup L on XCD L % 8), `lds` bytes of LDS

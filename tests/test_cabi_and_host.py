@@ -45,13 +45,74 @@ def test_library_exports_every_declared_symbol(libpath):
     assert l.las_speller_workspace_bytes(48, 160, 512, 128, 512, 1, 128, 30, 200, 1) > 0
 
 
+def _sweep_args(_hip, **fields):
+    """A las_rnn_seq_args that passes every check of both passes' common part (LSTM, bf16, H = 64, B = 8, T = 4) over fake, 16-byte
+    aligned pointers: a call that is refused dereferences none of them."""
+    a = _hip.RnnSeqArgs(cell=_hip.CELL_LSTM, prec=_hip.PREC_BF16, B=8, T=4, H=64, gates=0x10000, whh_fw=0x20000, whh_bw=0x30000, ldw=256,
+                        out=0x40000, ld_out=128, out_bstride=4 * 128, cstate=0x50000, forget_bias=1.0, ws=0x60000,
+                        ws_bytes=_hip.lib().las_rnn_seq_workspace_bytes(_hip.CELL_LSTM, _hip.PREC_BF16, 64, 8))
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a
+
+
 def test_argument_validation_happens_before_any_launch(libpath):
     from las import _hip
     l = _hip.lib()
     rc = l.las_gemm(7, 0, 0, 4, 4, 4, 1.0, None, 4, 0, None, 4, 0, 0.0, None, 4, 0, None, 0, 1, 0, 0, None, 0, None)
     assert rc < 0 and b"bad prec" in l.las_last_error()
-    rc = l.las_rnn_seq_fwd(1, 0, 0, 4, 8, None, None, None, 8, None, 16, 0, None, 1.0, 0, None, None, 0, None)
+    rc = l.las_rnn_seq_fwd(ctypes.byref(_hip.RnnSeqArgs(cell=1, prec=0, B=0, T=4, H=8, ldw=8, ld_out=16, forget_bias=1.0)), None)
     assert rc < 0 and b"las_rnn_seq_fwd" in l.las_last_error()
+    # One field of the argument struct each, refused by the check it belongs to.  A refusal (< 0) returns in front of the call's first
+    # launch; a launch would give a hipError_t (> 0) without a device, and read the fake pointers with one.
+    dout = dict(dout=0x70000, ld_dout=128, dout_bstride=4 * 128)
+    for fn, fields, msg in (
+            (l.las_rnn_seq_fwd, dict(row_T=0x80000, x_chunk_flag=0x90000, x_chunk_steps=2), b"las_rnn_seq_fwd: row_T and x_chunk_flag"),
+            (l.las_rnn_seq_bwd, dict(dout, progress=0x80000, progress_steps=2), b"las_rnn_seq_bwd: progress needs a chunked upstream gradient"),
+            (l.las_rnn_seq_fwd, dict(dout=0x70000), b"las_rnn_seq_fwd: a BPTT-only field"),
+            (l.las_rnn_seq_bwd, dict(dout, row_T=0x80000), b"las_rnn_seq_bwd: a forward-only field"),
+            (l.las_rnn_seq_bwd, dict(dout, ld_dout=127), b"las_rnn_seq_bwd: bad dout"),
+            (l.las_rnn_seq_bwd, dict(dout, dout_chunk_flag=0x80000, dout_chunk_rows=3, dout_rows=4), b"las_rnn_seq_bwd: bad chunk geometry"),
+            (l.las_rnn_seq_fwd, dict(ws_bytes=_sweep_args(_hip).ws_bytes - 1), b"workspace too small"),
+            (l.las_rnn_seq_bwd, dict(dout, ws_bytes=_sweep_args(_hip).ws_bytes - 1), b"workspace too small")):
+        rc = fn(ctypes.byref(_sweep_args(_hip, **fields)), None)
+        assert rc < 0 and msg in l.las_last_error(), (fields, rc, l.las_last_error())
+    assert l.las_rnn_seq_fwd(None, None) < 0 and b"las_rnn_seq_fwd: null argument struct" in l.las_last_error()
+    assert l.las_rnn_seq_bwd(None, None) < 0 and b"las_rnn_seq_bwd: null argument struct" in l.las_last_error()
+
+
+# include/las_hip.h's argument structs and the ctypes classes las/_hip.py lays out by hand for them
+ABI_STRUCTS = {"las_seq_prepare_desc": "SeqPrepareDesc", "las_rnn_seq_plan_info": "RnnSeqPlanInfo", "las_rnn_seq_args": "RnnSeqArgs",
+               "las_speller_fwd_args": "SpellerFwdArgs", "las_speller_bwd_args": "SpellerBwdArgs", "las_shadow_desc": "ShadowDesc",
+               "las_lstm_cell_args": "LstmCellArgs", "las_beam_loop_args": "BeamLoopArgs", "las_input_config": "InputConfig",
+               "las_input_batch": "InputBatch", "las_frontend_args": "FrontendArgs", "las_resample_args": "ResampleArgs",
+               "las_specaug_args": "SpecAugArgs"}
+
+
+def test_ctypes_structures_have_the_layout_the_compiler_gives_the_header(tmp_path):
+    """LAS_HIP_ABI_VERSION catches a stale library, not a slip in a hand-written _fields_ list: tests/native/abi_layout_main.cpp, built
+    host-only with the Makefile's compiler, prints sizeof of every struct the header declares and offsetof / sizeof of every field, and
+    each line must be what ctypes computes for the matching class (a Python field `in_` is the C field `in`; a nested struct is one
+    field)."""
+    from las import _hip
+    exe = str(tmp_path / "abi_layout")
+    r = subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-host-only", "-O1", "-std=c++17",
+                        os.path.join(ROOT, "tests", "native", "abi_layout_main.cpp"), "-o", exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    sizes, fields = {}, {}
+    for line in subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stdout.splitlines():
+        w = line.split()
+        if w[0] == "struct":
+            sizes[w[1]] = int(w[2])
+        else:
+            fields.setdefault(w[1], []).append((w[2], int(w[3]), int(w[4])))
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "las_hip.h")).read(), flags=re.S)
+    assert sorted(sizes) == sorted(ABI_STRUCTS) == sorted(re.findall(r"^}\s*(las_\w+);", hdr, flags=re.M))    # the program covers the header
+    for cname, pyname in ABI_STRUCTS.items():
+        cls = getattr(_hip, pyname)
+        got = [(n.rstrip("_"), getattr(cls, n).offset, getattr(cls, n).size) for n, *_ in cls._fields_]
+        assert got == fields[cname], (cname, [x for x in zip(got, fields[cname]) if x[0] != x[1]][:3], len(got), len(fields[cname]))
+        assert ctypes.sizeof(cls) == sizes[cname], cname
 
 
 def test_product_path_fails_loudly_without_gpu():

@@ -128,7 +128,7 @@ def test_f32_beam16_lm_at_the_bench_architecture_is_exact():
 
 def test_bf16_utterances_of_different_lengths_one_ragged_encoder_pass_equals_one_encoder_each():
     """decode_batch over utterances of DIFFERENT (odd and even) lengths: the single encoder pass with per-row frame counts
-    (las_rnn_seq_fwd_rows) against one encoder per utterance -- side by side on several streams, and one after the other: hypotheses,
+    (las_rnn_seq_fwd with row_T) against one encoder per utterance -- side by side on several streams, and one after the other: hypotheses,
     scores and alignments must be bit-identical (every real frame of the ragged pass is the frame the utterance gets alone)."""
     args, p0, plm, bs, _ = _setup("bf16")
     utts = [synthetic_batch(1, T_, 8, 30, seed=60 + k)[0] for k, T_ in enumerate((300, 287, 251, 300, 199, 274))]

@@ -190,7 +190,7 @@ def test_weight_shadows_are_rebuilt_by_one_launch_and_match_the_torch_build():
 def test_backward_hand_over_in_chunks_gives_the_same_gradients():
     """Speed-mode Listener backward: between two BPTT sweeps the dX products (recurrent layer's dX with the fused Tanh gradient,
     then the dense layer's dX) run in time chunks from both ends of the sequence, the lower sweep starting after the first chunk
-    (las.layers DOUT_CHUNK_ROWS, las_rnn_seq_bwd_db_chunked).  The parameter gradients must equal those of the whole-GEMM
+    (las.layers DOUT_CHUNK_ROWS, las_rnn_seq_args' dout_chunk_flag).  The parameter gradients must equal those of the whole-GEMM
     schedule: the chain values bit for bit (same tiles per row), the weight gradients up to split-K summation order."""
     from las import _hip, layers as L, variables as V
     B, T, F, H, layers = 8, 1100, 39, 256, 2

@@ -290,7 +290,7 @@ def test_rows16_flag_gives_the_same_sweep(case):
 
 
 def test_chunked_x_projection_is_waited_for():
-    """las_rnn_seq_fwd_chunked: the forward sweep may be launched while its x-projection is still being written in time chunks
+    """las_rnn_seq_fwd with x_chunk_flag: the forward sweep may be launched while its x-projection is still being written in time chunks
     (both ends of the sequence first) by kernels of ANOTHER stream; it must read a frame only after the chunk's flag.  Here the
     chunks are copied in late and slowly (sleep kernels between them) from a second stream; the result has to equal the sweep
     over the complete x-projection bit for bit.  A flag that never arrives must surface as a status error, not as a hang."""
@@ -346,7 +346,7 @@ def test_chunked_x_projection_is_waited_for():
 
 @pytest.mark.parametrize("pairs", [False, True])
 def test_chunked_upstream_gradient_is_waited_for(pairs):
-    """las_rnn_seq_bwd_db_chunked: the BPTT sweep may start while its upstream gradient `dout` is still being written in chunks of
+    """las_rnn_seq_bwd with dout_chunk_flag: the BPTT sweep may start while its upstream gradient `dout` is still being written in chunks of
     producer rows (frames, or frame PAIRS under a pyramid dense layer) from both ends of the sequence by another stream.  Late,
     slow chunks (poison in the frames not yet delivered) must give the same dZ / bias gradients as the sweep over the complete
     dout, bit for bit; a flag that never arrives surfaces as a status error."""
@@ -452,7 +452,7 @@ def test_prepared_workspace_sweeps_equal_self_packing_sweeps(cell, H, B, Bprep):
 
 
 def test_bptt_sweep_that_publishes_its_progress_is_followed_window_by_window():
-    """las_rnn_seq_bwd_db_progress + las_wait_words_min (round 5): the sweep stores d(pre-activation) with agent-scope stores and publishes,
+    """las_rnn_seq_bwd with progress + las_wait_words_min (round 5): the sweep stores d(pre-activation) with agent-scope stores and publishes,
     every `ps` steps, how many steps have reached memory.  (1) dZ and the bias gradients are bit-identical to the chunked sweep without
     progress; (2) a FOLLOWER on another stream, gated by las_wait_words_min, copies the frames each window vouches for WHILE the sweep is
     still running -- forward direction [T - s, T), backward direction [0, s) after s steps: every copy must equal the final dZ (stale or
@@ -546,7 +546,7 @@ def test_wait_announce_passes_for_numbers_that_have_come_and_gone():
 
 @pytest.mark.parametrize("cell", [1, 0])
 def test_forward_sweep_over_rows_of_different_lengths_equals_each_row_alone(cell):
-    """las_rnn_seq_fwd_rows: every real frame of a row (both directions, h and c) is bit-identical to sweeping that row alone at its own
+    """las_rnn_seq_fwd with row_T: every real frame of a row (both directions, h and c) is bit-identical to sweeping that row alone at its own
     length; behind a row's last frame h and c are zero."""
     from las import _hip
     dev = "cuda"
@@ -562,7 +562,7 @@ def test_forward_sweep_over_rows_of_different_lengths_equals_each_row_alone(cell
     out = torch.full((B, T, 2 * H), 7.0, device=dev, dtype=io)
     cst = torch.full((B, T, 2, H), 7.0, device=dev, dtype=io) if cell else None
     if not _hip.rnn_seq_fwd_rows_ok(cell, 1, B, H):
-        # (the tanh cell: no 8-row helper-wave kernel) the contract is "ask las_rnn_seq_fwd_rows_ok": a configuration it does not serve
+        # (the tanh cell: no 8-row helper-wave kernel) the contract is "ask las_rnn_seq_plan's rows": a configuration it does not serve
         # must be REFUSED, not swept as if the rows were of equal length
         with pytest.raises(RuntimeError, match="rows of different lengths"):
             _hip.rnn_seq_fwd(cell, 1, B, T, H, xp.clone(), w0, w1, G * H, out, 2 * H, T * 2 * H, cst, row_T=row_T)

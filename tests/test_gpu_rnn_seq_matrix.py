@@ -1,6 +1,6 @@
 """Every bf16 Listener sweep kernel the plan can reach (csrc/rnn_seq.hip plan_sweep), one table row per (cell, H, P, rows per tile,
 kernel), against the rounded-operand float64 reference of tests/rnn_seq_ref.py at the bounds recorded there.  Each case asks
-las_rnn_seq_plan_kernel which kernel its launch gets and asserts that it is the one the row names BEFORE it launches;
+las_rnn_seq_plan which kernel its launch gets and asserts that it is the one the row names BEFORE it launches;
 tests/test_rnn_seq_ref_host.py checks without a GPU that the tables cover every tuple the plan's grid reaches.
 
 The tables are plain data and this module imports without touching the device."""
@@ -138,7 +138,7 @@ def _assert_planned(case, flags, mode_f=0, mode_b=0):
 
 
 def _sweep(case, flags, rows=None, fwd_kw=None, bwd_kw=None):
-    """las_rnn_seq_fwd, then las_rnn_seq_bwd_db on the same buffers (batch rows `rows` of the case's inputs).  The frame pitch of h and of
+    """las_rnn_seq_fwd, then las_rnn_seq_bwd (with both bias gradients) on the same buffers (batch rows `rows` of the case's inputs).  The frame pitch of h and of
     the upstream gradient leaves one pad frame per row; the bias sums accumulate onto non-zero values.
     -> dict of CPU tensors: h [B, T, 2 H], c [B, T, 2, H], act (saved gates), dz [B, T, 2, G H], db [2][G H] (minus their initial values)"""
     from las import _hip
@@ -323,7 +323,7 @@ def test_chunk_aware_bptt_equals_the_plain_k_split_sweep(case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", [MATRIX[3], MATRIX[33]], ids=lambda c: "-".join(str(x) for x in c[:6]))
 def test_chunked_forward_equals_the_unchunked_one(case):
-    """las_rnn_seq_fwd_chunked outside H = 256 (LSTM H = 128 on 8-row tiles, the tanh cell at H = 512 on 16-row tiles) with every chunk
+    """las_rnn_seq_fwd with x_chunk_flag outside H = 256 (LSTM H = 128 on 8-row tiles, the tanh cell at H = 512 on 16-row tiles) with every chunk
     flagged complete before the launch: the same kernel, the same bits."""
     from las import _hip
     cell, H, B, T = case[:4]

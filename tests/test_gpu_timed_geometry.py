@@ -133,7 +133,7 @@ def test_three_b48_steps_are_bit_reproducible_and_independent_of_the_hand_overs(
         L.PREPARED_SWEEPS = saved_p
     assert l1 == l4 and torch.equal(g1, g4) and torch.equal(f1, f4), "prepared sweep workspaces changed the result"
     # round 5, off by default (no gain, las/layers.py TAIL_WINDOW): the end-of-step tail in windows that FOLLOW the last BPTT sweep
-    # (las_rnn_seq_bwd_db_progress -> las_wait_words_min -> las_wgrad_ih_hh_window on the side stream).  The windows are the arithmetic,
+    # (las_rnn_seq_bwd's progress -> las_wait_words_min -> las_wgrad_ih_hh_window on the side stream).  The windows are the arithmetic,
     # following is the schedule: with the hand-overs off the same window launches run behind the sweep -- bitwise equal; against the
     # one-launch tail the split of the contraction differs (tolerance)
     saved_w = L.TAIL_WINDOW

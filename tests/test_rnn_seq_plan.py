@@ -1,10 +1,10 @@
-"""The Listener sweep's host-side queries, pinned.  las_rnn_seq_fwd_chunks_ok, las_rnn_seq_fwd_rows_ok, las_rnn_seq_bwd_chunks_ok,
-las_rnn_seq_bwd_progress_words and las_rnn_seq_workspace_bytes are pure host arithmetic (no GPU needed) and must describe the kernel
-that the sweep launches: a chunked forward, a ragged forward and a chunked / progress-publishing BPTT are correct only on the kernel
+"""The Listener sweep's host-side queries, pinned.  las_rnn_seq_plan (its x_chunks, rows, dout_chunks and progress_words) and
+las_rnn_seq_workspace_bytes are pure host arithmetic (no GPU needed) and must describe the kernel that the sweep launches: a chunked forward, a ragged forward and a chunked / progress-publishing BPTT are correct only on the kernel
 that honours the mode.  The answers over a grid of precisions, cells, H, B, flags and cluster-width overrides are compared with a
 recorded table (tests/golden/rnn_seq_plan.json).
 
 The table assumes a device of 256 compute units (the MI355X); a host without a GPU reports the same count."""
+import ctypes
 import json
 import os
 
@@ -31,8 +31,11 @@ def grid():
 
 
 def answers(l, prec, cell, H, B, flags):
-    return [int(l.las_rnn_seq_fwd_chunks_ok(cell, prec, B, H, flags)), int(l.las_rnn_seq_fwd_rows_ok(cell, prec, B, H, flags)),
-            int(l.las_rnn_seq_bwd_chunks_ok(cell, prec, B, H, flags)), int(l.las_rnn_seq_bwd_progress_words(cell, prec, B, H, flags))]
+    from las import _hip
+    fwd, bwd = _hip.RnnSeqPlanInfo(), _hip.RnnSeqPlanInfo()
+    assert l.las_rnn_seq_plan(cell, prec, B, H, flags, 0, 0, ctypes.byref(fwd)) == 0
+    assert l.las_rnn_seq_plan(cell, prec, B, H, flags, 1, 0, ctypes.byref(bwd)) == 0
+    return [fwd.x_chunks, fwd.rows, bwd.dout_chunks, bwd.progress_words]
 
 
 def _table():
