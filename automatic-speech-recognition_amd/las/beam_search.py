@@ -317,15 +317,12 @@ class BeamSearch(object):
             ready.record()
             if self._enc_streams is None:
                 self._enc_streams = [torch.cuda.Stream() for _ in range(8)]
-            saved, L.XPROJ_CHUNK_STEPS = L.XPROJ_CHUNK_STEPS, 0
-            try:
+            with L.schedule(XPROJ_CHUNK_STEPS=0):
                 for i, us in enumerate(glist[1:]):
                     s_ = self._enc_streams[i % len(self._enc_streams)]
                     s_.wait_event(ready)
                     with torch.cuda.stream(s_):
                         encode_group(us).record_stream(cur)
-            finally:
-                L.XPROJ_CHUNK_STEPS = saved
             for s_ in self._enc_streams:
                 cur.wait_stream(s_)
         else:

@@ -9,9 +9,13 @@ Two module-level knobs select what the reference cannot express:
     set_cell('rnn'|'lstm')   'rnn' = tf.contrib.rnn.BasicRNNCell, what the reference actually builds
                              (reference las/layers.py:31); 'lstm' = BasicLSTMCell (north-star).
     set_precision('f32'|'bf16')  arithmetic of the contractions (see include/las_hip.h).
-"""
+
+The Listener's train-step schedule and its chunked hand-overs: DESIGN.md, "The Listener's host schedule"."""
+import collections
+import contextlib
 import os
 
+import numpy as np
 import torch
 
 from las import _hip
@@ -38,9 +42,6 @@ def _prec():
     return _hip.PREC_BF16 if _CFG["prec"] == "bf16" else _hip.PREC_F32
 
 
-WGRAD_ONE_PASS = os.environ.get("LAS_WGRAD_ONE_PASS", "1") != "0"
-
-
 def _cellid(cell):
     return _hip.CELL_LSTM if cell == "lstm" else _hip.CELL_RNN
 
@@ -49,9 +50,155 @@ def cell_scope(cell):
     return "basic_lstm_cell" if cell == "lstm" else "basic_rnn_cell"
 
 
-# ------------------------------------------------------------------------------------------------
-# autograd nodes (coarse: one node per layer, not per time step)
-# ------------------------------------------------------------------------------------------------
+# ---- schedule switches: plain module attributes; tests and tools read them, `schedule()` changes them for a while ----
+WGRAD_ONE_PASS = os.environ.get("LAS_WGRAD_ONE_PASS", "1") != "0"     # dW_ih and dW_hh of a direction in one pass over dG (H, GH multiples of 128)
+XPROJ_CHUNK_STEPS = int(os.environ.get("LAS_XPROJ_CHUNK", "64"))     # 0: the whole x-projection before the sweep
+# The dense + tanh in front of a chunked x-projection follows the same chunks up to this many rows (tried: LAS_DENSE_CHUNK=0, the whole
+# product between two sweeps -- 65 us of the forward chain per pyramid level; the whole product stays for more rows and under dropout)
+DENSE_CHUNK_MAX_ROWS = 64
+DOUT_CHUNK_ROWS = int(os.environ.get("LAS_DOUT_CHUNK", "64"))        # backward hand-over in chunks of this many rows (a power of two); 0 = off
+FUSE_TANH_GRAD = not os.environ.get("LAS_NO_FUSE_TANH_GRAD")
+# Round 5, measured and NOT on by default (profiles/r5_tail_follow.txt): the bottom layer's weight gradients in windows that
+# follow the last BPTT sweep hide the 240 us tail launch and cost the sweep what they hide (14.04-14.15 ms per step against 14.05-14.09)
+TAIL_WINDOW = int(os.environ.get("LAS_TAIL_WINDOW", "0"))              # ... contracted in windows of this many sweep steps (0 = the whole sequence at once);
+TAIL_FOLLOW = os.environ.get("LAS_TAIL_FOLLOW", "1") != "0"            # ... that FOLLOW the running BPTT sweep on the side stream (round 5)
+TAIL_WINDOW_WGS = int(os.environ.get("LAS_TAIL_WINDOW_WGS", "192"))    # workgroups of a window that runs beside the sweep (all but the last)
+TAIL_TWO_STREAMS = not os.environ.get("LAS_NO_TAIL_TWO_STREAMS")   # bottom layer's weight gradients without the one-pass product: one direction per auxiliary stream
+HOLD_SIDE = not os.environ.get("LAS_NO_HOLD_SIDE")   # side-stream weight gradients wait for the next sweep to be resident
+PREPARED_SWEEPS = os.environ.get("LAS_NO_PREPARED_SWEEPS") != "1"    # packs + exchange-state clears of a step's sweeps in one launch (las_rnn_seq_prepare)
+_SWITCHES = ("WGRAD_ONE_PASS", "XPROJ_CHUNK_STEPS", "DOUT_CHUNK_ROWS", "FUSE_TANH_GRAD", "TAIL_WINDOW", "TAIL_FOLLOW",
+             "TAIL_WINDOW_WGS", "TAIL_TWO_STREAMS", "HOLD_SIDE", "PREPARED_SWEEPS")
+
+ROW_T = [None]        # inference over a batch of utterances of DIFFERENT lengths: int32 [B] device tensor of the current layer's frames per row
+                      # (set around the listener call by BeamSearch.decode_batch; the pyramid layers halve it) -- las_rnn_seq_args' row_T
+BEFORE_TAIL_HOOK = [None]   # callable(bottom layer's parameters) run right before the end-of-step tail is enqueued (data parallel)
+
+
+@contextlib.contextmanager
+def schedule(**overrides):
+    """Run the enclosed steps with the named switches (`_SWITCHES`) set to these values; the earlier values come back on the way out."""
+    unknown = sorted(set(overrides) - set(_SWITCHES))
+    if unknown:
+        raise ValueError("las.layers.schedule: not a schedule switch: %s (switches: %s)" % (", ".join(unknown), ", ".join(_SWITCHES)))
+    g = globals()
+    saved = {k: g[k] for k in overrides}
+    g.update(overrides)
+    try:
+        yield
+    finally:
+        g.update(saved)
+
+
+@contextlib.contextmanager
+def fallback_schedule(on=True):
+    """The schedule LAS._recover re-runs a lost step on: nothing in it needs workgroups of DIFFERENT launches to be
+    co-resident -- the Speller as per-step launches (LAS_SPELLER_NO_FUSED_STEP), every x-projection and upstream gradient complete in
+    front of its sweep (no chunk hand-overs across streams), no held side stream, sweeps packing for themselves.  The sweeps keep their
+    clusters (2-8 workgroups each on 48-60 of the 256 CUs: they fit beside a neighbour; the hand-overs are what a stalled partner breaks)."""
+    if not on:
+        yield
+        return
+    flags = _hip.speller_flags
+    with schedule(XPROJ_CHUNK_STEPS=0, DOUT_CHUNK_ROWS=0, HOLD_SIDE=False, PREPARED_SWEEPS=False, TAIL_WINDOW=0):
+        _hip.speller_flags = flags | _hip.SPELLER_NO_FUSED_STEP
+        try:
+            yield
+        finally:
+            _hip.speller_flags = flags
+
+
+# ---- chunked hand-overs between the nodes of the pyramid (protocol: DESIGN.md, "The Listener's host schedule") ----
+def _chunk_frames(k, c, T):
+    """Frames of time chunk k (c sweep steps each) of a [*, T, *] tensor that a bidirectional sweep consumes while it is still being produced:
+    (lo0, nlo, hi0, nhi) = the forward direction's frames [lo0, lo0 + nlo) from t = 0 and the backward direction's [hi0, hi0 + nhi) from
+    t = T - 1, the mirror image.  The low ranges end at ceil(T / 2); the middle chunk's high range is clipped at its low range's end, so that
+    over the ceil(ceil(T / 2) / c) chunks every frame is produced exactly once.  The sweep kernels' chunk waits (las_rnn_seq_args x_chunk_steps /
+    dout_chunk_rows) count on exactly this partition: a producer that is off by one frame is a hang, not a wrong number."""
+    th = (T + 1) // 2
+    lo0, lo1 = k * c, min((k + 1) * c, th)
+    hi0, hi1 = max(T - lo1, lo1), T - lo0
+    return lo0, lo1 - lo0, hi0, hi1 - hi0
+
+
+def _chunk_product(k, c, A, Bm, C, nb, T, N, K, lda, ldb, ldc, **kw):
+    """las_gemm_kk over chunk k's frames of every utterance of the [nb, T, *] tensors A and C"""
+    _hip.gemm_kk_frames(A, Bm, C, nb, T, *_chunk_frames(k, c, T), N, K, lda, ldb, ldc, **kw)
+
+
+class _Handover:
+    """A tensor of which only time chunk 0 exists, registered under its data_ptr by its producer for the one node that consumes it:
+    `steps` per chunk, `frames` per utterance, `nchunks` of them; produce(k) enqueues chunk k on the current stream.  Per registry (table in
+    DESIGN.md): `keep_alive` tensors for the consumer's stream, `flag` the word the producer publishes its progress in, `holder` the list
+    that receives the event behind the last chunk, `first` (set by _dense_dx_chunked) the event behind chunk 0 for _rest_on_chain."""
+    __slots__ = ("steps", "frames", "nchunks", "produce", "keep_alive", "flag", "holder", "first")
+
+    def __init__(self, steps, frames, produce, keep_alive=(), flag=None, holder=None):
+        self.steps, self.frames, self.produce, self.keep_alive, self.flag, self.holder = steps, frames, produce, keep_alive, flag, holder
+        self.nchunks = ((frames + 1) // 2 + steps - 1) // steps
+
+    def finish(self):
+        """chunks 1 .. nchunks - 1 on the current stream (a consumer that does not take the chunks finishes the producer first)"""
+        for k in range(1, self.nchunks):
+            self.produce(k)
+
+
+_XCHUNK = {}          # dense + tanh output (forward) -> the recurrent layer above runs produce(k) in front of chunk k of its x-projection
+_DCHUNK = {}          # recurrent layer's dX = dPre (backward) -> the dense node below interleaves produce(k) with its own dX chunks
+_DOUT_CHUNKS = {}     # dense node's dX (backward) -> the BPTT sweep below starts on chunk 0 and calls _rest_on_chain behind its launch
+_TANH_OUT = {}        # data_ptr -> bf16 output of a dense+tanh layer (speed mode): a recurrent layer that reads exactly this tensor
+                      # fuses the Tanh gradient into its dX product (las_gemm_kk_tanhgrad) and hands dPre, not dY, to the dense node
+_DPRE = set()         # data_ptr of gradients that already ARE d(pre-activation) of the dense layer they flow into
+_EXPECT_DPRE = set()  # data_ptr of dense+tanh outputs whose consumer promised to hand back dPre (checked in _Dense16.backward: a
+                      # gradient that arrives there by any other route -- accumulation from a second consumer, a hook, retain_grad --
+                      # would get 1 - y^2 applied twice without this check)
+_PARAMS = {}          # hand-over of the leaf parameter objects to the autograd node being built (same thread, immediate)
+
+
+def _reset_handovers():
+    """Forget every registered hand-over; returns the names of the chunk registries that still held one."""
+    left = [n for n, r in (("_DCHUNK", _DCHUNK), ("_DOUT_CHUNKS", _DOUT_CHUNKS), ("_XCHUNK", _XCHUNK)) if r]
+    for r in (_TANH_OUT, _DPRE, _EXPECT_DPRE, _DCHUNK, _DOUT_CHUNKS, _XCHUNK):
+        r.clear()
+    return left
+
+
+def check_handovers_consumed():
+    """Called when a backward pass is complete (LAS.train): every chunked hand-over registered by a producer must have been
+    taken by its consumer -- a left-over entry means some node read a tensor whose later chunks were never computed."""
+    left = _reset_handovers()
+    if left:
+        raise RuntimeError("las.layers: chunked gradient hand-over left unconsumed (%s): the autograd graph between two recurrent "
+                           "layers is not the pBLSTMLayer stack -- set LAS_DOUT_CHUNK=0 for such graphs" % ", ".join(left))
+
+
+def _direct_ok(p):
+    """True when p is a flattened leaf parameter whose .grad is a view of the flat gradient bucket (accumulated there on a side stream)."""
+    return (p is not None and p.is_leaf and p.requires_grad and p.grad is not None
+            and V.default_store().flat_grad is not None and p.grad.is_contiguous())
+
+
+def _xproj_chunk_steps(B, T, H, cell):
+    """Sweep steps per time chunk of a layer's x-projection hand-over (0: the whole projection before the sweep)."""
+    cs = XPROJ_CHUNK_STEPS
+    if ROW_T[0] is not None:
+        return 0                                     # rows of different lengths (inference): whole x-projection, las_rnn_seq_fwd with row_T
+    return cs if cs and T >= 4 * cs and _hip.rnn_seq_fwd_chunks_ok(_cellid(cell), _hip.PREC_BF16, B, H) else 0
+
+
+# ---- autograd nodes (coarse: one node per layer, not per time step) ----
+def _dense_wgrad_direct(prec, x2d, dpre, Wp, bp, Kw, after=None):
+    """dW += x^T . dPre, db += column sums of dPre, straight into the flat gradient bucket on the side stream: off the chain, overlapping
+    with the next layer's BPTT sweep (which occupies only a few dozen CUs).  after: an event instead of the current stream's tail."""
+    M, K = x2d.shape
+    N = dpre.shape[1]
+    with _hip.on_side_stream(after=after):
+        for t in (x2d, dpre):
+            t.record_stream(_hip.side_stream())
+        _hip.gemm(prec, x2d, dpre, Wp.grad, True, False, Kw, N, M, K, N, N, beta=1.0)
+        if bp is not None:
+            _hip.colsum(dpre, M, N, N, bp.grad, beta=1.0)
+
+
 class _Dense(torch.autograd.Function):
     """tf.layers.dense on the last axis (+ optional tanh): y = act(x.W + b)."""
 
@@ -84,14 +231,7 @@ class _Dense(torch.autograd.Function):
         Wp, bp = ctx.params
         _hip.run_deferred()          # side-stream work queued by the previous node: its host cost lands here, off the chain
         if _direct_ok(Wp) and (bp is None or _direct_ok(bp)):
-            # off the chain: accumulate straight into the flat gradient bucket on the side stream, overlapping
-            # with the next layer's BPTT sweep (which occupies only a few dozen CUs)
-            with _hip.on_side_stream():
-                for t in (x2d, dpre):
-                    t.record_stream(_hip.side_stream())
-                _hip.gemm(ctx.prec, x2d, dpre, Wp.grad, True, False, K, N, M, K, N, N, beta=1.0)
-                if bp is not None:
-                    _hip.colsum(dpre, M, N, N, bp.grad, beta=1.0)
+            _dense_wgrad_direct(ctx.prec, x2d, dpre, Wp, bp, K)
             return dx, None, None, None, None
         dW = torch.empty_like(W)
         _hip.gemm(ctx.prec, x2d, dpre, dW, True, False, K, N, M, K, N, N)
@@ -100,70 +240,6 @@ class _Dense(torch.autograd.Function):
             db = torch.empty(N, device=dy.device, dtype=torch.float32)
             _hip.colsum(dpre, M, N, N, db)
         return dx, dW, db, None, None
-
-
-_TANH_OUT = {}        # data_ptr -> bf16 output of a dense+tanh layer (speed mode): a recurrent layer that reads exactly this tensor
-                      # fuses the Tanh gradient into its dX product (las_gemm_kk_tanhgrad) and hands dPre, not dY, to the dense node
-_DPRE = set()         # data_ptr of gradients that already ARE d(pre-activation) of the dense layer they flow into
-_EXPECT_DPRE = set()  # data_ptr of dense+tanh outputs whose consumer promised to hand back dPre (checked in _Dense16.backward: a
-                      # gradient that arrives there by any other route -- accumulation from a second consumer, a hook, retain_grad --
-                      # would get 1 - y^2 applied twice without this check)
-_DCHUNK = {}          # data_ptr of a dPre whose producer (a recurrent layer's dX product) has only run its first time chunk:
-                      # (chunk rows, rows per utterance, chunks, fn(k), holder) -- the dense node below runs fn(k) interleaved with its
-                      # own chunks and puts the event behind the last one into `holder`
-_DOUT_CHUNKS = {}     # data_ptr of a dense layer's dX that is still being produced in chunks on the chain stream: (flag, chunk rows, rows)
-_XCHUNK = {}          # data_ptr of a dense + tanh output (pBLSTMLayer, forward) of which only the first time chunk exists: (chunk steps,
-                      # frames per utterance, chunks, fn(k), tensors to keep alive on the side stream) -- the recurrent layer that consumes it runs fn(k) in front of chunk k of its
-                      # own x-projection (round 4: the dense product between two sweeps was 65 us of the forward chain per pyramid level)
-_PARAMS = {}          # hand-over of the leaf parameter objects to the autograd node being built (same thread, immediate)
-import os
-ROW_T = [None]        # inference over a batch of utterances of DIFFERENT lengths: int32 [B] device tensor of the current layer's frames per row
-                      # (set around the listener call by BeamSearch.decode_batch; the pyramid layers halve it) -- las_rnn_seq_args' row_T
-XPROJ_CHUNK_STEPS = int(os.environ.get("LAS_XPROJ_CHUNK", "64"))     # 0: the whole x-projection before the sweep
-DENSE_CHUNK_MAX_ROWS = 64
-DENSE_CHUNKS = os.environ.get("LAS_DENSE_CHUNK", "1") != "0"         # the dense + tanh in front of a chunked x-projection follows the same chunks
-DOUT_CHUNK_ROWS = int(os.environ.get("LAS_DOUT_CHUNK", "64"))        # backward hand-over in chunks of this many rows (a power of two); 0 = off
-FUSE_TANH_GRAD = not os.environ.get("LAS_NO_FUSE_TANH_GRAD")
-TAIL_ONE_LAUNCH = os.environ.get("LAS_TAIL_ONE_LAUNCH", "1") != "0"   # bottom layer's weight gradients: both directions in one launch on the launch stream
-# Round 5, measured and NOT on by default (profiles/r5_tail_follow.txt): the bottom layer's weight gradients in windows that follow the last BPTT
-# sweep on the side stream hide the 240 us tail launch -- and cost the sweep as much as they hide (14.04-14.15 ms per step with 3 ... 8
-# windows against 14.05-14.09 with the one launch behind the sweep; with 4-byte agent-scope dZ stores instead of one L2 write-back per
-# publication the sweep itself ran 1.77 -> 2.09 ms: 14.25).  LAS_TAIL_WINDOW=160 switches the windows on.
-TAIL_WINDOW = int(os.environ.get("LAS_TAIL_WINDOW", "0"))              # ... contracted in windows of this many sweep steps (0 = the whole sequence at once);
-TAIL_FOLLOW = os.environ.get("LAS_TAIL_FOLLOW", "1") != "0"            # ... that FOLLOW the running BPTT sweep on the side stream (round 5)
-TAIL_WINDOW_WGS = int(os.environ.get("LAS_TAIL_WINDOW_WGS", "192"))    # workgroups of a window that runs beside the sweep (all but the last)
-TAIL_TWO_STREAMS = not os.environ.get("LAS_NO_TAIL_TWO_STREAMS")   # bottom layer's weight gradients: one direction per auxiliary stream
-HOLD_SIDE = not os.environ.get("LAS_NO_HOLD_SIDE")   # side-stream weight gradients wait for the next sweep to be resident
-BEFORE_TAIL_HOOK = [None]   # callable(bottom layer's parameters) run right before the end-of-step tail is enqueued (data parallel)
-DIRECT_GRADS = True   # weight gradients accumulate into the flat bucket on a side stream (needs a flattened store)
-
-
-def _direct_ok(p):
-    """True when p is a flattened leaf parameter whose .grad is a view of the flat gradient bucket."""
-    return (DIRECT_GRADS and p is not None and p.is_leaf and p.requires_grad and p.grad is not None
-            and V.default_store().flat_grad is not None and p.grad.is_contiguous())
-
-
-def _xproj_chunk_steps(B, T, H, cell):
-    """Sweep steps per time chunk of a layer's x-projection hand-over (0: the whole projection before the sweep)."""
-    cs = XPROJ_CHUNK_STEPS
-    if ROW_T[0] is not None:
-        return 0                                     # rows of different lengths (inference): whole x-projection, las_rnn_seq_fwd with row_T
-    if cs and T >= 4 * cs and _hip.rnn_seq_fwd_chunks_ok(_cellid(cell), _hip.PREC_BF16, B, H):
-        return cs
-    return 0
-
-
-def check_handovers_consumed():
-    """Called when a backward pass is complete (LAS.train): every chunked hand-over registered by a producer must have been
-    taken by its consumer -- a left-over entry means some node read a tensor whose later chunks were never computed."""
-    left = [n for n, r in (("_DCHUNK", _DCHUNK), ("_DOUT_CHUNKS", _DOUT_CHUNKS), ("_XCHUNK", _XCHUNK)) if r]
-    if left:
-        _DCHUNK.clear()
-        _DOUT_CHUNKS.clear()
-        _XCHUNK.clear()
-        raise RuntimeError("las.layers: chunked gradient hand-over left unconsumed (%s): the autograd graph between two recurrent "
-                           "layers is not the pBLSTMLayer stack -- set LAS_DOUT_CHUNK=0 for such graphs" % ", ".join(left))
 
 
 def dense(x, W, b=None, tanh=False, out_f32=True):
@@ -185,6 +261,29 @@ def dense(x, W, b=None, tanh=False, out_f32=True):
     return y.view(*shp[:-1], W.shape[1])
 
 
+def _wgrad_two_products(prec, x_d, ldx, rows_ih, gates, out, gk, d, B, T, Tp, H, GH, I0, beta):
+    """Direction d's kernel gradient gk [(I0 + H), GH] = beta * gk + two products over dG_d (the d-th GH columns of `gates`):
+    dW_ih = x^T . dG_d (contraction over all B*T frames; split-K inside las_gemm; rows_ih rows, those past I0 meet zero operand columns),
+    dW_hh = sum_b sum_t h_prev^T . dG_d: per-utterance products (fw pairs h[t-1] with dG[t], bw pairs h[t+1] with dG[t]), then a
+    fixed-order sum over utterances, which also overwrites what the first product left in rows I0 ..."""
+    _hip.gemm(prec, x_d, gates, gk, True, False, rows_ih, GH, B * T, ldx, 2 * GH, GH, beta=beta, b_off=d * GH)
+    if T > 1:
+        # (`part` is allocated HERE, i.e. on the stream that uses it: a block of the main stream's pool handed to the
+        #  side stream would be recycled by the allocator while the side stream still writes it)
+        part = torch.empty(B, H, GH, device=gates.device)
+        a_off = d * H + (0 if d == 0 else 2 * H)
+        b_off = d * GH + (2 * GH if d == 0 else 0)
+        _hip.gemm(prec, out, gates, part, True, False, H, GH, T - 1, 2 * H, 2 * GH, GH, batch=B,
+                  strideA=Tp * 2 * H, strideB=T * 2 * GH, strideC=H * GH, a_off=a_off, b_off=b_off)
+        _hip.colsum(part, B, H * GH, H * GH, gk[I0:].reshape(-1), beta=beta)
+
+
+def _blstm_grads(dx, dx_bw, gfw=None, gbfw=None, gbw=None, gbbw=None):
+    """What a recurrent node's backward returns for (x, kfw, bfw, kbw, bbw, four settings, x_bw); with the weight gradients already in
+    the flat bucket that is (dx, None, None, None, None, None, None, None, None, dx_bw)."""
+    return (dx, gfw, gbfw, gbw, gbbw, None, None, None, None, dx_bw)
+
+
 class _BLSTM(torch.autograd.Function):
     """One bidirectional recurrent layer: K1 input projection + K2 persistent sweep (+ K2b BPTT).
 
@@ -195,8 +294,7 @@ class _BLSTM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, kfw, bfw, kbw, bbw, cell, prec, H, pad_even, x_bw=None):
         B, T, I = x.shape
-        G = 4 if cell == "lstm" else 1
-        GH = G * H
+        GH = (4 if cell == "lstm" else 1) * H
         dev = x.device
         x = x.contiguous()
         two = x_bw is not None
@@ -204,10 +302,9 @@ class _BLSTM(torch.autograd.Function):
             x_bw = x_bw.contiguous()
         Ik = I
         if I % 4 and (I + 3) // 4 * 4 <= I + H:
-            # MFCC-39: pad the operand with zero columns up to a multiple of 4 so the contraction takes the branch-free
-            # MFMA path (16-byte loads) -- in both precisions since round 5 (the parity mode's exact-fp32 kernels have one too; a zero
-            # times a weight is an exact zero at the end of the fma chain: bit-identical).  The extra weight rows it meets are the first rows of W_hh: multiplied by zeros
-            # here, and given an exactly-zero gradient contribution in backward.
+            # MFCC-39: pad the operand with zero columns up to a multiple of 4 so the contraction takes the branch-free MFMA path (16-byte loads)
+            # -- in both precisions since round 5 (the parity mode's exact-fp32 kernels have one too; a zero times a weight is an exact zero at the
+            # end of the fma chain: bit-identical).  The extra weight rows it meets are the first rows of W_hh: zero contribution here and in backward.
             Ik = (I + 3) // 4 * 4
             x = torch.nn.functional.pad(x, (0, Ik - I))
             if two:
@@ -236,8 +333,7 @@ class _BLSTM(torch.autograd.Function):
         x, kfw, kbw, gates, out, cst, x_bw = ctx.saved_tensors
         cell, prec, H, Tp, I0 = ctx.cfg
         B, T, I = x.shape                              # I = operand width (I0 padded to a multiple of 4 in speed mode)
-        G = 4 if cell == "lstm" else 1
-        GH = G * H
+        GH = (4 if cell == "lstm" else 1) * H
         dev = x.device
         dout = dout.contiguous()
         two = x_bw is not None
@@ -268,18 +364,9 @@ class _BLSTM(torch.autograd.Function):
             def wgrad(d, strm):
                 for t in (x, gates, out) + ((x_bw,) if two else ()):
                     t.record_stream(strm)
-                kp, bp = P4[2 * d], P4[2 * d + 1]
-                gk = kp.grad                       # [(I+H), GH] view of the flat bucket
                 if not db_in_sweep:
-                    _hip.colsum(gates, B * T, GH, 2 * GH, bp.grad, x_off=d * GH, beta=1.0)
-                _hip.gemm(prec, xs[d], gates, gk, True, False, I, GH, B * T, I, 2 * GH, GH, beta=1.0, b_off=d * GH)
-                if T > 1:
-                    part = torch.empty(B, H, GH, device=dev)
-                    a_off = d * H + (0 if d == 0 else 2 * H)
-                    b_off = d * GH + (2 * GH if d == 0 else 0)
-                    _hip.gemm(prec, out, gates, part, True, False, H, GH, T - 1, 2 * H, 2 * GH, GH, batch=B,
-                              strideA=Tp * 2 * H, strideB=T * 2 * GH, strideC=H * GH, a_off=a_off, b_off=b_off)
-                    _hip.colsum(part, B, H * GH, H * GH, gk[I0:].reshape(-1), beta=1.0)
+                    _hip.colsum(gates, B * T, GH, 2 * GH, P4[2 * d + 1].grad, x_off=d * GH, beta=1.0)
+                _wgrad_two_products(prec, xs[d], I, I, gates, out, P4[2 * d].grad, d, B, T, Tp, H, GH, I0, 1.0)
 
             # the bottom layer's weight gradients are the end-of-step tail (nothing left to hide behind): one direction per auxiliary
             # stream, as in the speed mode (its products do not fill the chip alone); the other layers' run on the side stream
@@ -291,29 +378,17 @@ class _BLSTM(torch.autograd.Function):
             if tail2:
                 with _hip.on_chain_stream():
                     wgrad(1, _hip.chain_stream())
-            return (dx, None, None, None, None, None, None, None, None, dx_bw)
+            return _blstm_grads(dx, dx_bw)
         grads = []
-        part = torch.empty(B, H, GH, device=dev) if T > 1 else None
         for d, k in enumerate((kfw, kbw)):
             dk = torch.empty_like(k)
-            # dW_ih = x^T . dG_d        (contraction over all B*T frames; split-K inside las_gemm)
-            _hip.gemm(prec, xs[d], gates, dk, True, False, I, GH, B * T, I, 2 * GH, GH, b_off=d * GH)
-            # dW_hh = sum_b sum_t h_prev^T . dG_d : per-utterance products (fw pairs h[t-1] with dG[t],
-            # bw pairs h[t+1] with dG[t]), then a fixed-order sum over utterances
-            if T > 1:
-                a_off = d * H + (0 if d == 0 else 2 * H)
-                b_off = d * GH + (2 * GH if d == 0 else 0)
-                _hip.gemm(prec, out, gates, part, True, False, H, GH, T - 1, 2 * H, 2 * GH, GH, batch=B,
-                          strideA=Tp * 2 * H, strideB=T * 2 * GH, strideC=H * GH, a_off=a_off, b_off=b_off)
-                whh = torch.empty(H * GH, device=dev)
-                _hip.colsum(part, B, H * GH, H * GH, whh)
-                dk[I0:] = whh.view(H, GH)
-            else:
+            _wgrad_two_products(prec, xs[d], I, I, gates, out, dk, d, B, T, Tp, H, GH, I0, 0.0)
+            if T == 1:
                 dk[I0:] = 0
             db = torch.empty(GH, device=dev)
             _hip.colsum(gates, B * T, GH, 2 * GH, db, x_off=d * GH)
             grads += [dk, db]
-        return (dx, grads[0], grads[1], grads[2], grads[3], None, None, None, None, dx_bw)
+        return _blstm_grads(dx, dx_bw, *grads)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -327,7 +402,6 @@ def _shadow(tag, srcs, rows, transpose, dst_rows, dst_cols, bf16=True):
     op = transpose or identity, [dst_rows, dst_cols], bf16 (or fp32).  Valid until the parameters change (Adam / load / flatten
     clear `store.shadows`).  The first build runs through torch and registers the recipe; afterwards ALL registered shadows are
     rebuilt together by one las_build_shadows launch at the first request after an optimiser step."""
-    import ctypes
     st = V.default_store()
     key = (tag, int(rows), bool(transpose), int(dst_rows), int(dst_cols), bool(bf16)) + tuple(int(q.data_ptr()) for q in srcs)
     sh = st.shadows.get(key)
@@ -368,7 +442,6 @@ def _shadow(tag, srcs, rows, transpose, dst_rows, dst_cols, bf16=True):
     return sh
 
 
-PREPARED_SWEEPS = os.environ.get("LAS_NO_PREPARED_SWEEPS") != "1"
 _STEP_START = [None]  # event on the launch stream at the start of the current train step (begin_step)
 _STEP_ROWS = [0]      # batch rows of the recurrent layer that is being built (the prepared workspaces are laid out for it)
 
@@ -433,82 +506,60 @@ def _prepared_ws(kfw, kbw, cell, H, GH, off, B, bwd):
     return None
 
 
-_CHUNK_FLAGS = {}
+_RING = 32           # hand-over words of a step
+_PROG = 512          # progress words of a BPTT sweep that publishes how far its dZ has reached memory (behind the ring: one fill zeroes both)
+_RINGS = {}
+
+
+class _Ring:
+    """Per device: _RING hand-over + _PROG progress `words`, `next` hand-over word to give out, how many are still `clean` (zero from begin_step's fill), whether the progress words are."""
+    __slots__ = ("words", "next", "clean", "progress_clean")
+
+
+def _flag_ring(dev):
+    # (r4: this used to be `_CHUNK_FLAGS.setdefault(key, [torch.zeros(...), 0, 0])` -- Python evaluates the default on EVERY call, i.e. one
+    #  allocation + one 5-7 us fill kernel per hand-over word, eleven per step, seven of them on the dependency chain)
+    ring = _RINGS.get(str(dev))
+    if ring is None:
+        ring = _RINGS[str(dev)] = _Ring()
+        ring.words, ring.next, ring.clean, ring.progress_clean = torch.zeros(_RING + _PROG, dtype=torch.int32, device=dev), 0, 0, False
+    return ring
 
 
 def _chunk_flag(dev):
     """A zeroed device word for the completion count of one layer's x-projection chunks (a small ring: a word is reused only
     after several later sweeps have been enqueued behind the one that reads it)."""
     ring = _flag_ring(dev)
-    i = ring[1] % _RING
-    ring[1] += 1
-    w = ring[0][i:i + 1]
-    if ring[2] > 0:
-        ring[2] -= 1                                     # zeroed with the whole ring by begin_step
+    i = ring.next % _RING
+    ring.next += 1
+    w = ring.words[i:i + 1]
+    if ring.clean > 0:
+        ring.clean -= 1                                  # zeroed with the whole ring by begin_step
     else:
         VARIANTS["flag_fills"] += 1                      # (a fill on the chain: more hand-overs in one step than the ring holds, or no begin_step)
         w.zero_()
     return w
 
 
-_RING = 32
-_PROG = 512          # progress words of a BPTT sweep that publishes how far its dZ has reached memory (behind the ring: one fill zeroes both)
-
-
 def _progress_words(dev, n):
     """n zeroed device words for las_rnn_seq_args' progress (zeroed with the flag ring by begin_step; by a fill otherwise)"""
     ring = _flag_ring(dev)
-    w = ring[0][_RING:_RING + n]
-    if len(ring) > 3 and ring[3]:
-        ring[3] = False
+    w = ring.words[_RING:_RING + n]
+    if ring.progress_clean:
+        ring.progress_clean = False
     else:
         VARIANTS["flag_fills"] += 1
         w.zero_()
     return w
 
 
-def _flag_ring(dev):
-    # (r4: this used to be `_CHUNK_FLAGS.setdefault(key, [torch.zeros(...), 0, 0])` -- Python evaluates the default on EVERY call, i.e. one
-    #  allocation + one 5-7 us fill kernel per hand-over word, eleven per step, seven of them on the dependency chain)
-    key = str(dev)
-    ring = _CHUNK_FLAGS.get(key)
-    if ring is None:
-        ring = _CHUNK_FLAGS[key] = [torch.zeros(_RING + _PROG, dtype=torch.int32, device=dev), 0, 0, False]
-    return ring
-
-
-# Which schedule variants the current step used (LAS.train copies it into `las.last_variants`): sweeps launched with their x-projection
-# still arriving in chunks (-> rnn_seq_fwd_hw_kernel's chunk waits), BPTT sweeps launched on an upstream gradient still arriving in
-# chunks (-> the rnn_seq_bwd_ks_kernel<..., CH = true> instance), side-stream weight-gradient groups held until the next sweep is
-# resident; "serial": hand-overs that ran with their producers in front of the consumer on one stream (LAS_ALLOW_SERIAL_STREAMS=1 under a
-# tool that serialises kernels -- the same kernel instances, nothing overlapped).  Tests and bench.py assert / print it: the variant
-# that is timed must be the variant that is tested.
+# Which schedule variants the current step used (LAS.train copies it into `las.last_variants`): sweeps launched with their x-projection still
+# arriving in chunks (-> rnn_seq_fwd_hw_kernel's chunk waits), BPTT sweeps launched on an upstream gradient still arriving in chunks (-> the
+# rnn_seq_bwd_ks_kernel<..., CH = true> instance), side-stream weight-gradient groups held until the next sweep is resident; "serial": hand-overs
+# that ran with their producers in front of the consumer on one stream (LAS_ALLOW_SERIAL_STREAMS=1 under a tool that serialises kernels -- the same
+# kernel instances, nothing overlapped).  Tests and bench.py assert / print it: the variant that is timed must be the variant that is tested.
 VARIANTS = {"xproj_chunks": 0, "dense_chunks": 0, "dout_chunks": 0, "hold_side": 0, "sweeps_fwd": 0, "sweeps_bwd": 0, "serial": 0, "flag_fills": 0,
             "prepared_sweeps": 0, "tail_windows": 0, "tail_follow": 0, "prepare_behind_now": 0}     # prepared_sweeps: sweeps that found their pack + clean exchange state ready (las_rnn_seq_prepare; from a model's second step on: all)
-
-
-import contextlib
-
-
-@contextlib.contextmanager
-def fallback_schedule(on=True):
-    """The schedule LAS._recover re-runs a lost step on: nothing in it needs workgroups of DIFFERENT launches (or more workgroups than a
-    busy device can place at once) to be co-resident -- the Speller as per-step launches (LAS_SPELLER_NO_FUSED_STEP: the prefetching rows /
-    the wide path, same arithmetic family as the loop kernels), every x-projection and upstream gradient complete in front of its sweep
-    (no chunk hand-overs across streams), no held side stream, sweeps packing for themselves.  The recurrent sweeps themselves keep
-    their clusters (2-8 workgroups each on 48-60 of the 256 CUs: they fit beside a neighbour; the hand-overs are what a stalled
-    partner stream breaks)."""
-    global XPROJ_CHUNK_STEPS, DOUT_CHUNK_ROWS, HOLD_SIDE, PREPARED_SWEEPS, TAIL_WINDOW
-    if not on:
-        yield
-        return
-    saved = (XPROJ_CHUNK_STEPS, DOUT_CHUNK_ROWS, HOLD_SIDE, PREPARED_SWEEPS, TAIL_WINDOW, _hip.speller_flags)
-    XPROJ_CHUNK_STEPS, DOUT_CHUNK_ROWS, HOLD_SIDE, PREPARED_SWEEPS, TAIL_WINDOW = 0, 0, False, False, 0
-    _hip.speller_flags = _hip.speller_flags | _hip.SPELLER_NO_FUSED_STEP
-    try:
-        yield
-    finally:
-        XPROJ_CHUNK_STEPS, DOUT_CHUNK_ROWS, HOLD_SIDE, PREPARED_SWEEPS, TAIL_WINDOW, _hip.speller_flags = saved
 
 
 def begin_step(dev):
@@ -519,8 +570,8 @@ def begin_step(dev):
     if _prec() == _hip.PREC_BF16:
         _hip.streams_overlap(dev)       # probed (once) HERE: a device whose streams cannot overlap raises before any hand-over state exists
     ring = _flag_ring(dev)
-    ring[0].zero_()
-    ring[1], ring[2], ring[3] = 0, _RING, True
+    ring.words.zero_()
+    ring.next, ring.clean, ring.progress_clean = 0, _RING, True
     ev = torch.cuda.Event()
     ev.record()
     _STEP_START[0] = (ev, V.default_store().weights_epoch)
@@ -539,6 +590,43 @@ def _as_bf16_operand(x):
     return x.contiguous()                                   # (.to() keeps the strides of a transposed view)
 
 
+def _dense_dx_chunked(dpre, Wb, dx, up, M, K, N):
+    """Wavefront hand-over to the BPTT sweep below (the mirror of the chunked x-projection): dPre arrives in time chunks from both ends
+    of the sequence (`up`), this dX product follows chunk by chunk -- chunk 0 here, the others on the chain stream while the sweep already
+    runs -- and publishes its progress in `flag`.  Returns the hand-over it registers."""
+    dev, nb = dpre.device, M // up.frames
+    flag = _chunk_flag(dev)
+
+    def both(k):
+        if k > 0:
+            up.produce(k)
+        _chunk_product(k, up.steps, dpre, Wb, dx, nb, up.frames, K, N, N, N, K)
+        if k > 0:                          # (chunk 0 precedes the consumer sweep in stream order: never waited for)
+            _hip.set_word(flag, k + 1)
+
+    both(0)
+    first = torch.cuda.Event()
+    first.record()
+    rec = _DOUT_CHUNKS[dx.data_ptr()] = _Handover(up.steps, up.frames, both, keep_alive=(dpre, dx, flag) + up.keep_alive, flag=flag, holder=up.holder)
+    rec.first = first
+    return rec
+
+
+def _rest_on_chain(rec):
+    """Chunks 1 .. of the upstream-gradient hand-over `rec`, once: enqueued by the consumer AFTER it has launched its sweep (the host must
+    not spend the 3 launches per chunk in front of that launch), at the latest by the next run_deferred().  (A function of the record, not a
+    closure stored in it: a reference cycle would keep the step's largest tensors alive until the collector runs.)"""
+    if rec.holder:
+        return
+    overlap = _hip.streams_overlap(rec.flag.device)        # (serialised streams: same products, this stream, in front of the consumer)
+    with _hip.on_chain_stream(after=rec.first) if overlap else contextlib.nullcontext():
+        for t in rec.keep_alive if overlap else ():
+            t.record_stream(_hip.chain_stream())
+        rec.finish()
+        rec.holder.append(torch.cuda.Event())      # (the producer above orders its weight gradients behind it)
+        rec.holder[0].record()
+
+
 class _Dense16(torch.autograd.Function):
     """tf.layers.dense (+ tanh) on bf16 activations: y = act(x.W + b), y bf16 or fp32 (`out_f32`)."""
 
@@ -548,22 +636,18 @@ class _Dense16(torch.autograd.Function):
         Kw, N = W.shape
         WT = _shadow("denseT", (W,), Kw, True, N, _k64(Kw))                              # W^T: [N, K64]
         y = torch.empty(M, N, device=x2d.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
+        a = _hip.ACT_TANH if act else _hip.ACT_NONE
         xc = _PARAMS.pop("xchunk", None)              # (cs, B, T): the consumer is a recurrent layer that takes its input in time chunks
         if xc is not None and not out_f32 and xc[1] * xc[2] == M:
             cs, nb, Tq = xc
-            th = (Tq + 1) // 2
-            nch = (th + cs - 1) // cs
-            a = _hip.ACT_TANH if act else _hip.ACT_NONE
 
             def produce(k):
-                lo0, lo1 = k * cs, min((k + 1) * cs, th)
-                hi0, hi1 = max(Tq - lo1, lo1), Tq - lo0
-                _hip.gemm_kk_frames(x2d, WT, y, nb, Tq, lo0, lo1 - lo0, hi0, hi1 - hi0, N, K, K, K, N, bias=b, act=a)
+                _chunk_product(k, cs, x2d, WT, y, nb, Tq, N, K, K, K, N, bias=b, act=a)
 
             produce(0)
-            _XCHUNK[y.data_ptr()] = (cs, Tq, nch, produce, (x2d, WT, y) + ((b,) if b is not None else ()))
+            _XCHUNK[y.data_ptr()] = _Handover(cs, Tq, produce, keep_alive=(x2d, WT, y) + ((b,) if b is not None else ()))
         else:
-            _hip.gemm_kk(x2d, WT, y, M, N, K, K, K, N, bias=b, act=_hip.ACT_TANH if act else _hip.ACT_NONE)
+            _hip.gemm_kk(x2d, WT, y, M, N, K, K, K, N, bias=b, act=a)
         ctx.save_for_backward(x2d, W, y)
         ctx.act, ctx.has_b = act, b is not None
         ctx.params = (_PARAMS.get("W"), _PARAMS.get("b"))
@@ -589,89 +673,36 @@ class _Dense16(torch.autograd.Function):
         else:
             dpre = dy if dy.dtype == torch.bfloat16 else dy.to(torch.bfloat16)
         dx = None
-        ch = _DCHUNK.pop(dy.data_ptr(), None) if dpre is dy else None
-        chain_done = None
-        if ch is not None and not (ctx.needs_input_grad[0] and _k64(N) == N):
-            for k in range(1, ch[2]):                  # no hand-over here: finish the producer's product first (this stream)
-                ch[3](k)
-            ch = None
+        up = _DCHUNK.pop(dy.data_ptr(), None) if dpre is dy else None
+        if up is not None and not (ctx.needs_input_grad[0] and _k64(N) == N):
+            up.finish()                                # no hand-over here: finish the producer's product first (this stream)
+            up = None
+        mine = None                                    # this node's dX handed on in chunks (then: its events order the weight gradients)
         if ctx.needs_input_grad[0]:                    # on the dependency chain: main stream, first
             Wb = _shadow("dense", (W,), Kw, False, K, _k64(N))                           # W, rows padded to K: [K, N64]
             dx = torch.empty(M, K, device=dy.device, dtype=torch.bfloat16)
             Nk = Wb.shape[1]
-            if Nk != N:                                # contraction width padded to 64: pad dpre too (rare: N % 64 != 0)
-                dpre_k = torch.nn.functional.pad(dpre, (0, Nk - N))
-            else:
-                dpre_k = dpre
-            if ch is not None:
-                # Wavefront hand-over to the BPTT sweep below (the mirror of the chunked x-projection): dPre arrives in time
-                # chunks from both ends of the sequence, this product follows chunk by chunk -- chunk 0 here, the others on the
-                # chain stream while the sweep already runs -- and publishes its progress in `flag`.
-                c, Tq, nch, produce, holder = ch
-                nb, th = M // Tq, (Tq + 1) // 2
-                flag = _chunk_flag(dy.device)
-
-                def mine(k):
-                    lo0, lo1 = k * c, min((k + 1) * c, th)
-                    hi0, hi1 = max(Tq - lo1, lo1), Tq - lo0
-                    _hip.gemm_kk_frames(dpre, Wb, dx, nb, Tq, lo0, lo1 - lo0, hi0, hi1 - hi0, K, N, N, N, K)
-                    if k > 0:                          # (chunk 0 precedes the consumer sweep in stream order: never waited for)
-                        _hip.set_word(flag, k + 1)
-
-                mine(0)
-                first = torch.cuda.Event()
-                first.record()
-                chain_done = []
-
-                def rest():
-                    # enqueued by the consumer AFTER it has launched its sweep (the host must not spend the 3 launches per chunk
-                    # in front of that launch); at the latest by the next run_deferred()
-                    if chain_done:
-                        return
-                    if _hip.streams_overlap(dy.device):
-                        with _hip.on_chain_stream(after=first):
-                            for t in (dpre, dx, flag):
-                                t.record_stream(_hip.chain_stream())
-                            for k in range(1, nch):
-                                produce(k)
-                                mine(k)
-                            chain_done.append(torch.cuda.Event())
-                            chain_done[0].record()
-                    else:                              # serialised streams: same products, this stream, in front of the consumer
-                        for k in range(1, nch):
-                            produce(k)
-                            mine(k)
-                        chain_done.append(torch.cuda.Event())
-                        chain_done[0].record()
-                    holder.append(chain_done[0])
-
-                _DOUT_CHUNKS[dx.data_ptr()] = (flag, c, Tq, rest)
-            else:
+            if up is not None:
+                mine = _dense_dx_chunked(dpre, Wb, dx, up, M, K, N)
+            else:                                      # contraction width padded to 64: pad dpre too (rare: N % 64 != 0)
+                dpre_k = torch.nn.functional.pad(dpre, (0, Nk - N)) if Nk != N else dpre
                 _hip.gemm_kk(dpre_k, Wb, dx, M, K, Nk, Nk, Nk, K)
         Wp, bp = ctx.params
-        if chain_done is None:
+        if mine is None:
             _hip.run_deferred()                        # (else: the consumer sweep's node runs them, after its launch)
         Kg = (Kw + 3) // 4 * 4                         # rows of the weight gradient the TN product writes (zero operand columns beyond Kw)
         if _direct_ok(Wp) and (bp is None or _direct_ok(bp)) and Kg == Kw:
-            def wgrad(after=None):
-                with _hip.on_side_stream(after=after):
-                    for t in (x2d, dpre):
-                        t.record_stream(_hip.side_stream())
-                    _hip.gemm(_hip.PREC_BF16, x2d, dpre, Wp.grad, True, False, Kw, N, M, K, N, N, beta=1.0)
-                    if bp is not None:
-                        _hip.colsum(dpre, M, N, N, bp.grad, beta=1.0)
-
-            if chain_done is None:
-                wgrad()
+            if mine is None:
+                _dense_wgrad_direct(_hip.PREC_BF16, x2d, dpre, Wp, bp, Kw)
             else:
                 def later():
-                    rest()
-                    wgrad(chain_done[0])           # all of dPre
+                    _rest_on_chain(mine)
+                    _dense_wgrad_direct(_hip.PREC_BF16, x2d, dpre, Wp, bp, Kw, after=mine.holder[0])      # all of dPre
                 _hip.defer_side(later)
             return dx, None, None, None, None
-        if chain_done is not None:
-            rest()
-            torch.cuda.current_stream().wait_event(chain_done[0])
+        if mine is not None:
+            _rest_on_chain(mine)
+            torch.cuda.current_stream().wait_event(mine.holder[0])
         dW = torch.zeros(Kg, N, device=dy.device)
         _hip.gemm(_hip.PREC_BF16, x2d, dpre, dW, True, False, Kg, N, M, K, N, N)
         db = None
@@ -681,6 +712,199 @@ class _Dense16(torch.autograd.Function):
         return dx, dW[:Kw], db, None, None
 
 
+# ---- _BLSTM16's phases: each function takes what it reads; the ORDER of their host calls is the schedule ----
+_Node16 = collections.namedtuple("_Node16", "x x_bw kfw kbw gates out cst cell B T Tp H GH Ik I0 P4 direct one_pass")   # what the backward phases read
+
+
+def _xproj16(x, WT, bias, gates, B, T, H, GH, cell):
+    """Forward x-projection of both directions.  Returns (chunk_flag, cs, rest_chunks): the word the chunks' completion is published in
+    and the steps per chunk (None, 0: the whole product is enqueued), and what enqueues chunks 1 .. on the side stream BEHIND the sweep's launch."""
+    dev, Ik = x.device, x.shape[2]
+    cs = _xproj_chunk_steps(B, T, H, cell)
+    xc = _XCHUNK.pop(x.data_ptr(), None)         # the dense + tanh below has only produced its first time chunk
+    if xc is not None and (xc.steps != cs or xc.frames != T):
+        xc.finish()                              # not the chunks this layer takes: finish the producer first
+        xc = None
+    if not cs:
+        _hip.gemm_kk(x, WT, gates, B * T, 2 * GH, Ik, Ik, Ik, 2 * GH, bias=bias)
+        return None, 0, None
+    # Only the first chunk of frames -- both ends of the sequence -- has to exist when the sweep starts: chunk 0 on this stream, the others on the
+    # side stream WHILE the sweep runs (it holds a fifth of the CUs); its helper waves wait for a chunk's completion flag before they read its frames.
+    chunk_flag = _chunk_flag(dev)
+
+    def chunk(k):
+        if xc is not None and k > 0:
+            xc.produce(k)                        # the input frames of this chunk (dense + tanh of the layer below)
+        _chunk_product(k, cs, x, WT, gates, B, T, 2 * GH, Ik, Ik, Ik, 2 * GH, bias=bias)
+        if k > 0:                                # (chunk 0 precedes the sweep in stream order: the sweep never waits for it)
+            _hip.set_word(chunk_flag, k + 1)
+
+    chunk(0)
+    mine = _Handover(cs, T, chunk, flag=chunk_flag)      # (never registered: its consumer is this node's own sweep)
+    VARIANTS["dense_chunks"] += int(xc is not None)
+    if not _hip.streams_overlap(dev):
+        # serialised streams (LAS_ALLOW_SERIAL_STREAMS=1, counter passes): the SAME kernel instances, every producer in front of its consumer on this stream
+        VARIANTS["serial"] += 1
+        mine.finish()
+        return chunk_flag, cs, None
+    # Round 5: the SWEEP is launched right behind chunk 0 and the other chunks are enqueued behind its launch, on the side
+    # stream, ordered after chunk 0 by an event (r4 timeline: the host needed 0.36 ms to enqueue the 18 launches of layer 0's
+    # nine chunks in front of the sweep's launch -- the first sweep of a step started 547 us into it)
+    chunk0_done = torch.cuda.Event()
+    chunk0_done.record()
+
+    def rest_chunks(pad=None):
+        with _hip.on_side_stream(after=chunk0_done):
+            side = _hip.side_stream()
+            for t in (x, gates, chunk_flag) + (xc.keep_alive if xc is not None else ()) + (() if pad is None else (pad,)):
+                t.record_stream(side)
+            if pad is not None:
+                pad.zero_()              # the zero frame behind an odd T (nobody reads it before the join below)
+            mine.finish()
+
+    return chunk_flag, cs, rest_chunks
+
+
+def _upstream_handover(n, dout):
+    """dout's hand-over, when the dense node above still produces it in chunks; one this sweep cannot take is finished first."""
+    dc = _DOUT_CHUNKS.pop(dout.data_ptr(), None)
+    if dc is not None and not (dc.frames in (n.T, (n.T + 1) // 2) and _hip.rnn_seq_bwd_chunks_ok(_cellid(n.cell), _hip.PREC_BF16, n.B, n.H)):
+        _rest_on_chain(dc)
+        _hip.join_chain_stream()
+        dc = None
+    return dc
+
+
+def _bptt_sweep16(n, dout, dc, windows):
+    """The BPTT sweep -- gates: activated gates -> d(pre-activation) (bf16), in place; the bias gradients accumulate in fp32 -- on a
+    complete dout or behind chunk 0 of dc, whose other chunks are enqueued BEHIND the launch.  windows: the tail will contract in
+    windows; returns (progress words, their number, event in front of the sweep) when the sweep publishes its progress for them."""
+    dev, cid = n.x.device, _cellid(n.cell)
+    VARIANTS["sweeps_bwd"] += 1
+    VARIANTS["dout_chunks"] += int(dc is not None)
+    serial = dc is not None and not _hip.streams_overlap(dev)
+    if serial:
+        VARIANTS["serial"] += 1
+        _rest_on_chain(dc)               # serialised streams: every chunk in front of the (same, chunk-aware) sweep
+    follow = None
+    if windows and TAIL_FOLLOW and dc is not None and not serial:
+        nprog = _hip.rnn_seq_bwd_progress_words(cid, _hip.PREC_BF16, n.B, n.H)
+        if 0 < nprog <= _PROG:
+            follow = (_progress_words(dev, nprog), nprog, torch.cuda.Event())
+            follow[2].record()
+    _hip.rnn_seq_bwd(cid, _hip.PREC_BF16, n.B, n.T, n.H, n.gates, n.kfw, n.kbw, n.GH, n.out, 2 * n.H, n.Tp * 2 * n.H, n.cst,
+                     dout, 2 * n.H, n.Tp * 2 * n.H, 1.0, wf_off=n.I0 * n.GH, wb_off=n.I0 * n.GH,
+                     db_fw=n.P4[1].grad if n.direct else None, db_bw=n.P4[3].grad if n.direct else None,
+                     chunk_flag=None if dc is None else dc.flag, chunk_rows=0 if dc is None else dc.steps,
+                     n_rows=0 if dc is None else dc.frames, prepared_ws=_prepared_ws(n.kfw, n.kbw, n.cell, n.H, n.GH, n.I0 * n.GH, n.B, True),
+                     progress=None if follow is None else follow[0], progress_steps=TAIL_WINDOW)
+    if dc is not None and not serial:
+        _rest_on_chain(dc)               # the other chunks: chain stream, enqueued behind the sweep's launch
+        _hip.join_chain_stream()         # (they are finished when the sweep is; this orders later readers of dout)
+    return follow
+
+
+def _dx16(n, need_dx, need_dx_bw, x_is_tanh, in_pyramid):
+    """The input gradient(s): on the dependency chain, main stream, first.  Returns (dx, dx_bw, handed): handed = (event behind chunk 0,
+    list that receives the event behind the last chunk) when dX leaves as a chunked hand-over to the dense node below."""
+    B, T, Ik, GH, dev, bf = n.B, n.T, n.Ik, n.GH, n.x.device, torch.bfloat16
+    if need_dx and n.x_bw is None:
+        # dX [B*T, Ik] = dZ [B*T, 2GH] . [W_ih_fw | W_ih_bw]^T : B operand = shadow of the concatenated weights [Ik, 2GH]
+        Wb = _shadow("ih", (n.kfw, n.kbw), n.I0, False, Ik, 2 * GH)                           # rows padded to Ik: [Ik, 2GH]
+        dx = torch.empty(B, T, Ik, device=dev, dtype=bf)
+        c = DOUT_CHUNK_ROWS
+        if x_is_tanh and in_pyramid and c and T >= 4 * c and n.direct and _hip.rnn_seq_bwd_chunks_ok(_cellid(n.cell), _hip.PREC_BF16, B, n.H):
+            # first time chunk only; the dense node below (the consumer of this dPre) interleaves the others with its own.  (Only inside pBLSTMLayer's stack, where
+            # that dense node's input gradient goes to the recurrent layer below and nowhere else: a consumer that does not know about the chunks would read an unfinished tensor.)
+            def produce(k):
+                _chunk_product(k, c, n.gates, Wb, dx, B, T, Ik, 2 * GH, 2 * GH, 2 * GH, Ik, tanh_y=n.x, ldy=Ik)
+
+            produce(0)
+            handed = (torch.cuda.Event(), [])
+            _DCHUNK[dx.data_ptr()] = _Handover(c, T, produce, keep_alive=(n.gates, n.x, dx), holder=handed[1])
+            _DPRE.add(dx.data_ptr())
+            handed[0].record()
+            return dx, None, handed
+        _hip.gemm_kk(n.gates, Wb, dx, B * T, Ik, 2 * GH, 2 * GH, 2 * GH, Ik, tanh_y=n.x if x_is_tanh else None, ldy=Ik if x_is_tanh else 0)
+        if x_is_tanh:
+            _DPRE.add(dx.data_ptr())
+        return dx, None, None
+    if n.x_bw is not None and (need_dx or need_dx_bw):
+        dx, dx_bw = torch.empty(B, T, Ik, device=dev, dtype=bf), torch.empty(B, T, Ik, device=dev, dtype=bf)
+        for d, (dxd, k) in enumerate(((dx, n.kfw), (dx_bw, n.kbw))):
+            Wd = _shadow("ih%d" % d, (k,), n.I0, False, Ik, GH)
+            _hip.gemm_kk(n.gates, Wd, dxd, B * T, Ik, GH, 2 * GH, GH, Ik, a_off=d * GH)
+        return dx, dx_bw, None
+    return None, None, None
+
+
+def _wgrad16(n, d, gk):
+    """gk += direction d's dW_ih and dW_hh"""
+    x_d = n.x if d == 0 or n.x_bw is None else n.x_bw
+    if n.one_pass:        # one pass over dG_d for both (round 4): the left operand is [x | h_prev] with h_prev read from `out` one frame back
+        _hip.wgrad_ih_hh(x_d, n.Ik, n.I0, n.out, 2 * n.H, n.Tp * 2 * n.H, n.gates, 2 * n.GH, n.B, n.T, n.H, n.GH, d, gk)
+    else:                 # dW_ih in (I0 + 3) // 4 * 4 rows: those past I0 meet zero operand columns (exact zeros)
+        _wgrad_two_products(_hip.PREC_BF16, x_d, n.Ik, (n.I0 + 3) // 4 * 4, n.gates, n.out, gk, d, n.B, n.T, n.Tp, n.H, n.GH, n.I0, 1.0)
+
+
+def _wgrads16_side(n, hold, handed=None):
+    """Both directions' weight gradients on the side stream: behind the dX hand-over `handed`, held for the next sweep, or right away."""
+    after, chain_done = handed if handed is not None else (None, None)
+    with _hip.on_side_stream(after=after):
+        side = _hip.side_stream()
+        for t in (n.x, n.gates, n.out) + (() if n.x_bw is None else (n.x_bw,)):
+            t.record_stream(side)
+        if after is not None:
+            # hand-over in chunks: these GEMMs would compete with the chain-stream chunks the next sweep waits for -- they start behind the last one
+            if chain_done:
+                side.wait_event(chain_done[0])
+        elif hold:
+            VARIANTS["hold_side"] += 1
+            # keep the side stream (these GEMMs and whatever is queued behind them) off the machine until the NEXT BPTT sweep is resident: they
+            # would delay its start (it needs whole CUs) and slow the chain GEMMs in front of it; bounded wait, scheduling only
+            _hip.hold_until_next_sweep(n.x.device)
+        for d in range(2):
+            _wgrad16(n, d, n.P4[2 * d].grad)
+
+
+def _wgrads16_tail(n, windows, follow):
+    """The bottom layer's weight gradients = the end-of-step tail, nothing left to hide behind.  Three forms:
+    one launch -- both directions on THIS stream (round 4; tried: one direction per auxiliary stream with the one-pass product, LAS_TAIL_ONE_LAUNCH=0
+        -- an event hand-over to another queue in front of it and behind it, 28 + 67 us of the 347 us tail);
+    two streams -- without the one-pass product: the two directions' products on two streams (a single one does not fill the chip);
+    windows -- of TAIL_WINDOW sweep steps (the forward direction's frames from the end of the sequence, the backward direction's from its start: the
+        order in which the sweep produces dZ), each on the side stream as soon as the sweep has passed it when it publishes its progress (`follow`),
+        else all behind the sweep.  The windows are the ARITHMETIC (fixed by T and TAIL_WINDOW), following the sweep only the schedule.  No gain; tested."""
+    x, gates, out, P4, B, T, H, GH = n.x, n.gates, n.out, n.P4, n.B, n.T, n.H, n.GH
+    if BEFORE_TAIL_HOOK[0] is not None:
+        # data parallel: every gradient but this layer's is final once the work queued so far has run -- the
+        # all-reduce of that part of the bucket starts now, under the tail (las.las.LAS.train)
+        BEFORE_TAIL_HOOK[0](P4)
+    if windows:
+        S = TAIL_WINDOW
+        nwin = (T + S - 1) // S
+        VARIANTS["tail_windows"] += nwin
+        VARIANTS["tail_follow"] += int(follow is not None)
+        prog, nprog, before_sweep = follow if follow is not None else (None, 0, None)
+        with _hip.on_side_stream(after=before_sweep) if follow is not None else contextlib.nullcontext():
+            for t in (x, gates, out, prog) if follow is not None else ():
+                t.record_stream(_hip.side_stream())
+            for c in range(nwin):
+                lo, nfr = c * S, min(S, T - c * S)
+                if follow is not None:
+                    _hip.wait_words_min(prog, nprog, min((c + 1) * S, T))
+                _hip.wgrad_ih_hh_window(x, n.Ik, n.I0, out, 2 * H, n.Tp * 2 * H, gates, 2 * GH, B, T, H, GH, 2, T - lo - nfr, lo, nfr,
+                                        TAIL_WINDOW_WGS if c + 1 < nwin else 0, P4[0].grad, P4[2].grad, None)
+    elif n.one_pass:
+        _hip.wgrad_ih_hh(x, n.Ik, n.I0, out, 2 * H, n.Tp * 2 * H, gates, 2 * GH, B, T, H, GH, 2, P4[0].grad, P4[2].grad, None)
+    else:
+        for d, on_stream, strm in ((0, _hip.on_side_stream, _hip.side_stream), (1, _hip.on_chain_stream, _hip.chain_stream)):
+            with on_stream():
+                for t in (x, gates, out):
+                    t.record_stream(strm())
+                _wgrad16(n, d, P4[2 * d].grad)
+
+
 class _BLSTM16(torch.autograd.Function):
     """One bidirectional recurrent layer with bf16 activation storage: K1 x-projection (las_gemm_kk) + K2 sweep + K2b BPTT.
     x: bf16 [B,T,Ik] (Ik = input width padded to a multiple of 64 with zero columns); I0 = true input width."""
@@ -688,17 +912,14 @@ class _BLSTM16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, kfw, bfw, kbw, bbw, cell, H, pad_even, I0, x_bw=None):
         B, T, Ik = x.shape
-        G = 4 if cell == "lstm" else 1
-        GH = G * H
-        dev = x.device
-        prec = _hip.PREC_BF16
+        GH = (4 if cell == "lstm" else 1) * H
+        dev, prec, bf = x.device, _hip.PREC_BF16, torch.bfloat16
         x = x.contiguous()
         two = x_bw is not None
         if two:
             x_bw = x_bw.contiguous()
-        bf = torch.bfloat16
         gates = torch.empty(B, T, 2, GH, device=dev, dtype=bf)
-        rest_chunks = None
+        chunk_flag, cs, rest_chunks = None, 0, None
         training = any(ctx.needs_input_grad) and ROW_T[0] is None      # (grad mode itself is off inside an autograd node's forward)
         if training:
             _STEP_ROWS[0] = B                        # (the first shadow request after an optimiser step prepares every sweep of the step for B rows)
@@ -706,56 +927,7 @@ class _BLSTM16(torch.autograd.Function):
             # both directions in ONE product over the concatenated weights: B operand = shadow of [W_ih_fw | W_ih_bw]^T
             WT = _shadow("ihT", (kfw, kbw), I0, True, 2 * GH, _k64(I0))                     # [W_ih_fw | W_ih_bw]^T: [2GH, Ik]
             bias = _shadow("ihb", (bfw, bbw), 1, False, 1, 2 * GH, bf16=False).view(-1)
-            chunk_flag, cs = None, _xproj_chunk_steps(B, T, H, cell)
-            xc = _XCHUNK.pop(x.data_ptr(), None)         # the dense + tanh below has only produced its first time chunk
-            if xc is not None and (xc[0] != cs or xc[1] != T):
-                for k in range(1, xc[2]):                # not the chunks this layer takes: finish the producer first
-                    xc[3](k)
-                xc = None
-            if cs:
-                # The sweep consumes the x-projection in time order (forward direction from t = 0, backward from t = T - 1), so only
-                # the first chunk of frames -- both ends of the sequence -- has to exist when it starts: chunk 0 on this stream,
-                # the others on the side stream WHILE the sweep runs (it holds a fifth of the CUs); the sweep's helper waves wait
-                # for a chunk's completion flag before they read its frames.
-                th = (T + 1) // 2
-                nch = (th + cs - 1) // cs
-                chunk_flag = _chunk_flag(dev)
-
-                def chunk(k):
-                    if xc is not None and k > 0:
-                        xc[3](k)                         # the input frames of this chunk (dense + tanh of the layer below)
-                    lo0, lo1 = k * cs, min((k + 1) * cs, th)
-                    hi0, hi1 = max(T - lo1, lo1), T - lo0
-                    _hip.gemm_kk_frames(x, WT, gates, B, T, lo0, lo1 - lo0, hi0, hi1 - hi0, 2 * GH, Ik, Ik, Ik, 2 * GH, bias=bias)
-                    if k > 0:                            # (chunk 0 precedes the sweep in stream order: the sweep never waits for it)
-                        _hip.set_word(chunk_flag, k + 1)
-
-                chunk(0)
-                VARIANTS["dense_chunks"] += int(xc is not None)
-                if _hip.streams_overlap(dev):
-                    # Round 5: the SWEEP is launched right behind chunk 0 and the other chunks are enqueued behind its launch, on the side
-                    # stream, ordered after chunk 0 by an event (r4 timeline: the host needed 0.36 ms to enqueue the 18 launches of layer 0's
-                    # nine chunks in front of the sweep's launch -- the first sweep of a step started 547 us into it)
-                    chunk0_done = torch.cuda.Event()
-                    chunk0_done.record()
-
-                    def rest_chunks(pad=None):
-                        with _hip.on_side_stream(after=chunk0_done):
-                            side = _hip.side_stream()
-                            for t in (x, gates, chunk_flag) + (xc[4] if xc is not None else ()) + (() if pad is None else (pad,)):
-                                t.record_stream(side)
-                            if pad is not None:
-                                pad.zero_()              # the zero frame behind an odd T (nobody reads it before the join below)
-                            for k in range(1, nch):
-                                chunk(k)
-                else:
-                    # serialised streams (LAS_ALLOW_SERIAL_STREAMS=1, counter passes): the SAME kernel instances -- chunk products and
-                    # the chunk-aware sweep -- with every producer in front of its consumer on this stream
-                    VARIANTS["serial"] += 1
-                    for k in range(1, nch):
-                        chunk(k)
-            else:
-                _hip.gemm_kk(x, WT, gates, B * T, 2 * GH, Ik, Ik, Ik, 2 * GH, bias=bias)
+            chunk_flag, cs, rest_chunks = _xproj16(x, WT, bias, gates, B, T, H, GH, cell)
         else:
             for d, (xd, k, b) in enumerate(((x, kfw, bfw), (x_bw, kbw, bbw))):
                 WTd = _shadow("ihT%d" % d, (k,), I0, True, GH, _k64(I0))                    # [GH, Ik]
@@ -767,16 +939,16 @@ class _BLSTM16(torch.autograd.Function):
         if row_T is not None and (two or torch.is_grad_enabled() or not _hip.rnn_seq_fwd_rows_ok(_cellid(cell), prec, B, H)):
             raise RuntimeError("rows of different lengths (layers.ROW_T) are an inference-only path of the 8-row speed-mode sweep")
         VARIANTS["sweeps_fwd"] += 1
-        VARIANTS["xproj_chunks"] += int(not two and chunk_flag is not None)
+        VARIANTS["xproj_chunks"] += int(chunk_flag is not None)
         _hip.rnn_seq_fwd(_cellid(cell), prec, B, T, H, gates, kfw, kbw, GH, out, 2 * H, Tp * 2 * H, cst,
-                         1.0, wf_off=I0 * GH, wb_off=I0 * GH, chunk_flag=None if two else chunk_flag, chunk_steps=0 if two else cs,
+                         1.0, wf_off=I0 * GH, wb_off=I0 * GH, chunk_flag=chunk_flag, chunk_steps=cs,
                          row_T=row_T, prepared_ws=_prepared_ws(kfw, kbw, cell, H, GH, I0 * GH, B, False) if training else None)
         if rest_chunks is not None:
             # chunks 1 .. of the x-projection: side stream, enqueued behind the sweep's launch (with the pad frame's fill, off the chain)
             rest_chunks(out[:, T:] if Tp != T else None)
         elif Tp != T:
             out[:, T:].zero_()               # only the pad frame (the sweep writes every real frame, and never this one)
-        if not two and chunk_flag is not None:
+        if chunk_flag is not None:
             _hip.join_side_stream()          # (the chunks are long finished; this orders later users of `gates` after them)
         ctx.save_for_backward(x, kfw, kbw, gates, out, cst, x_bw)
         ctx.cfg = (cell, H, Tp, I0)
@@ -794,196 +966,37 @@ class _BLSTM16(torch.autograd.Function):
         x, kfw, kbw, gates, out, cst, x_bw = ctx.saved_tensors
         cell, H, Tp, I0 = ctx.cfg
         B, T, Ik = x.shape
-        G = 4 if cell == "lstm" else 1
-        GH = G * H
-        dev = x.device
-        prec = _hip.PREC_BF16
-        bf = torch.bfloat16
+        GH = (4 if cell == "lstm" else 1) * H
         dout = dout.contiguous()
-        two = x_bw is not None
-        xs = (x, x_bw if two else x)
         P4 = ctx.params
-        direct = P4 is not None and all(_direct_ok(p) for p in P4)
-        produced = None
-        dc = _DOUT_CHUNKS.pop(dout.data_ptr(), None)       # dout still arrives in chunks (the dense node above, chain stream)
-        if dc is not None and not (dc[2] in (T, (T + 1) // 2) and _hip.rnn_seq_bwd_chunks_ok(_cellid(cell), prec, B, H)):
-            dc[3]()
-            _hip.join_chain_stream()
-            dc = None
-        VARIANTS["sweeps_bwd"] += 1
-        VARIANTS["dout_chunks"] += int(dc is not None)
-        serial = dc is not None and not _hip.streams_overlap(dev)
-        if serial:
-            VARIANTS["serial"] += 1
-            dc[3]()                          # serialised streams: every chunk in front of the (same, chunk-aware) sweep
-        # Round 5, the end-of-step tail: the bottom layer's weight gradients are contracted in WINDOWS of TAIL_WINDOW sweep steps (the
-        # forward direction's frames from the end of the sequence, the backward direction's from its start: the order in which the sweep
-        # produces dZ), and -- when the sweep can publish its progress -- each window runs on the side stream as soon as the sweep has
-        # passed it, instead of all of them behind the sweep (a 240 us launch at the bench geometry).  The windows are the ARITHMETIC
-        # (fixed by T and TAIL_WINDOW); following the sweep is only the schedule: without it the same launches run behind the sweep.
-        one_pass_ = WGRAD_ONE_PASS and T > 1 and H % 128 == 0 and GH % 128 == 0 and B * T < (1 << 24) and out.dtype == bf and x.dtype == bf
-        is_tail = (P4 is not None and all(_direct_ok(p) for p in P4) and not ctx.needs_input_grad[0] and not two and one_pass_ and TAIL_ONE_LAUNCH)
-        windows = is_tail and TAIL_WINDOW > 0 and T >= 3 * TAIL_WINDOW
-        follow, prog, nprog = False, None, 0
-        if windows and TAIL_FOLLOW and dc is not None and not serial:
-            nprog = _hip.rnn_seq_bwd_progress_words(_cellid(cell), prec, B, H)
-            if 0 < nprog <= _PROG:
-                follow, prog = True, _progress_words(dev, nprog)
-                before_sweep = torch.cuda.Event()
-                before_sweep.record()
-        # gates: activated gates -> d(pre-activation) (bf16), in place; the sweep accumulates the bias gradients in fp32
-        _hip.rnn_seq_bwd(_cellid(cell), prec, B, T, H, gates, kfw, kbw, GH, out, 2 * H, Tp * 2 * H, cst,
-                         dout, 2 * H, Tp * 2 * H, 1.0, wf_off=I0 * GH, wb_off=I0 * GH,
-                         db_fw=P4[1].grad if direct else None, db_bw=P4[3].grad if direct else None,
-                         chunk_flag=None if dc is None else dc[0], chunk_rows=0 if dc is None else dc[1],
-                         n_rows=0 if dc is None else dc[2], prepared_ws=_prepared_ws(kfw, kbw, cell, H, GH, I0 * GH, B, True),
-                         progress=prog, progress_steps=TAIL_WINDOW)
-        if dc is not None and not serial:
-            dc[3]()                          # the other chunks: chain stream, enqueued behind the sweep's launch
-            _hip.join_chain_stream()         # (they are finished when the sweep is; this orders later readers of dout)
-        dx = dx_bw = None
-        if ctx.needs_input_grad[0] and not two:        # on the dependency chain: main stream, first
-            # dX [B*T, Ik] = dZ [B*T, 2GH] . [W_ih_fw | W_ih_bw]^T : B operand = shadow of the concatenated weights [Ik, 2GH]
-            Wb = _shadow("ih", (kfw, kbw), I0, False, Ik, 2 * GH)                           # rows padded to Ik: [Ik, 2GH]
-            dx = torch.empty(B, T, Ik, device=dev, dtype=bf)
-            c = DOUT_CHUNK_ROWS
-            if ctx.x_is_tanh and ctx.in_pyramid and c and T >= 4 * c and direct and _hip.rnn_seq_bwd_chunks_ok(_cellid(cell), prec, B, H):
-                # first time chunk only; the dense node below (the consumer of this dPre) interleaves the others with its own.
-                # (Only inside pBLSTMLayer's stack, where that dense node's input gradient goes to the recurrent layer below and
-                #  nowhere else: a consumer that does not know about the chunks would read an unfinished tensor.)
-                th = (T + 1) // 2
-
-                def produce(k):
-                    if k == 1 and _hip.streams_overlap(dev):
-                        for t in (gates, x, dx):
-                            t.record_stream(_hip.chain_stream())
-                    lo0, lo1 = k * c, min((k + 1) * c, th)
-                    hi0, hi1 = max(T - lo1, lo1), T - lo0
-                    _hip.gemm_kk_frames(gates, Wb, dx, B, T, lo0, lo1 - lo0, hi0, hi1 - hi0, Ik, 2 * GH, 2 * GH, 2 * GH, Ik,
-                                        tanh_y=x, ldy=Ik)
-
-                produce(0)
-                chain_done = []
-                _DCHUNK[dx.data_ptr()] = (c, T, (th + c - 1) // c, produce, chain_done)
-                _DPRE.add(dx.data_ptr())
-                produced = torch.cuda.Event()
-                produced.record()
-            elif ctx.x_is_tanh:
-                _hip.gemm_kk(gates, Wb, dx, B * T, Ik, 2 * GH, 2 * GH, 2 * GH, Ik, tanh_y=x, ldy=Ik)
-                _DPRE.add(dx.data_ptr())
-            else:
-                _hip.gemm_kk(gates, Wb, dx, B * T, Ik, 2 * GH, 2 * GH, 2 * GH, Ik)
-        elif two and (ctx.needs_input_grad[0] or ctx.needs_input_grad[9]):
-            dx, dx_bw = torch.empty(B, T, Ik, device=dev, dtype=bf), torch.empty(B, T, Ik, device=dev, dtype=bf)
-            for d, (dxd, k) in enumerate(((dx, kfw), (dx_bw, kbw))):
-                Wd = _shadow("ih%d" % d, (k,), I0, False, Ik, GH)
-                _hip.gemm_kk(gates, Wd, dxd, B * T, Ik, GH, 2 * GH, GH, Ik, a_off=d * GH)
+        need_dx = ctx.needs_input_grad[0]
+        n = _Node16(x=x, x_bw=x_bw, kfw=kfw, kbw=kbw, gates=gates, out=out, cst=cst, cell=cell, B=B, T=T, Tp=Tp, H=H, GH=GH, Ik=Ik, I0=I0, P4=P4,
+                    direct=P4 is not None and all(_direct_ok(p) for p in P4),
+                    one_pass=WGRAD_ONE_PASS and T > 1 and H % 128 == 0 and GH % 128 == 0 and B * T < (1 << 24) and out.dtype == x.dtype == torch.bfloat16)
+        tail = n.direct and not need_dx and x_bw is None          # the bottom layer: its weight gradients are the end of the step
+        windows = tail and n.one_pass and TAIL_WINDOW > 0 and T >= 3 * TAIL_WINDOW
+        dc = _upstream_handover(n, dout)
+        follow = _bptt_sweep16(n, dout, dc, windows)
+        dx, dx_bw, handed = _dx16(n, need_dx, ctx.needs_input_grad[9], ctx.x_is_tanh, ctx.in_pyramid)
         _hip.run_deferred()
-        Ig = (I0 + 3) // 4 * 4          # rows of dW_ih the TN product writes; rows I0..Ig meet zero operand columns (exact zeros)
-
-        one_pass = WGRAD_ONE_PASS and T > 1 and H % 128 == 0 and GH % 128 == 0 and B * T < (1 << 24) and out.dtype == bf and x.dtype == bf
-
-        def wgrads(gk_of, d):
-            # dW_ih = x^T . dG_d (contraction over all B*T frames; split-K inside las_gemm); dW_hh = sum_b sum_t h_prev^T . dG_d
-            # (`part` is allocated HERE, i.e. on the stream that uses it: a block of the main stream's pool handed to the
-            #  side stream would be recycled by the allocator while the side stream still writes it)
-            gk = gk_of(d)
-            if one_pass:
-                # one pass over dG_d for both (round 4): the left operand is [x | h_prev] with h_prev read from `out` one frame back
-                _hip.wgrad_ih_hh(xs[d], Ik, I0, out, 2 * H, Tp * 2 * H, gates, 2 * GH, B, T, H, GH, d, gk)
-                return
-            part = torch.empty(B, H, GH, device=dev) if T > 1 else None
-            _hip.gemm(prec, xs[d], gates, gk, True, False, Ig, GH, B * T, Ik, 2 * GH, GH, beta=1.0, b_off=d * GH)
-            if T > 1:
-                a_off = d * H + (0 if d == 0 else 2 * H)
-                b_off = d * GH + (2 * GH if d == 0 else 0)
-                _hip.gemm(prec, out, gates, part, True, False, H, GH, T - 1, 2 * H, 2 * GH, GH, batch=B,
-                          strideA=Tp * 2 * H, strideB=T * 2 * GH, strideC=H * GH, a_off=a_off, b_off=b_off)
-                _hip.colsum(part, B, H * GH, H * GH, gk[I0:].reshape(-1), beta=1.0)
-
-        def wgrads_both(gk_of, pair=False):
-            if one_pass and pair:                      # both directions in one launch
-                _hip.wgrad_ih_hh(x, Ik, I0, out, 2 * H, Tp * 2 * H, gates, 2 * GH, B, T, H, GH, 2, gk_of(0), gk_of(1), x_bw if two else None)
+        if n.direct:
+            # weight gradients: off the chain, accumulated straight into the flat gradient bucket
+            hold = ctx.hold_side and need_dx and _hip.streams_overlap(x.device)
+            if handed is not None:
+                _hip.defer_side(lambda: _wgrads16_side(n, hold, handed))      # run by the next sweep's node, after its launch
+            elif tail and (TAIL_TWO_STREAMS or windows):
+                _wgrads16_tail(n, windows, follow)
             else:
-                for d in range(2):
-                    wgrads(gk_of, d)
-
-        if direct:
-            # weight gradients: off the chain -> side stream, accumulated straight into the flat gradient bucket
-            hold = ctx.hold_side and ctx.needs_input_grad[0] and _hip.streams_overlap(dev)
-
-            def side_work(after=None):
-                with _hip.on_side_stream(after=after):
-                    side = _hip.side_stream()
-                    for t in (x, gates, out) + ((x_bw,) if two else ()):
-                        t.record_stream(side)
-                    if after is not None:
-                        # hand-over in chunks: these GEMMs would compete with the chain-stream chunks the next sweep is
-                        # waiting for -- they start when the last chunk is done
-                        if chain_done:
-                            side.wait_event(chain_done[0])
-                    elif hold:
-                        VARIANTS["hold_side"] += 1
-                        # keep the side stream (these GEMMs and whatever is queued behind them) off the machine until the NEXT
-                        # BPTT sweep is resident: they would delay its start (it needs whole CUs) and slow the chain GEMMs in
-                        # front of it; bounded wait, scheduling only
-                        _hip.hold_until_next_sweep(dev)
-                    wgrads_both(lambda d: P4[2 * d].grad)
-
-            if produced is not None:
-                _hip.defer_side(lambda: side_work(produced))      # run by the next sweep's node, after its launch
-            elif (TAIL_TWO_STREAMS or windows) and not ctx.needs_input_grad[0] and not two:
-                if BEFORE_TAIL_HOOK[0] is not None:
-                    # data parallel: every gradient but this layer's is final once the work queued so far has run -- the
-                    # all-reduce of that part of the bucket starts now, under the tail (las.las.LAS.train)
-                    BEFORE_TAIL_HOOK[0](P4)
-                # bottom layer = the end-of-step tail, nothing left to hide behind.  Round 4: both directions in ONE launch on THIS
-                # stream (no event hand-over to another queue in front of it and behind it: 28 + 67 us of the 347 us tail).  Without the
-                # one-pass kernel: the two directions' products on two streams (a single one of them does not fill the chip)
-                if windows:
-                    S = TAIL_WINDOW
-                    nwin = (T + S - 1) // S
-                    VARIANTS["tail_windows"] += nwin
-                    VARIANTS["tail_follow"] += int(follow)
-
-                    def window(c):
-                        lo, n = c * S, min(S, T - c * S)
-                        _hip.wgrad_ih_hh_window(x, Ik, I0, out, 2 * H, Tp * 2 * H, gates, 2 * GH, B, T, H, GH, 2, T - lo - n, lo, n,
-                                                TAIL_WINDOW_WGS if c + 1 < nwin else 0, P4[0].grad, P4[2].grad, None)
-
-                    if follow:
-                        with _hip.on_side_stream(after=before_sweep):
-                            for t in (x, gates, out, prog):
-                                t.record_stream(_hip.side_stream())
-                            for c in range(nwin):
-                                _hip.wait_words_min(prog, nprog, min((c + 1) * S, T))
-                                window(c)
-                    else:
-                        for c in range(nwin):
-                            window(c)
-                    return (dx, None, None, None, None, None, None, None, None, dx_bw)
-                if one_pass and TAIL_ONE_LAUNCH:
-                    wgrads_both(lambda d: P4[2 * d].grad, pair=True)
-                    return (dx, None, None, None, None, None, None, None, None, dx_bw)
-                with _hip.on_side_stream():
-                    for t in (x, gates, out):
-                        t.record_stream(_hip.side_stream())
-                    wgrads(lambda d: P4[2 * d].grad, 0)
-                with _hip.on_chain_stream():
-                    for t in (x, gates, out):
-                        t.record_stream(_hip.chain_stream())
-                    wgrads(lambda d: P4[2 * d].grad, 1)
-            else:
-                side_work()
-            return (dx, None, None, None, None, None, None, None, None, dx_bw)
+                _wgrads16_side(n, hold)
+            return _blstm_grads(dx, dx_bw)
         grads = []
         for d, k in enumerate((kfw, kbw)):
             dk = torch.zeros_like(k)
-            wgrads(lambda d, dk=dk: dk, d)
-            db = torch.empty(GH, device=dev)
+            _wgrad16(n, d, dk)
+            db = torch.empty(GH, device=x.device)
             _hip.colsum(gates, B * T, GH, 2 * GH, db, x_off=d * GH)
             grads += [dk, db]
-        return (dx, grads[0], grads[1], grads[2], grads[3], None, None, None, None, dx_bw)
+        return _blstm_grads(dx, dx_bw, *grads)
 
 
 def _blstm_params(scope, I, H, cell):
@@ -1005,9 +1018,6 @@ def blstm(inputs, cell_units, dropout_rate, is_training, scope="blstm"):
     return outputs, states
 
 
-DROPOUT_KERNEL = os.environ.get("LAS_NO_DROPOUT_KERNEL") != "1"     # input dropout of both directions in one launch (las_dropout_pair_fwd)
-
-
 class _DropoutPair(torch.autograd.Function):
     """The two directions' independently masked copies of a recurrent layer's input (las/layers.py:37-47), as the x-projection's operand
     blocks: [.., K] -> two [.., ld] tensors (bf16 or fp32; columns K .. ld - 1 zero).  Masks are a counter-based function of
@@ -1026,8 +1036,7 @@ class _DropoutPair(torch.autograd.Function):
         odt = torch.bfloat16 if out_bf16 else torch.float32
         yf = torch.empty(rows, ld, device=x.device, dtype=odt)
         yb = torch.empty(rows, ld, device=x.device, dtype=odt)
-        dt = lambda t: _hip.DT_BF16 if t.dtype == torch.bfloat16 else _hip.DT_F32
-        _hip.check(_hip.lib().las_dropout_pair_fwd(_hip.p(x2), dt(x2), rows, K, K, _hip.p(yf), _hip.p(yb), dt(yf), ld, float(keep), int(seed),
+        _hip.check(_hip.lib().las_dropout_pair_fwd(_hip.p(x2), _hip._dt(x2), rows, K, K, _hip.p(yf), _hip.p(yb), _hip._dt(yf), ld, float(keep), int(seed),
                                                    _hip.stream()), "las_dropout_pair_fwd")
         ctx.cfg = (float(keep), int(seed), K, ld, x.dtype, tuple(shp))
         return yf.view(*shp[:-1], ld), yb.view(*shp[:-1], ld)
@@ -1042,8 +1051,7 @@ class _DropoutPair(torch.autograd.Function):
         gf2, gb2 = gf.reshape(-1, gf.shape[-1]).contiguous(), gb.reshape(-1, gb.shape[-1]).contiguous()
         rows = gf2.shape[0]
         dx = torch.empty(rows, K, device=gf.device, dtype=xdt if xdt in (torch.float32, torch.bfloat16) else torch.float32)
-        dt = lambda t: _hip.DT_BF16 if t.dtype == torch.bfloat16 else _hip.DT_F32
-        _hip.check(_hip.lib().las_dropout_pair_bwd(_hip.p(gf2), _hip.p(gb2), dt(gf2), gf2.shape[-1], rows, K, _hip.p(dx), dt(dx), K, keep, seed,
+        _hip.check(_hip.lib().las_dropout_pair_bwd(_hip.p(gf2), _hip.p(gb2), _hip._dt(gf2), gf2.shape[-1], rows, K, _hip.p(dx), _hip._dt(dx), K, keep, seed,
                                                    _hip.stream()), "las_dropout_pair_bwd")
         return dx.view(shp), None, None, None, None
 
@@ -1064,19 +1072,15 @@ def _blstm_full(inputs, cell_units, dropout_rate, is_training, scope="blstm", pa
         # draws its own fresh Bernoulli mask on the cell INPUT at every time step, scaled by 1/keep.
         # The input projection is hoisted over all t, so the per-step masks of a direction are one mask over [B,T,I]
         # (torch RNG: plumbing, the masks are not on the MFMA path).
-        if DROPOUT_KERNEL:
-            # round 6: both directions' masked operand blocks in ONE launch, already bf16 / zero-padded to the product's K where the speed
-            # mode's sweeps serve this layer (was: 2 x F.dropout + 2 x pad + 2 x cast); masks from a counter, regenerated in backward
-            I_ = inputs.shape[-1]
-            speed = _prec() == _hip.PREC_BF16 and _hip.rnn_seq_io_dtype(_cellid(_CFG["cell"]), _hip.PREC_BF16, int(cell_units)) == torch.bfloat16
-            ld = _k64(I_) if speed else (I_ + 3) // 4 * 4
-            x_fw, x_bw = _DropoutPair.apply(inputs, 1.0 - float(dropout_rate), _dropout_seed(), speed, ld)
-            if not speed and ld != I_:
-                x_fw, x_bw = x_fw[..., :I_], x_bw[..., :I_]
-            inputs = x_fw
-        else:
-            x_bw = torch.nn.functional.dropout(inputs, p=float(dropout_rate), training=True)
-            inputs = torch.nn.functional.dropout(inputs, p=float(dropout_rate), training=True)
+        # Round 6: both directions' masked operand blocks in ONE launch, already bf16 / zero-padded to the product's K where the speed
+        # mode's sweeps serve this layer (tried: 2 x F.dropout + 2 x pad + 2 x cast, LAS_NO_DROPOUT_KERNEL=1 -- six launches on the chain
+        # for one); masks from a counter, regenerated in backward
+        speed = _prec() == _hip.PREC_BF16 and _hip.rnn_seq_io_dtype(_cellid(_CFG["cell"]), _hip.PREC_BF16, int(cell_units)) == torch.bfloat16
+        ld = _k64(I_true) if speed else (I_true + 3) // 4 * 4
+        x_fw, x_bw = _DropoutPair.apply(inputs, 1.0 - float(dropout_rate), _dropout_seed(), speed, ld)
+        if not speed and ld != I_true:
+            x_fw, x_bw = x_fw[..., :I_true], x_bw[..., :I_true]
+        inputs = x_fw
     cell = _CFG["cell"]
     H = int(cell_units)
     I = I_true                                  # (the dropout launch may already have padded the operand blocks to the product's K)
@@ -1108,17 +1112,12 @@ def pBLSTMLayer(inputs, audiolen, num_layers, cell_units, dropout_rate, is_train
     sc = scope + "/blstm"
     if _prec() == _hip.PREC_BF16 and XPROJ_CHUNK_STEPS and ROW_T[0] is None:
         _hip.streams_overlap(inputs.device)     # (callers that do not go through LAS.train: probe before the first chunk is issued)
-    _TANH_OUT.clear()
-    _DPRE.clear()
-    _EXPECT_DPRE.clear()
-    _DCHUNK.clear()
-    _DOUT_CHUNKS.clear()
-    _XCHUNK.clear()
+    _reset_handovers()
 
     def hint(B, Tn):
         # the dense + tanh whose output goes straight into the next recurrent layer (no dropout mask in between) follows that
         # layer's time chunks: only the first chunk of frames is on the chain in front of the sweep
-        cs = _xproj_chunk_steps(B, Tn, H, _CFG["cell"]) if DENSE_CHUNKS and not (is_training is True and dropout_rate) else 0
+        cs = _xproj_chunk_steps(B, Tn, H, _CFG["cell"]) if not (is_training is True and dropout_rate) else 0
         # (B <= 64: the sweep's clusters must leave most of the machine to the chunk products -- at B = 96, the stacked steps, the sweep holds
         #  120 of the 256 CUs and the dense chunks arrive late: 22.9 vs 21.4 ms per step with the x-projection's chunks alone)
         if cs and B <= DENSE_CHUNK_MAX_ROWS and _prec() == _hip.PREC_BF16:
@@ -1205,7 +1204,7 @@ def bn(inputs, is_training, scope="batch_normalization", relu=False):
     (las/layers.py:108,161), fused into the same passes in training mode."""
     st = V.default_store()
     C = inputs.shape[-1]
-    gamma = st.get(scope + "/gamma", (C,), init=lambda rng, shp: __import__("numpy").ones(shp))
+    gamma = st.get(scope + "/gamma", (C,), init=lambda rng, shp: np.ones(shp))
     beta = st.get(scope + "/beta", (C,), init="zeros")
     mean = st.get_buffer(scope + "/moving_mean", (C,), 0.0)
     var = st.get_buffer(scope + "/moving_variance", (C,), 1.0)
@@ -1230,7 +1229,6 @@ def conv2d(inputs, output_dim, k_h=3, k_w=3, d_h=2, d_w=2, stddev=1, name="conv2
     """3x3 stride-2 SAME convolution + bias (+ BN) + ReLU on an NHWC block (reference las/layers.py:97-112).
     Secondary encoder path: the convolution itself runs through torch/MIOpen, with TF's
     asymmetric SAME padding applied explicitly."""
-    import numpy as np
     st = V.default_store()
     Cin = inputs.shape[-1]
     w = st.get(name + "/w", (k_h, k_w, Cin, output_dim), init=lambda rng, shp: rng.randn(*shp) * stddev * 0.01)

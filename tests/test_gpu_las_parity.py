@@ -202,29 +202,27 @@ def test_backward_hand_over_in_chunks_gives_the_same_gradients():
     dy = None
     got = {}
     L.set_cell("lstm"); L.set_precision("bf16")
-    old = L.DOUT_CHUNK_ROWS
     try:
         for rows in (0, 64):
-            L.DOUT_CHUNK_ROWS = rows
-            st = V.reset_default_store(device="cuda", seed=3)
-            for _ in range(2):                        # first pass creates the variables; the second runs on the flattened store
-                y, _, _ = L.pBLSTMLayer(x, [T] * B, layers, H, 0.0, True)
-                if st.flat_grad is None:
-                    st.flatten()
-                    continue
-                if dy is None:
-                    dy = torch.randn(y.shape, generator=g).cuda() * 0.1
-                st.flat_grad.zero_()
-                for k in L.VARIANTS:
-                    L.VARIANTS[k] = 0
-                y.backward(dy)
-                _hip.join_side_stream()
-            torch.cuda.synchronize()
-            _hip.check_status()
-            got[rows] = st.flat_grad.clone()
-            used[rows] = dict(L.VARIANTS)
+            with L.schedule(DOUT_CHUNK_ROWS=rows):
+                st = V.reset_default_store(device="cuda", seed=3)
+                for _ in range(2):                        # first pass creates the variables; the second runs on the flattened store
+                    y, _, _ = L.pBLSTMLayer(x, [T] * B, layers, H, 0.0, True)
+                    if st.flat_grad is None:
+                        st.flatten()
+                        continue
+                    if dy is None:
+                        dy = torch.randn(y.shape, generator=g).cuda() * 0.1
+                    st.flat_grad.zero_()
+                    for k in L.VARIANTS:
+                        L.VARIANTS[k] = 0
+                    y.backward(dy)
+                    _hip.join_side_stream()
+                torch.cuda.synchronize()
+                _hip.check_status()
+                got[rows] = st.flat_grad.clone()
+                used[rows] = dict(L.VARIANTS)
     finally:
-        L.DOUT_CHUNK_ROWS = old
         L.set_cell("rnn"); L.set_precision("f32")
     a, b = got[0], got[64]
     # the two runs really were two schedules: whole GEMMs between the sweeps vs the CH = true BPTT instance behind chunked products

@@ -118,36 +118,21 @@ def test_three_b48_steps_are_bit_reproducible_and_independent_of_the_hand_overs(
     assert l1 == l2, (l1, l2)
     assert torch.equal(g1, g2), "first-step gradient differs between two identical runs: max %.3e" % (g1 - g2).abs().max().item()
     assert torch.equal(f1, f2), "parameters after 3 steps differ between two identical runs: max %.3e" % (f1 - f2).abs().max().item()
-    saved = (L.XPROJ_CHUNK_STEPS, L.DOUT_CHUNK_ROWS, L.HOLD_SIDE, L.TAIL_TWO_STREAMS)
-    try:
-        L.XPROJ_CHUNK_STEPS, L.DOUT_CHUNK_ROWS, L.HOLD_SIDE, L.TAIL_TWO_STREAMS = 0, 0, False, False
+    handovers_off = dict(XPROJ_CHUNK_STEPS=0, DOUT_CHUNK_ROWS=0, HOLD_SIDE=False, TAIL_TWO_STREAMS=False)
+    with L.schedule(**handovers_off):
         f3, g3, l3 = _three_steps(args, p0, xs, ys, handovers=False)      # (asserts that nothing was handed over)
-    finally:
-        L.XPROJ_CHUNK_STEPS, L.DOUT_CHUNK_ROWS, L.HOLD_SIDE, L.TAIL_TWO_STREAMS = saved
     # ... and with every sweep packing for itself (rounds 1-4's launches): the prepared workspaces must change nothing, bit for bit
-    saved_p = L.PREPARED_SWEEPS
-    try:
-        L.PREPARED_SWEEPS = False
+    with L.schedule(PREPARED_SWEEPS=False):
         f4, g4, l4 = _three_steps(args, p0, xs, ys, prepared=False)
-    finally:
-        L.PREPARED_SWEEPS = saved_p
     assert l1 == l4 and torch.equal(g1, g4) and torch.equal(f1, f4), "prepared sweep workspaces changed the result"
     # round 5, off by default (no gain, las/layers.py TAIL_WINDOW): the end-of-step tail in windows that FOLLOW the last BPTT sweep
     # (las_rnn_seq_bwd's progress -> las_wait_words_min -> las_wgrad_ih_hh_window on the side stream).  The windows are the arithmetic,
     # following is the schedule: with the hand-overs off the same window launches run behind the sweep -- bitwise equal; against the
     # one-launch tail the split of the contraction differs (tolerance)
-    saved_w = L.TAIL_WINDOW
-    try:
-        L.TAIL_WINDOW = 160
+    with L.schedule(TAIL_WINDOW=160):
         f5, g5, l5 = _three_steps(args, p0, xs, ys)
-        saved = (L.XPROJ_CHUNK_STEPS, L.DOUT_CHUNK_ROWS, L.HOLD_SIDE, L.TAIL_TWO_STREAMS)
-        try:
-            L.XPROJ_CHUNK_STEPS, L.DOUT_CHUNK_ROWS, L.HOLD_SIDE, L.TAIL_TWO_STREAMS = 0, 0, False, False
+        with L.schedule(**handovers_off):
             f6, g6, l6 = _three_steps(args, p0, xs, ys, handovers=False)
-        finally:
-            L.XPROJ_CHUNK_STEPS, L.DOUT_CHUNK_ROWS, L.HOLD_SIDE, L.TAIL_TWO_STREAMS = saved
-    finally:
-        L.TAIL_WINDOW = saved_w
     assert l5 == l6 and torch.equal(g5, g6), "tail windows: following the sweep changed the result"
     assert (g5 - g1).abs().max().item() <= 2e-3 * g1.abs().max().item() and abs(l5[0] - l1[0]) <= 1e-5 * max(1.0, abs(l1[0]))
     gerr = (g1 - g3).abs().max().item() / g1.abs().max().item()
@@ -173,9 +158,7 @@ def test_train_eval_train_uses_the_updated_recurrent_weights():
     p0 = O.init_params(args, seed=4, cell="lstm")
 
     def run(prepared):
-        saved = L.PREPARED_SWEEPS
-        L.PREPARED_SWEEPS = prepared
-        try:
+        with L.schedule(PREPARED_SWEEPS=prepared):
             las, st = _fresh(args, p0)
             losses, used = [], []
             losses.append(float(las.train(xs, ys)[0]))
@@ -188,8 +171,6 @@ def test_train_eval_train_uses_the_updated_recurrent_weights():
             torch.cuda.synchronize()
             las.check_status()
             return losses, st.flat.clone(), y_hat.cpu(), used
-        finally:
-            L.PREPARED_SWEEPS = saved
 
     l_ref, f_ref, y_ref, _ = run(False)
     l_new, f_new, y_new, used = run(True)

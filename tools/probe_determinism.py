@@ -30,20 +30,18 @@ sampled_host = np.random.RandomState(1).randint(3, 30, size=(len(xs[1]), U)).ast
 
 def two(seq_flags=0, sampled=None, coins=coins, **knobs):
     L.set_cell("lstm"); L.set_precision("bf16")
-    saved = {k: getattr(L, k) for k in knobs}
     sf = _hip.seq_flags
-    for k, v in knobs.items(): setattr(L, k, v)
     _hip.seq_flags = seq_flags
     try:
-        st = V.reset_default_store(device="cuda"); st.load(p0)
-        las = LAS(args, Listener, Speller, {})
-        for k in range(2):
-            st.global_step = 3
-            las.train(xs, ys, coins=coins, sampled=sampled)
-            torch.cuda.synchronize()
-        return st.flat_grad.clone()
+        with L.schedule(**knobs):
+            st = V.reset_default_store(device="cuda"); st.load(p0)
+            las = LAS(args, Listener, Speller, {})
+            for k in range(2):
+                st.global_step = 3
+                las.train(xs, ys, coins=coins, sampled=sampled)
+                torch.cuda.synchronize()
+            return st.flat_grad.clone()
     finally:
-        for k, v in saved.items(): setattr(L, k, v)
         _hip.seq_flags = sf
 
 cases = [("default on-device sampling", {}), ("host-supplied samples", dict(sampled=sampled_host)),
@@ -51,7 +49,7 @@ cases = [("default on-device sampling", {}), ("host-supplied samples", dict(samp
          ("seq NO_KSPLIT", dict(seq_flags=2)), ("seq AGENT_GRANULES", dict(seq_flags=1)), ("seq NO_WARMERS", dict(seq_flags=16)),
          ("seq NO_HELPER_WAVES", dict(seq_flags=4)), ("seq ROWS16", dict(seq_flags=8)),
          ("TAIL_TWO_STREAMS off", dict(TAIL_TWO_STREAMS=False)), ("FUSE_TANH_GRAD off", dict(FUSE_TANH_GRAD=False)),
-         ("DENSE_CHUNKS off", dict(DENSE_CHUNKS=False)), ("TAIL_ONE_LAUNCH off", dict(TAIL_ONE_LAUNCH=False)), ("WGRAD_ONE_PASS off", dict(WGRAD_ONE_PASS=False))]
+         ("WGRAD_ONE_PASS off", dict(WGRAD_ONE_PASS=False))]
 if os.environ.get("FEW"):
     cases = cases[:3]
 for name, kw in cases:
