@@ -5,7 +5,10 @@ T' in (128, 160] -- what bench.py times -- included.
 
 Tolerance: same rounding points on both sides (bf16 operands, fp32 accumulation), so what is left is accumulation
 order / fast transcendentals / boundary flips of the bf16 rounding: logits 5e-3 (of max|logit|), alignments 2e-3,
-gradients 2e-2 of the largest oracle entry."""
+gradients 2e-2 of the largest oracle entry.
+
+Every case here runs the LSTM cell; the same families with the tanh cell (BasicRNNCell) are held to the oracle by
+tests/test_gpu_speller_rnn_cell.py."""
 import numpy as np
 import pytest
 import torch
