@@ -178,6 +178,9 @@ _SIGS = {
     "las_ctc_log_softmax": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "las_ctc_prefix_step": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p,
                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "las_ctc_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "las_ctc_align": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_size_t, c_void_p]),
     "las_sumsq_workspace_bytes": (c_size_t, [c_longlong]),
     "las_sumsq": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_size_t, c_void_p]),
     "las_clip_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_float, c_float,
@@ -222,7 +225,7 @@ _SIGS = {
 }
 
 
-ABI_VERSION = 603      # include/las_hip.h LAS_HIP_ABI_VERSION
+ABI_VERSION = 604      # include/las_hip.h LAS_HIP_ABI_VERSION
 
 
 def declared_symbols():

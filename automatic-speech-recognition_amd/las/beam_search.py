@@ -79,6 +79,19 @@ class _AttRows(collections.abc.Sequence):
         return list(self) + list(other)
 
 
+class AlignInputs(object):
+    """what BeamSearch.align needs of a searched batch (kept on request, BeamSearch.retain_align): the encoder outputs, or -- when the
+    search computed them -- the CTC head's log-probabilities, which are then not computed a second time"""
+
+    def __init__(self, encs, enc_lens, h_one, ctc_lp):
+        self.encs, self.enc_lens, self.h_one, self.ctc_lp = encs, enc_lens, h_one, ctc_lp
+
+
+class _Results(list):
+    """decode_batch's result list; `align_inputs` is the batch's AlignInputs when BeamSearch.retain_align was set, else None"""
+    align_inputs = None
+
+
 class BeamSearch(object):
     """reference las/beam_search.py:32-312."""
 
@@ -104,6 +117,10 @@ class BeamSearch(object):
         if self.ctc_weight > 0 and not getattr(args, "ctc", False):
             raise ValueError("--ctc_decode_weight %g needs the CTC head: decode with --ctc True (a model trained with --ctc)" % self.ctc_weight)
         self._las = las
+        # decode_batch / decode_batches keep what align() needs of every batch in its results' `align_inputs` (off: nothing is retained --
+        # the CTC log-probabilities are 410 MB at 64 utterances and V = 5000)
+        self.retain_align = False
+        self._head_absent = None            # restore_las: (checkpoint path, the CTC head's variables it lacks)
         self.use_graph = os.environ.get("LAS_NO_DECODE_GRAPH") != "1"     # decode_batch replays one captured step
         self.fuse_projection = os.environ.get("LAS_NO_DECODE_FUSED_PROJ") != "1"   # decode_batch: cell in one launch, projection inside the beam kernel
         # decode_batch (round 5): rows + LM 1 | Speller cell + LM 2 | pruning + gather -- three dependent launches instead of five.  OFF by
@@ -352,6 +369,35 @@ class BeamSearch(object):
         _hip.check(_hip.lib().las_ctc_log_softmax(_hip.p(z), n, Tp, Vc, _hip.p(lp), _hip.stream()), "las_ctc_log_softmax")
         return lp
 
+    def need_ctc_head(self, what):
+        """the ValueError of the --ctc_decode_weight checks for anything else that reads the CTC head"""
+        if not getattr(self.args, "ctc", False):
+            raise ValueError("%s needs the CTC head: decode with --ctc True (a model trained with --ctc)" % what)
+        if self._head_absent is not None:
+            raise ValueError("%s: checkpoint %s holds no CTC head (%s); it was not trained with --ctc True"
+                             % (what, self._head_absent[0], ", ".join(self._head_absent[1])))
+
+    def align(self, encs, enc_lens, token_lists, h_one=None, ctc_lp=None):
+        """CTC Viterbi alignment (las.align.ctc_align) of token_lists[u] to the encoder frames of utterance u: -> (scores,
+        spans), spans[u][j] = (first, last) frame of token j.  encs / enc_lens / h_one: _run_encoders' (or a retained AlignInputs');
+        the head runs here whether or not ctc_decode_weight is set -- unless the caller hands in the `ctc_lp` a search already computed."""
+        from las.align import ctc_align
+        self.need_ctc_head("BeamSearch.align")
+        with torch.no_grad():
+            if ctc_lp is None:
+                ctc_lp = self._ctc_log_probs(encs, h_one)
+            return ctc_align(ctc_lp, [int(x) for x in enc_lens], token_lists)
+
+    def align_results(self, results, token_lists=None):
+        """align() on the AlignInputs a search retained in `results` (retain_align); token_lists defaults to every utterance's best
+        hypothesis without its <SOS> (an utterance without a hypothesis aligns the empty sequence)"""
+        k = getattr(results, "align_inputs", None)
+        if k is None:
+            raise ValueError("BeamSearch.align_results: the search retained nothing -- set retain_align = True before decoding")
+        if token_lists is None:
+            token_lists = [list(r[-1].token_ids[1:]) if r else [] for r in results]
+        return self.align(k.encs, k.enc_lens, token_lists, h_one=k.h_one, ctc_lp=k.ctc_lp)
+
     def decode_batch(self, sess, xs_list, sync_every=32, _pre=None, _after_launch=None, _defer=False):
         """Beam search for several utterances at once (what decode.py's loop over utterances, decode.py:131-149, becomes on
         one GPU): xs_list = [(audio [1,T_u,feat_dim,3], audiolen [1]), ...] -> [list of BeamState (ascending), ...].
@@ -382,6 +428,7 @@ class BeamSearch(object):
         if _pre is None:
             _pre = self._run_encoders(sess, xs_list)
         encs, enc_lens, dec_steps, h_one, ctc_lp = _pre
+        kept = AlignInputs(encs, enc_lens, h_one, ctc_lp) if self.retain_align else None
         lam = self.ctc_weight
         Tps = [h.shape[1] for h in encs]
         Tp, Hd = max(Tps), encs[0].shape[2]
@@ -712,9 +759,9 @@ class BeamSearch(object):
                 ts_ = self._tail_stream
                 ts_.wait_event(ev)
                 with torch.cuda.stream(ts_):
-                    return self._decode_tail(dev, n, selcap, Umax, i32, ba, lib, alphas_hist, Tps, mark)
+                    return self._decode_tail(dev, n, selcap, Umax, i32, ba, lib, alphas_hist, Tps, mark, kept)
             return finish
-        results = self._decode_tail(dev, n, selcap, Umax, i32, ba, lib, alphas_hist, Tps, mark)
+        results = self._decode_tail(dev, n, selcap, Umax, i32, ba, lib, alphas_hist, Tps, mark, kept)
         mark("done")
         parts = {}
         if tm:        # device time of the parts of a decode step (HIP events, 50 eager repetitions each, after the search)
@@ -748,7 +795,7 @@ class BeamSearch(object):
                 print("decode_batch timing (s):", self.last_timing)
         return results
 
-    def _decode_tail(self, dev, n, selcap, Umax, i32, ba, lib, alphas_hist, Tps, mark):
+    def _decode_tail(self, dev, n, selcap, Umax, i32, ba, lib, alphas_hist, Tps, mark, kept=None):
         """What follows a search (decode_batch; on the current stream): the back pointers are walked on the device (las_beam_backtrack), one
         read-back, then the reference's host-side objects (las/beam_search.py:136-158, :297-312)."""
         import ctypes
@@ -774,7 +821,8 @@ class BeamSearch(object):
         # <= 2 x beam candidates of every utterance was 4.2 ms behind a 64-utterance search, a tenth of the batch)
         nz = np.nonzero(lens)[0]
         offs = np.concatenate(([0], np.cumsum(lens[nz] + 1)))[:-1] if nz.size else np.zeros(0, np.int64)
-        results = [[] for _ in range(n)]
+        results = _Results([] for _ in range(n))
+        results.align_inputs = kept
         first = np.searchsorted(nz, np.arange(n + 1) * selcap)
         for u in range(n):
             ws, of = nz[first[u]:first[u + 1]], offs[first[u]:first[u + 1]]
@@ -795,6 +843,7 @@ class BeamSearch(object):
         missing = []
         path = checkpoint.restore(save_path, restore_epoch, missing=missing)
         absent = [nm for nm in checkpoint.CTC_HEAD if nm in missing]
+        self._head_absent = (path, absent) if path is not None and absent else None
         if path is not None and self.ctc_weight > 0 and absent:
             # the head would keep its initial values: the prefix scores would be noise
             raise ValueError("--ctc_decode_weight %g: checkpoint %s holds no CTC head (%s); it was not trained with --ctc True"

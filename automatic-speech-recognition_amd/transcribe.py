@@ -3,12 +3,21 @@
     python transcribe.py [model / checkpoint / LM / CTC flags of decode.py] a.wav b.wav ...
     python transcribe.py --synthetic True            (random weights, generated noise "audio": runs with no data)
     python transcribe.py --synthetic True a.wav ...  (random weights on the given files: the audio path without a checkpoint)
+    python transcribe.py --ctc True --timestamps True a.wav ...        (one JSON object per line: text, score, word times)
+    python transcribe.py --ctc True --align_text refs.txt a.wav ...    (forced alignment: line k of refs.txt is the transcript of file k)
+
+With --timestamps the best hypothesis is aligned to the encoder frames by the CTC head (las.align, csrc/ctc_align.hip: a Viterbi pass
+over the head's log-probabilities) and every line is {"text", "score", "words": [{"word", "start", "end"}]}: times in seconds, None when
+the hypothesis has more tokens than the recording has frames; score = the log-probability of the best alignment path (None likewise).
+--align_text skips the search and aligns the given transcripts.
 
 The files are read with preprocess.read_audio (.flac needs `soundfile`), `--decode_batch` of them at a time go through the device front
 end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip; a file at another rate than --sample_rate is resampled
 on the device first, csrc/resample.hip) and stay on the device for BeamSearch.decode_batches:
 the extraction and the encoders of batch k+1 run under the search of batch k.  The reference has no such entry point (its decode.py reads
 the feature dumps of preprocess.py); the model side is decode.py's."""
+import collections
+import json
 import logging
 import os
 import sys
@@ -17,7 +26,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from las import layers, variables                                  # noqa: E402
-from las.arguments import build_parser                             # noqa: E402
+from las import align as A                                         # noqa: E402
+from las.arguments import build_parser, str2bool                   # noqa: E402
 from las.beam_search import BeamSearch                             # noqa: E402
 from las.frontend import FeatureExtractor                          # noqa: E402
 from las.las import LAS, Listener, Speller                         # noqa: E402
@@ -37,7 +47,14 @@ def main(argv=None):
     from decode import load_lm, restore_lm
     parser = build_parser()
     parser.add_argument("audio", nargs="*", help=".wav / .npy files to transcribe")
+    parser.add_argument("--timestamps", type=str2bool, default=False, help="One JSON object per line with word times (needs --ctc True).")
+    parser.add_argument("--align_text", type=str, default=None, metavar="FILE",
+                        help="Forced alignment: one transcript per audio file, in order; skips the search, implies --timestamps True.")
     args = parser.parse_args(argv)
+    if args.align_text is not None:
+        args.timestamps = True
+    if args.timestamps and not args.ctc:
+        raise ValueError("--timestamps needs the CTC head: decode with --ctc True (a model trained with --ctc)")
     logging.basicConfig(stream=sys.stderr, format='%(asctime)s %(levelname)s:%(message)s', level=logging.INFO, datefmt='%I:%M:%S')
     if not args.synthetic and not args.audio:
         parser.error("no audio files (or --synthetic True)")
@@ -67,6 +84,8 @@ def main(argv=None):
         logging.info("LAS restored: {}".format(bs.restore_las(None, args.save_dir, args.restore_epoch)))
         if result is not None:
             restore_lm(lm, result['best_model'])
+    if args.timestamps:
+        bs.need_ctc_head("--timestamps")                              # (a checkpoint without the head: refused before any audio is read)
     fe = FeatureExtractor(args, device=dev)
     if args.synthetic and not args.audio:
         count = args.max_steps if args.max_steps >= 0 else 8
@@ -75,6 +94,14 @@ def main(argv=None):
         waves = None
         count = len(args.audio)
     nb = max(1, int(args.decode_batch))
+    texts = None
+    if args.align_text is not None:
+        with open(args.align_text) as f:
+            texts = [line.strip() for line in f.read().splitlines()]
+        if len(texts) != count:
+            raise ValueError("--align_text %s holds %d lines for %d audio files" % (args.align_text, len(texts), count))
+    durations = collections.deque()                                    # seconds per utterance, in the order of the results
+    frame_s = A.frame_seconds(args, args.enc_type)
 
     def load(i):
         if waves is not None:
@@ -87,6 +114,7 @@ def main(argv=None):
     def batches():
         for c0 in range(0, count, nb):
             chunk = [load(i) for i in range(c0, min(c0 + nb, count))]          # (host work: file reads)
+            durations.extend(len(w) / float(fs) for w, fs in chunk)
 
             def make(chunk=chunk):
                 # called by decode_batches on the encoders' stream: one upload + three launches (one more per sample rate that is not
@@ -95,7 +123,29 @@ def main(argv=None):
                 return [(cube[u:u + 1, :lens[u]], lens[u:u + 1]) for u in range(len(chunk))]
             yield make
 
+    def timed_lines(token_lists, scores, spans):
+        for tokens, score, span in zip(token_lists, scores, spans):
+            print(json.dumps({"text": convert_idx_to_string(tokens, id_to_token, args.unit),
+                              "score": score if np.isfinite(score) else None,
+                              "words": A.words(tokens, span, id_to_token, args.unit, frame_s, durations.popleft())}))
+
+    if texts is not None:
+        # forced alignment: the listener and the head, no search
+        done = 0
+        for make in batches():
+            with torch.no_grad():
+                encs, enc_lens, _, h_one, ctc_lp = bs._run_encoders(None, make())
+            token_lists = [tokenizer.encode(t, with_eos=True) for t in texts[done:done + len(encs)]]
+            done += len(encs)
+            timed_lines(token_lists, *bs.align(encs, enc_lens, token_lists, h_one=h_one, ctc_lp=ctc_lp))
+        sys.stdout.flush()
+        return
+    bs.retain_align = bool(args.timestamps)
     for results in bs.decode_batches(None, batches()):
+        if args.timestamps:
+            token_lists = [list(r[-1].token_ids[1:]) if r else [] for r in results]
+            timed_lines(token_lists, *bs.align_results(results, token_lists))
+            continue
         for beam_states in results:
             print(convert_idx_to_string(beam_states[-1].token_ids[1:], id_to_token, args.unit))
     sys.stdout.flush()

@@ -37,7 +37,7 @@ enum { LAS_ACT_NONE = 0, LAS_ACT_TANH = 1 };
 enum { LAS_ATT_ADD = 0, LAS_ATT_LOC = 1 };      /* las/las.py:44-49 */
 enum { LAS_DT_F32 = 0, LAS_DT_BF16 = 1 };       /* element type of a tensor in HBM (see las_gemm_kk) */
 
-#define LAS_HIP_ABI_VERSION 603      /* bumped whenever an argument struct or a signature changes: las_version() of a library
+#define LAS_HIP_ABI_VERSION 604      /* bumped whenever an argument struct or a signature changes: las_version() of a library
                                         built from another header differs, and the Python loader refuses it */
 int         las_version(void);
 const char* las_last_error(void);
@@ -619,7 +619,30 @@ int las_ctc_prefix_step(const float* lp, const int* enc_len, int nutt, int beam,
                         const int* dec_step, int Umax, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * K10b  device-resident BeamSearch.decode loop (las/beam_search.py:94-158) for `nutt` utterances at once: ONE call per
+ * K10d  CTC Viterbi (forced) alignment of a token sequence to the encoder frames: token and word times.  The max-plus form
+ * of las_ctc_loss's extended-label recursion (states 0 .. 2L: blank, label 0, blank, ..., label L-1, blank) with a back-trace.
+ *   lp           las_ctc_log_softmax's output, fp32 [n, Vc, Tp] class-major, blank = class Vc - 1
+ *   enc_len [n]  frames of row u, clamped to [1, Tp] (as las_ctc_prefix_step)
+ *   y, y_len     the labels of row u are y[u, 0 : y_len[u]] (int32, pitch ldy >= U).  Any token id is a label, EOS included, and id 0 is
+ *                NOT skipped (unlike las_ctc_loss): the caller passes exactly the sequence to align.
+ *   score [n]    fp64: max over the paths pi that collapse to the labels of sum_{t < enc_len} lp[u, pi_t, t]
+ *   first, last  int32 [n, U]: the inclusive frame range the best path spends on label j, j < y_len[u]; other entries are not written
+ *   frame_state  int32 [n, Tp] or NULL: the state s in [0, 2L] of the best path at frame t, -1 for t >= enc_len[u]
+ * Arithmetic (part of the contract): path scores are fp64; best(0, s) = (double)lp for s <= 1, -inf otherwise; best(t, s) = max(prev(s),
+ * prev(s-1), prev(s-2) if s is a label that differs from the label before it) + (double)lp.  On equal values the smaller step wins (stay,
+ * then s-1, then s-2); the final state is the larger of 2L and 2L-1, 2L on a tie.  One fp64 addition per frame and no products: a float64
+ * restatement that adds in the same order along t gives the same bits (tests/ctc_align_ref.py), and so do two runs (no atomics).
+ * A row that cannot be aligned -- y_len[u] outside [0, U], a label outside [0, Vc-2], or no path (L + repeats > enc_len) -- gets score =
+ * -inf, first = last = -1 for j < min(max(y_len[u], 0), U) and frame_state = -1; the other rows are unaffected and the call returns 0.
+ * Refused on the host before anything is launched: U > 511, Tp > 2048 (the limits of las_ctc_loss / las_ctc_prefix_step), n > 65535,
+ * ws_bytes < las_ctc_align_workspace_bytes(n, Tp, U).  Three launches on `stream` (gather, recursion, back-trace), no synchronisation.
+ */
+size_t las_ctc_align_workspace_bytes(int n, int Tp, int U);
+int las_ctc_align(const float* lp, int Vc, int Tp, const int* enc_len, int n, const int* y, int ldy, const int* y_len, int U,
+                  int* first, int* last, int* frame_state, double* score, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K10b device-resident BeamSearch.decode loop (las/beam_search.py:94-158) for `nutt` utterances at once: ONE call per
  * step prunes every utterance exactly as las_beam_step does AND keeps the reference's bookkeeping on the device, so
  * the host never waits inside the loop:
  *   - live hypotheses: score / length [nutt,beam] and nlive [nutt] updated in place (compacted, ascending rank);
