@@ -222,10 +222,15 @@ _SIGS = {
     "las_resample": (c_int, [POINTER(ResampleArgs), c_void_p]),
     "las_specaug_tile": (c_int, []),
     "las_specaug": (c_int, [POINTER(SpecAugArgs), c_void_p]),
+    "las_vad_tile": (c_int, []),
+    "las_vad_max_runs": (c_longlong, [c_longlong, c_int]),
+    "las_vad_workspace_bytes": (c_size_t, [c_int, c_longlong]),
+    "las_vad": (c_int, [c_void_p, c_int, c_longlong, c_void_p, POINTER(c_int), c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_int,
+                        c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 
-ABI_VERSION = 604      # include/las_hip.h LAS_HIP_ABI_VERSION
+ABI_VERSION = 605      # include/las_hip.h LAS_HIP_ABI_VERSION
 
 
 def declared_symbols():

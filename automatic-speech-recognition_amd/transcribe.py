@@ -5,11 +5,19 @@
     python transcribe.py --synthetic True a.wav ...  (random weights on the given files: the audio path without a checkpoint)
     python transcribe.py --ctc True --timestamps True a.wav ...        (one JSON object per line: text, score, word times)
     python transcribe.py --ctc True --align_text refs.txt a.wav ...    (forced alignment: line k of refs.txt is the transcript of file k)
+    python transcribe.py --segment True meeting.wav ...                (long recordings: cut at the silences first, one line per file)
 
 With --timestamps the best hypothesis is aligned to the encoder frames by the CTC head (las.align, csrc/ctc_align.hip: a Viterbi pass
 over the head's log-probabilities) and every line is {"text", "score", "words": [{"word", "start", "end"}]}: times in seconds, None when
 the hypothesis has more tokens than the recording has frames; score = the log-probability of the best alignment path (None likewise).
 --align_text skips the search and aligns the given transcripts.
+
+With --segment every file is first cut into segments by an energy voice-activity detector on the device (las.vad, csrc/vad.hip: speech =
+frames within --vad_top_db of the file's loudest and over --vad_floor_db, padded by --vad_pad_ms, runs under --vad_min_speech_ms
+dropped, runs over --max_segment_s -- the training cap -- cut at their quietest frame).  The segments of all files form one stream that
+goes through the front end and the search --decode_batch at a time, as files do otherwise.  A file's line is its segments' hypotheses
+joined by one space (an empty line for a silent file); with --timestamps it is {"text", "score", "words", "segments": [{"start", "end",
+"text", "score", "words"}]}: word times offset by the segment's start, score = the sum of the segment scores (None if one is None).
 
 The files are read with preprocess.read_audio (.flac needs `soundfile`), `--decode_batch` of them at a time go through the device front
 end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip; a file at another rate than --sample_rate is resampled
@@ -27,6 +35,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from las import layers, variables                                  # noqa: E402
 from las import align as A                                         # noqa: E402
+from las import vad as VAD                                         # noqa: E402
 from las.arguments import build_parser, str2bool                   # noqa: E402
 from las.beam_search import BeamSearch                             # noqa: E402
 from las.frontend import FeatureExtractor                          # noqa: E402
@@ -50,7 +59,10 @@ def main(argv=None):
     parser.add_argument("--timestamps", type=str2bool, default=False, help="One JSON object per line with word times (needs --ctc True).")
     parser.add_argument("--align_text", type=str, default=None, metavar="FILE",
                         help="Forced alignment: one transcript per audio file, in order; skips the search, implies --timestamps True.")
+    VAD.add_flags(parser, str2bool)
     args = parser.parse_args(argv)
+    if args.segment and args.align_text is not None:
+        raise ValueError("--segment cuts the recordings, --align_text aligns one transcript per whole file: use one of them")
     if args.align_text is not None:
         args.timestamps = True
     if args.timestamps and not args.ctc:
@@ -129,6 +141,8 @@ def main(argv=None):
                               "score": score if np.isfinite(score) else None,
                               "words": A.words(tokens, span, id_to_token, args.unit, frame_s, durations.popleft())}))
 
+    if args.segment:
+        return transcribe_segmented(args, bs, fe, VAD.VoiceActivity(args, device=dev), load, count, nb, id_to_token, frame_s)
     if texts is not None:
         # forced alignment: the listener and the head, no search
         done = 0
@@ -148,6 +162,71 @@ def main(argv=None):
             continue
         for beam_states in results:
             print(convert_idx_to_string(beam_states[-1].token_ids[1:], id_to_token, args.unit))
+    sys.stdout.flush()
+
+
+def transcribe_segmented(args, bs, fe, va, load, count, nb, id_to_token, frame_s):
+    """--segment: every file cut by las.vad at its own sample rate, the segments of all files as one stream through the front end and
+    the search, nb at a time (a batch may span files and rates); one output line per file, in file order"""
+    files = collections.deque()                                        # [segments (start s, end s) of a file, its results so far]
+
+    def batches():
+        chunk = []
+
+        def flush():
+            def make(chunk=chunk[:]):
+                cube, lens = fe.extract([w for w, _ in chunk], rate=[fs for _, fs in chunk])
+                return [(cube[u:u + 1, :lens[u]], lens[u:u + 1]) for u in range(len(chunk))]
+            del chunk[:]
+            return make
+
+        for i in range(count):
+            audio, fs = load(i)
+            ranges = va.segments(audio, fs)                            # (one upload, one las_vad call, one wait per file)
+            files.append(([(s0 / float(fs), s1 / float(fs)) for s0, s1 in ranges], []))
+            for s0, s1 in ranges:
+                chunk.append((audio[s0:s1], fs))
+                if len(chunk) == nb:
+                    yield flush()
+        if chunk:
+            yield flush()
+
+    def emit_finished():
+        while files and len(files[0][1]) == len(files[0][0]):
+            spans, done = files.popleft()
+            text = " ".join(d["text"] for d in done)
+            if not args.timestamps:
+                print(text)
+                continue
+            scores = [d["score"] for d in done]
+            print(json.dumps({"text": text, "score": None if any(x is None for x in scores) else float(sum(scores)),
+                              "words": [w for d in done for w in d["words"]], "segments": done}))
+
+    def take(tokens, score=None, span=None):
+        emit_finished()                                                # (silent files in front of this segment's file)
+        spans, done = files[0]                                         # results arrive in stream order: the first unfinished file
+        t0, t1 = spans[len(done)]
+        d = {"text": convert_idx_to_string(tokens, id_to_token, args.unit)}
+        if args.timestamps:
+            ws = A.words(tokens, span, id_to_token, args.unit, frame_s, t1 - t0)
+            for w in ws:                                               # file time, clipped to the segment's end
+                if w["start"] is not None:
+                    w["start"], w["end"] = min(t0 + w["start"], t1), min(t0 + w["end"], t1)
+            d = {"start": t0, "end": t1, "text": d["text"], "score": score if np.isfinite(score) else None, "words": ws}
+        done.append(d)
+        emit_finished()
+
+    bs.retain_align = bool(args.timestamps)
+    for results in bs.decode_batches(None, batches()):
+        token_lists = [list(r[-1].token_ids[1:]) if r else [] for r in results]
+        if args.timestamps:
+            for tokens, score, span in zip(token_lists, *bs.align_results(results, token_lists)):
+                take(tokens, score, span)
+        else:
+            for tokens in token_lists:
+                take(tokens)
+    emit_finished()                                                    # (trailing silent files; no file at all is left unfinished)
+    assert not files
     sys.stdout.flush()
 
 

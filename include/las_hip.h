@@ -37,7 +37,7 @@ enum { LAS_ACT_NONE = 0, LAS_ACT_TANH = 1 };
 enum { LAS_ATT_ADD = 0, LAS_ATT_LOC = 1 };      /* las/las.py:44-49 */
 enum { LAS_DT_F32 = 0, LAS_DT_BF16 = 1 };       /* element type of a tensor in HBM (see las_gemm_kk) */
 
-#define LAS_HIP_ABI_VERSION 604      /* bumped whenever an argument struct or a signature changes: las_version() of a library
+#define LAS_HIP_ABI_VERSION 605      /* bumped whenever an argument struct or a signature changes: las_version() of a library
                                         built from another header differs, and the Python loader refuses it */
 int         las_version(void);
 const char* las_last_error(void);
@@ -828,6 +828,38 @@ typedef struct las_specaug_args {
 } las_specaug_args;
 int las_specaug_tile(void);                           /* consecutive frames of one utterance a workgroup owns */
 int las_specaug(const las_specaug_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K15  energy voice-activity detector and segmenter in front of las_frontend: a batch of n recordings of very different
+ * lengths -> per recording the runs of frames that hold speech.  Plain arguments, no struct (as las_ctc_align).
+ *   frames    the front end's: T_u = floor((n_u - fl) / step) (0 when n_u < fl), frame t covers samples [t step, t step + fl).  samples
+ *             fp32 or int16 (samples_i16: value / 32767 in fp32, as las_frontend) [n, ld_samples], finite; n_samples int32 [n] on the
+ *             device, n_samples_host the same values on the host (what the entry validates).
+ *   energy    e[u, t] is a DOUBLE: the sum over the frame's samples, in ascending order, of x x, starting at 0, x the fp32 sample widened
+ *             to double -- the product is exact in double, every step is one rounding, a numpy loop gives the same bits.
+ *   peak      emax[u] = max_t e[u, t] (0 for T_u = 0);  thr[u] = max(emax[u] * ratio, floor), ONE double multiply.
+ *   raw       raw[t] = e[t] >= thr && e[t] > 0
+ *   dilation  s[t] = any raw[t'] with |t' - t| <= hang, clipped to [0, T_u): pads the speech, joins gaps of at most 2 hang frames
+ *   runs      a run is a maximal stretch [a, b) of s; runs shorter than min_run frames are dropped
+ * Outputs: runs int32 [n, max_runs, 2]: runs[u, k] = (a, b) in ascending order for k < n_runs[u], entries behind the count are NOT
+ * written; n_runs int32 [n] always written (0 for silence and for T_u = 0).  energy fp64 [n, Tmax] (frames t >= T_u written as 0) and
+ * emax fp64 [n] may be NULL.  las_vad_max_runs(T, hang) = ceil(T / (2 hang + 2)) is the most runs T frames can hold (< 0: bad
+ * arguments); las_vad_tile() the frames of one recording a workgroup owns.
+ * Six launches on `stream` (energies + tile peaks, row peak, tile summaries, row scan, emit, filter + compact), no atomics, no
+ * synchronisation: two calls give the same bits, and a row gives the result it gives alone, whatever the batch and the tile.
+ * Refused on the host before anything is launched (< 0, las_last_error): a NULL samples / n_samples / n_samples_host / runs / n_runs /
+ * ws; n outside 1..65535; Tmax < 1; fl < 1 or step < 1; hang < 0; min_run < 2 (a run of r frames yields r - 1 front-end frames, and
+ * the front end needs one); ratio outside (0, 1]; floor < 0 or not finite; max_runs < las_vad_max_runs(Tmax, hang); ld_samples
+ * outside [1, INT32_MAX]; n_samples_host[u] outside [1, ld_samples]; T_u > Tmax; ws_bytes < las_vad_workspace_bytes(n, Tmax).
+ */
+int       las_vad_tile(void);
+long long las_vad_max_runs(long long T, int hang);
+size_t    las_vad_workspace_bytes(int n, long long Tmax);
+int       las_vad(const void* samples, int samples_i16, long long ld_samples,
+                  const int* n_samples, const int* n_samples_host, int n, int Tmax, int fl, int step,
+                  double ratio, double floor, int hang, int min_run,
+                  double* energy, double* emax, int* runs, int max_runs, int* n_runs,
+                  void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
