@@ -220,6 +220,8 @@ extern "C" int las_bn_relu_bwd(const float* x, const float* y, const float* dy, 
     LAS_ARG(x && dy && gamma && mean && rstd && dx && rows > 0 && C > 0 && (C % 4) == 0, "las_bn_relu_bwd: bad arguments");
     LAS_ARG(!relu || y, "las_bn_relu_bwd: the ReLU's mask needs y");
     LAS_ARG(ws && ws_bytes >= las_bn_workspace_bytes(rows, C), "las_bn_relu_bwd: workspace too small");
+    LAS_ARG(((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)dy) | ((uintptr_t)dx) | ((uintptr_t)gamma) | ((uintptr_t)mean) | ((uintptr_t)rstd) |
+              ((uintptr_t)ws)) & 15) == 0, "las_bn_relu_bwd: 16-byte alignment");          // (float4 loads on all of them; y == NULL without the ReLU)
     hipStream_t st = (hipStream_t)stream;
     int rp;
     const int S = bn_split(rows, &rp);

@@ -1184,6 +1184,8 @@ class _BNReLU(torch.autograd.Function):
         dy = dy.contiguous()
         if dy.dtype != torch.float32:
             dy = dy.float()
+        if dy.data_ptr() % 16:                                   # (a view into a larger gradient: the kernel loads float4)
+            dy = dy.clone()
         dx = torch.empty_like(x2d)
         gp, bp = ctx.params
         direct = _direct_ok(gp) and _direct_ok(bp)
@@ -1219,7 +1221,15 @@ def bn(inputs, is_training, scope="batch_normalization", relu=False):
         y = _BNReLU.apply(x2, gamma, beta, mean, var, bool(relu))
         _PARAMS.pop("bn_gamma", None); _PARAMS.pop("bn_beta", None)
         return y.view(inputs.shape)
-    y = torch.nn.functional.batch_norm(x2, mean, var, gamma, beta, training=bool(is_training), momentum=0.01, eps=1e-3)
+    if bool(is_training) and x2.shape[0] == 1:
+        # one row (torch's batch_norm refuses it): the row is its own mean, the variance is 0 and feeds the moving variance as it is
+        mu, v = x2.mean(0), x2.var(0, unbiased=False)
+        y = (x2 - mu) * torch.rsqrt(v + 1e-3) * gamma + beta
+        with torch.no_grad():
+            mean.mul_(0.99).add_(mu, alpha=0.01)
+            var.mul_(0.99).add_(v, alpha=0.01)
+    else:
+        y = torch.nn.functional.batch_norm(x2, mean, var, gamma, beta, training=bool(is_training), momentum=0.01, eps=1e-3)
     if relu:
         y = torch.relu(y)
     return y.view(inputs.shape)
