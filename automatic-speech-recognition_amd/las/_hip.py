@@ -178,6 +178,8 @@ _SIGS = {
     "las_ctc_log_softmax": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "las_ctc_prefix_step": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p,
                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "las_bias_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                              c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "las_ctc_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "las_ctc_align": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -230,7 +232,7 @@ _SIGS = {
 }
 
 
-ABI_VERSION = 605      # include/las_hip.h LAS_HIP_ABI_VERSION
+ABI_VERSION = 606      # include/las_hip.h LAS_HIP_ABI_VERSION
 
 
 def declared_symbols():

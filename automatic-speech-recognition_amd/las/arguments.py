@@ -93,6 +93,9 @@ _EXTRA = [
                                   "64 x 16 rows decode 1.8x the utterances/s of 16 x 16)."),
     (("--ctc_decode_weight",), float, 0.0, "Weight of the CTC prefix scores in joint CTC-attention beam search (needs --ctc True; 0: attention "
                                            "(+ LM) scores only).  A candidate scores logit + weight * (CTC prefix score gain)."),
+    (("--hotwords",), str, "", "Contextual biasing (las.bias): a file with one phrase per line ('#' lines are comments) whose tokens the beam "
+                               "search boosts; needs --hotword_weight > 0."),
+    (("--hotword_weight",), float, 0.0, "Bonus per matched token of a --hotwords phrase, taken back when the match breaks (0: off)."),
     (("--lm_dir",), str, "lang/output/", "Output directory of train_lm.py (result.json, vocab.json, models) for --apply_lm."),
     (("--frontend",), str, "cpu", "Feature extraction of preprocess.py: cpu = the float64 numpy restatement, gpu = the HIP front end "
                                   "(las.frontend.FeatureExtractor, fp32)."),

@@ -30,7 +30,8 @@ class BeamState(object):
 
     def __init__(self, token_ids, log_prob, att, dec_state, lm_state):
         self._token_ids = token_ids             # a list, or (round 5, decode_batch's results) a (start id, numpy row) pair turned into the list on first use
-        self.log_prob = log_prob
+        self.log_prob = log_prob               # the search's score: the sum of the RANKED per-token scores -- with a hotword context
+        #                                        (las.bias) it includes the hypothesis' biasing bonus
         self.att = att
         self.dec_state = dec_state
         self.lm_state = lm_state
@@ -117,6 +118,12 @@ class BeamSearch(object):
         if self.ctc_weight > 0 and not getattr(args, "ctc", False):
             raise ValueError("--ctc_decode_weight %g needs the CTC head: decode with --ctc True (a model trained with --ctc)" % self.ctc_weight)
         self._las = las
+        # contextual biasing: --hotwords FILE --hotword_weight W; no file or weight 0 = off, and then none of its code runs.
+        # A weight > 0 without a file and a missing file are refused here, before anything is launched
+        self.context = None
+        if (getattr(args, "hotwords", "") or "") or float(getattr(args, "hotword_weight", 0.0) or 0.0) != 0.0:
+            from las import bias
+            self.set_context(bias.from_args(args))
         # decode_batch / decode_batches keep what align() needs of every batch in its results' `align_inputs` (off: nothing is retained --
         # the CTC log-probabilities are 410 MB at 64 utterances and V = 5000)
         self.retain_align = False
@@ -143,6 +150,14 @@ class BeamSearch(object):
         self.last_timing = None
         self._capture_stream = None
         self._tail_stream = None            # decode_batches: a batch's back-tracking and read-back run here, beside the next batch's search
+
+    def set_context(self, graph):
+        """the hotword context (las.bias.ContextGraph) of the searches that follow, or None: swapped between batches"""
+        if graph is not None and graph.child_tok.size and int(graph.child_tok.max()) >= self.args.vocab_size:
+            raise ValueError("set_context: the context holds token %d, the vocabulary has %d" % (int(graph.child_tok.max()), self.args.vocab_size))
+        if graph is not None and self.args.vocab_size > 16384:
+            raise ValueError("set_context: las_bias_step handles vocabularies up to 16384 tokens (got %d)" % self.args.vocab_size)
+        self.context = graph
 
     # -- model calls (the reference's sess.run wrappers, las/beam_search.py:203-246) -------------------
     def _get_encode(self, sess, audio, audiolen):
@@ -552,8 +567,21 @@ class BeamSearch(object):
             ctc_len = torch.tensor([int(x) for x in enc_lens], **i32)
             st_in.append(ctc_cur); st_out.append(ctc_par)
             ba.logits = joint.data_ptr()
+        ctx = self.context if (self.context is not None and self.context.active) else None
+        if ctx is not None:
+            # contextual biasing: las_bias_step advances every live row's trie node from its gathered parent `bias_par` into
+            # `bias_cur` and adds the candidates' gains to the scores the pruning ranks (the logits, or `joint`), in place; `bias_cur` follows
+            # its hypotheses through the gather.  Rows of 4 floats (the node is the first): a row of one float would take every state
+            # tensor of the gather off its 16-byte path
+            bias_w = 4
+            bias_tab = ctx.to(dev)
+            bias_par = torch.zeros(N, bias_w, device=dev)
+            bias_cur = torch.zeros(N, bias_w, device=dev)
+            bias_scores = joint if lam > 0 else logits
+            st_in.append(bias_cur); st_out.append(bias_par)
         if len(st_in) > 16:
-            raise ValueError("decode_batch: %d state tensors follow the hypotheses; las_beam_loop_step gathers at most 16" % len(st_in))
+            raise ValueError("decode_batch: %d state tensors follow the hypotheses (decoder and LM state, alignment, CTC and hotword state); "
+                             "las_beam_loop_step gathers at most 16" % len(st_in))
         ba.start_id, ba.end_id, ba.ntens = self.start_id, self.end_id, len(st_in)
         for k, (ti, to) in enumerate(zip(st_in, st_out)):
             ba.state_in[k], ba.state_out[k], ba.state_width[k] = ti.data_ptr(), to.data_ptr(), ti.shape[-1]
@@ -591,8 +619,8 @@ class BeamSearch(object):
         # rows + ONE cell launch) and the vocabulary projection -- the Speller's output layer and, concatenated along K, the LM's softmax
         # layer scaled by lm_weight and shifted to its token columns -- happens inside las_beam_loop_step: 5 launches per step instead of 8
         E_ = a.embedding_size
-        # (not with the CTC prefix scores: they are placed between the materialised logits and the pruning launch)
-        fused_proj = (lam == 0 and prec == _hip.PREC_BF16 and lstm and NL == 1 and self.fuse_projection and D % 32 == 0 and (E_ + Hd + D) % 32 == 0 and
+        # (not with the CTC prefix scores, nor with a hotword context: they are placed between the materialised logits and the pruning launch)
+        fused_proj = (ctx is None and lam == 0 and prec == _hip.PREC_BF16 and lstm and NL == 1 and self.fuse_projection and D % 32 == 0 and (E_ + Hd + D) % 32 == 0 and
                       ((beam + 15) // 16) * ((V_ + 15) // 16) <= 8 and (lm is None or (lm.hidden_size % 32 == 0 and "packs" in lm_plan)))
         proj_keep = None
         mode["fused"] = fused_proj
@@ -674,6 +702,13 @@ class BeamSearch(object):
                                                lam, _hip.p(ctc_par), _hip.p(ctc_cur), ctc_w, _hip.p(next_token), _hip.p(step),
                                                _hip.p(nlive), _hip.p(done), _hip.p(dstep), Umax, _hip.stream()), "las_ctc_prefix_step")
 
+        def bias_part():                                 # hotword state advance and bonus of the step (reads the device step counter)
+            _hip.check(lib.las_bias_step(_hip.p(bias_tab["child_off"]), _hip.p(bias_tab["child_tok"]), _hip.p(bias_tab["child_next"]),
+                                         _hip.p(bias_tab["gdef"]), _hip.p(bias_tab["groot"]), float(ctx.beta), ctx.num_nodes,
+                                         int(ctx.child_tok.size), _hip.p(bias_scores), n, beam, V_, _hip.p(bias_par), _hip.p(bias_cur), bias_w,
+                                         _hip.p(next_token), _hip.p(step), _hip.p(nlive), _hip.p(done), _hip.p(dstep), Umax, _hip.stream()),
+                       "las_bias_step")
+
         def beam_part():                                 # files alphas_cur under the device step counter, prunes, gathers, advances the counter
             _hip.check(lib.las_beam_loop_step(ctypes.byref(ba), _hip.stream()), "las_beam_loop_step")
 
@@ -685,6 +720,8 @@ class BeamSearch(object):
                 lm_part()
             if lam > 0:
                 ctc_part()
+            if ctx is not None:
+                bias_part()
             beam_part()
 
         steps_run = 0
@@ -768,10 +805,10 @@ class BeamSearch(object):
             live_steps = int((hist_n.sum(1) > 0).sum())              # steps in which some utterance still had a live hypothesis
             step.zero_()
             for name, fn in (("speller", speller_part), ("lm", lm_part if lm is not None else None),
-                             ("ctc", ctc_part if lam > 0 else None), ("beam", beam_part)):
+                             ("ctc", ctc_part if lam > 0 else None), ("bias", bias_part if ctx is not None else None), ("beam", beam_part)):
                 if fn is None:
                     continue
-                if name == "ctc":
+                if name in ("ctc", "bias"):
                     # every row live at a step > 0 (after the search every utterance is done and the kernel would return at once); the
                     # loop words are put back before the pruning part is timed
                     saved = (done.clone(), nlive.clone())
@@ -786,11 +823,11 @@ class BeamSearch(object):
                     e1.record()
                 torch.cuda.synchronize(dev)
                 parts[name] = round(e0.elapsed_time(e1) / 50 * 1e3, 2)
-                if name == "ctc":
+                if name in ("ctc", "bias"):
                     done.copy_(saved[0]); nlive.copy_(saved[1]); step.zero_()
             ks = list(tm)
             self.last_timing = {ks[i + 1]: round(tm[ks[i + 1]] - tm[ks[i]], 4) for i in range(len(ks) - 1)}
-            self.last_timing.update(steps=steps_run, live_steps=live_steps, rows=N, frames=Tp, graph=graph is not None, parts_us=parts)
+            self.last_timing.update(steps=steps_run, live_steps=live_steps, rows=N, frames=Tp, graph=graph is not None, short_form=bool(mode["fused"]), parts_us=parts)
             if self.args.verbose > 0:
                 print("decode_batch timing (s):", self.last_timing)
         return results

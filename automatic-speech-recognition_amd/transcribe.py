@@ -6,6 +6,7 @@
     python transcribe.py --ctc True --timestamps True a.wav ...        (one JSON object per line: text, score, word times)
     python transcribe.py --ctc True --align_text refs.txt a.wav ...    (forced alignment: line k of refs.txt is the transcript of file k)
     python transcribe.py --segment True meeting.wav ...                (long recordings: cut at the silences first, one line per file)
+    python transcribe.py --hotwords names.txt --hotword_weight 2.0 a.wav ...   (contextual biasing: the search boosts the listed phrases)
 
 With --timestamps the best hypothesis is aligned to the encoder frames by the CTC head (las.align, csrc/ctc_align.hip: a Viterbi pass
 over the head's log-probabilities) and every line is {"text", "score", "words": [{"word", "start", "end"}]}: times in seconds, None when
@@ -65,6 +66,7 @@ def main(argv=None):
         raise ValueError("--segment cuts the recordings, --align_text aligns one transcript per whole file: use one of them")
     if args.align_text is not None:
         args.timestamps = True
+        args.hotwords, args.hotword_weight = "", 0.0              # (no search: nothing to bias)
     if args.timestamps and not args.ctc:
         raise ValueError("--timestamps needs the CTC head: decode with --ctc True (a model trained with --ctc)")
     logging.basicConfig(stream=sys.stderr, format='%(asctime)s %(levelname)s:%(message)s', level=logging.INFO, datefmt='%I:%M:%S')

@@ -37,7 +37,7 @@ enum { LAS_ACT_NONE = 0, LAS_ACT_TANH = 1 };
 enum { LAS_ATT_ADD = 0, LAS_ATT_LOC = 1 };      /* las/las.py:44-49 */
 enum { LAS_DT_F32 = 0, LAS_DT_BF16 = 1 };       /* element type of a tensor in HBM (see las_gemm_kk) */
 
-#define LAS_HIP_ABI_VERSION 605      /* bumped whenever an argument struct or a signature changes: las_version() of a library
+#define LAS_HIP_ABI_VERSION 606      /* bumped whenever an argument struct or a signature changes: las_version() of a library
                                         built from another header differs, and the Python loader refuses it */
 int         las_version(void);
 const char* las_last_error(void);
@@ -619,7 +619,40 @@ int las_ctc_prefix_step(const float* lp, const int* enc_len, int nutt, int beam,
                         const int* dec_step, int Umax, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * K10d  CTC Viterbi (forced) alignment of a token sequence to the encoder frames: token and word times.  The max-plus form
+ * K10e  contextual biasing (hotword boosting) of the search by shallow fusion.  A context is a set of phrases (non-empty
+ * token-id sequences without SOS / PAD) with one per-token weight beta > 0, compiled on the host (las/bias.py, ContextGraph) into a
+ * token trie with node 0 = root.  depth(s); base(s) = depth of the deepest phrase-end node on the path root .. s (s included), 0 if
+ * none; pend(s) = fl32(beta) * fl32(depth(s) - base(s)) = the bonus paid out for a match that is not complete yet.  Tables:
+ *   child_off int32 [nnodes + 1], child_tok int32 [nchild] (ascending inside a node), child_next int32 [nchild] (rule 4 applied),
+ *   gdef fp32 [nnodes] = -pend, groot fp32 [nnodes] = fl32(beta - pend).
+ * Transition on token v from node s:  1. v is a child of s: t = child(s, v), gain beta;  2. else s != root and v is a child of the
+ * root: t = child(root, v), gain groot[s];  3. else t = root, gain gdef[s] (nothing, and no add, from the root);  4. a t that ends a
+ * phrase and has no children is the root, the bonus is kept (a phrase end WITH children stays, pend = 0).  EOS is an ordinary token.
+ * No fail links: an occurrence that starts inside a failed partial match, other than at the failing token, is not seen.
+ *
+ * las_bias_step: one search step, launched behind the step's logits (behind las_ctc_prefix_step when that runs) and in front of
+ * las_beam_loop_step; all arguments are fixed across the search (the step is read from *step: hipGraph friendly).  Live rows as for
+ * las_ctc_prefix_step: row = u * beam + j with j < nlive[u] (j = 0 at step 0); utterances with done[u] or *step >= dec_step[u], and
+ * every row once *step >= Umax, are skipped; rows that are not live are not written.  Per live row:
+ *   - state_in[row][0] is the gathered parent's node as a float (the root at step 0 whatever the buffer holds; a value outside
+ *     [0, nnodes) or not finite is the root); it is advanced by the entering token token[row] (outside [0, V): rule 3) and written to
+ *     state_out[row][0].  state_width floats per row, only the first is used (the search passes 4: rows of 16 bytes keep the 16-byte
+ *     path of las_beam_loop_step's gather for all the state tensors).
+ *   - scores [nutt * beam, V] (the logits, or las_ctc_prefix_step's joint scores) in place: scores[row][v] receives exactly one fp32
+ *     add of the gain of v from the advanced node, and none where the gain is 0; -inf stays -inf (a boosted token still has to make
+ *     the CTC bank by its attention logit).  A row at the root touches only the root's children; a row with pend != 0 makes one pass
+ *     over V.  The result is bit-identical to numpy float32 (tests/bias_ref.py).
+ * K10's note that the top-`topn` cut cannot bind while beam < topn still holds when the cut is read as a cut on the ranked, biased score.
+ * V <= 16384, nnodes <= 2^22, beta finite and > 0, state_in != state_out: refused (< 0, las_last_error) before anything is launched.
+ * No atomics: two runs give the same bits.
+ */
+int las_bias_step(const int* child_off, const int* child_tok, const int* child_next, const float* gdef, const float* groot,
+                  float beta, int nnodes, int nchild, float* scores, int nutt, int beam, int V, const float* state_in,
+                  float* state_out, int state_width, const int* token, const int* step, const int* nlive, const int* done,
+                  const int* dec_step, int Umax, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K10d CTC Viterbi (forced) alignment of a token sequence to the encoder frames: token and word times.  The max-plus form
  * of las_ctc_loss's extended-label recursion (states 0 .. 2L: blank, label 0, blank, ..., label L-1, blank) with a back-trace.
  *   lp           las_ctc_log_softmax's output, fp32 [n, Vc, Tp] class-major, blank = class Vc - 1
  *   enc_len [n]  frames of row u, clamped to [1, Tp] (as las_ctc_prefix_step)
