@@ -96,6 +96,9 @@ _EXTRA = [
     (("--hotwords",), str, "", "Contextual biasing (las.bias): a file with one phrase per line ('#' lines are comments) whose tokens the beam "
                                "search boosts; needs --hotword_weight > 0."),
     (("--hotword_weight",), float, 0.0, "Bonus per matched token of a --hotwords phrase, taken back when the match breaks (0: off)."),
+    (("--ngram_lm",), str, "", "N-gram LM shallow fusion (las.ngram): a back-off model over the model's own tokens in the ARPA text format "
+                               "(train_ngram.py writes one); needs --ngram_weight > 0."),
+    (("--ngram_weight",), float, 0.0, "Weight of the n-gram LM's natural-log probabilities in the beam search (0: off)."),
     (("--lm_dir",), str, "lang/output/", "Output directory of train_lm.py (result.json, vocab.json, models) for --apply_lm."),
     (("--frontend",), str, "cpu", "Feature extraction of preprocess.py: cpu = the float64 numpy restatement, gpu = the HIP front end "
                                   "(las.frontend.FeatureExtractor, fp32)."),

@@ -31,7 +31,8 @@ class BeamState(object):
     def __init__(self, token_ids, log_prob, att, dec_state, lm_state):
         self._token_ids = token_ids             # a list, or (round 5, decode_batch's results) a (start id, numpy row) pair turned into the list on first use
         self.log_prob = log_prob               # the search's score: the sum of the RANKED per-token scores -- with a hotword context
-        #                                        (las.bias) it includes the hypothesis' biasing bonus
+        #                                        (las.bias) it includes the hypothesis' biasing bonus, with an n-gram LM
+        #                                        (las.ngram) the weighted log-probability of every token
         self.att = att
         self.dec_state = dec_state
         self.lm_state = lm_state
@@ -124,6 +125,12 @@ class BeamSearch(object):
         if (getattr(args, "hotwords", "") or "") or float(getattr(args, "hotword_weight", 0.0) or 0.0) != 0.0:
             from las import bias
             self.set_context(bias.from_args(args))
+        # n-gram LM shallow fusion: --ngram_lm FILE --ngram_weight W; no file or weight 0 = off, and then none of its code
+        # runs.  A weight > 0 without a file, a missing file and a negative or non-finite weight are refused here
+        self.ngram, self.ngram_weight = None, 0.0
+        if (getattr(args, "ngram_lm", "") or "") or float(getattr(args, "ngram_weight", 0.0) or 0.0) != 0.0:
+            from las import ngram
+            self.set_ngram(ngram.from_args(args), float(args.ngram_weight))
         # decode_batch / decode_batches keep what align() needs of every batch in its results' `align_inputs` (off: nothing is retained --
         # the CTC log-probabilities are 410 MB at 64 utterances and V = 5000)
         self.retain_align = False
@@ -158,6 +165,18 @@ class BeamSearch(object):
         if graph is not None and self.args.vocab_size > 16384:
             raise ValueError("set_context: las_bias_step handles vocabularies up to 16384 tokens (got %d)" % self.args.vocab_size)
         self.context = graph
+
+    def set_ngram(self, lm, weight=0.0):
+        """the n-gram LM (las.ngram.NgramLM) and its weight for the searches that follow, or (None, 0): swapped between batches.  A model
+        with weight 0 is kept and stays off."""
+        w = float(weight)
+        if not np.isfinite(w) or w < 0:
+            raise ValueError("set_ngram: the weight must be finite and >= 0 (got %r)" % (weight,))
+        if lm is not None and lm.vocab_size != self.args.vocab_size:
+            raise ValueError("set_ngram: the LM is over %d tokens, the vocabulary has %d" % (lm.vocab_size, self.args.vocab_size))
+        if lm is not None and w > 0:
+            lm.tables(w)                    # (a weight that takes a table value out of float32 is refused here)
+        self.ngram, self.ngram_weight = lm, (w if lm is not None else 0.0)
 
     # -- model calls (the reference's sess.run wrappers, las/beam_search.py:203-246) -------------------
     def _get_encode(self, sess, audio, audiolen):
@@ -579,9 +598,19 @@ class BeamSearch(object):
             bias_cur = torch.zeros(N, bias_w, device=dev)
             bias_scores = joint if lam > 0 else logits
             st_in.append(bias_cur); st_out.append(bias_par)
+        ng = self.ngram if (self.ngram is not None and self.ngram_weight > 0) else None
+        if ng is not None:
+            # n-gram LM shallow fusion: las_ngram_step advances every live row's trie node from its gathered parent `ng_par`
+            # into `ng_cur` and adds the candidates' weighted log-probabilities to the logits, in place, in front of the CTC bank cut and
+            # the hotword bonus; `ng_cur` follows its hypotheses through the gather (rows of 4 floats, as the hotword state)
+            ng_w = 4
+            ng_tab = ng.to(dev, self.ngram_weight)
+            ng_par = torch.zeros(N, ng_w, device=dev)
+            ng_cur = torch.zeros(N, ng_w, device=dev)
+            st_in.append(ng_cur); st_out.append(ng_par)
         if len(st_in) > 16:
-            raise ValueError("decode_batch: %d state tensors follow the hypotheses (decoder and LM state, alignment, CTC and hotword state); "
-                             "las_beam_loop_step gathers at most 16" % len(st_in))
+            raise ValueError("decode_batch: %d state tensors follow the hypotheses (decoder and LM state, alignment, CTC, hotword and "
+                             "n-gram LM state); las_beam_loop_step gathers at most 16" % len(st_in))
         ba.start_id, ba.end_id, ba.ntens = self.start_id, self.end_id, len(st_in)
         for k, (ti, to) in enumerate(zip(st_in, st_out)):
             ba.state_in[k], ba.state_out[k], ba.state_width[k] = ti.data_ptr(), to.data_ptr(), ti.shape[-1]
@@ -619,8 +648,9 @@ class BeamSearch(object):
         # rows + ONE cell launch) and the vocabulary projection -- the Speller's output layer and, concatenated along K, the LM's softmax
         # layer scaled by lm_weight and shifted to its token columns -- happens inside las_beam_loop_step: 5 launches per step instead of 8
         E_ = a.embedding_size
-        # (not with the CTC prefix scores, nor with a hotword context: they are placed between the materialised logits and the pruning launch)
-        fused_proj = (ctx is None and lam == 0 and prec == _hip.PREC_BF16 and lstm and NL == 1 and self.fuse_projection and D % 32 == 0 and (E_ + Hd + D) % 32 == 0 and
+        # (not with the CTC prefix scores, a hotword context or an n-gram LM: they are placed between the materialised logits and the pruning
+        #  launch)
+        fused_proj = (ng is None and ctx is None and lam == 0 and prec == _hip.PREC_BF16 and lstm and NL == 1 and self.fuse_projection and D % 32 == 0 and (E_ + Hd + D) % 32 == 0 and
                       ((beam + 15) // 16) * ((V_ + 15) // 16) <= 8 and (lm is None or (lm.hidden_size % 32 == 0 and "packs" in lm_plan)))
         proj_keep = None
         mode["fused"] = fused_proj
@@ -702,6 +732,13 @@ class BeamSearch(object):
                                                lam, _hip.p(ctc_par), _hip.p(ctc_cur), ctc_w, _hip.p(next_token), _hip.p(step),
                                                _hip.p(nlive), _hip.p(done), _hip.p(dstep), Umax, _hip.stream()), "las_ctc_prefix_step")
 
+        def ngram_part():                                # n-gram state advance and LM scores of the step (reads the device step counter)
+            _hip.check(lib.las_ngram_step(_hip.p(ng_tab["child_off"]), _hip.p(ng_tab["child_tok"]), _hip.p(ng_tab["child_lp"]),
+                                          _hip.p(ng_tab["child_next"]), _hip.p(ng_tab["bow"]), _hip.p(ng_tab["bo"]), _hip.p(ng_tab["uni_lp"]),
+                                          _hip.p(ng_tab["uni_next"]), ng.num_nodes, ng.num_entries, ng.order, _hip.p(logits), n, beam, V_,
+                                          _hip.p(ng_par), _hip.p(ng_cur), ng_w, _hip.p(next_token), _hip.p(step), _hip.p(nlive),
+                                          _hip.p(done), _hip.p(dstep), Umax, _hip.stream()), "las_ngram_step")
+
         def bias_part():                                 # hotword state advance and bonus of the step (reads the device step counter)
             _hip.check(lib.las_bias_step(_hip.p(bias_tab["child_off"]), _hip.p(bias_tab["child_tok"]), _hip.p(bias_tab["child_next"]),
                                          _hip.p(bias_tab["gdef"]), _hip.p(bias_tab["groot"]), float(ctx.beta), ctx.num_nodes,
@@ -718,6 +755,8 @@ class BeamSearch(object):
             speller_part()
             if lm is not None:
                 lm_part()
+            if ng is not None:
+                ngram_part()
             if lam > 0:
                 ctc_part()
             if ctx is not None:
@@ -805,10 +844,11 @@ class BeamSearch(object):
             live_steps = int((hist_n.sum(1) > 0).sum())              # steps in which some utterance still had a live hypothesis
             step.zero_()
             for name, fn in (("speller", speller_part), ("lm", lm_part if lm is not None else None),
-                             ("ctc", ctc_part if lam > 0 else None), ("bias", bias_part if ctx is not None else None), ("beam", beam_part)):
+                             ("ngram", ngram_part if ng is not None else None), ("ctc", ctc_part if lam > 0 else None),
+                             ("bias", bias_part if ctx is not None else None), ("beam", beam_part)):
                 if fn is None:
                     continue
-                if name in ("ctc", "bias"):
+                if name in ("ngram", "ctc", "bias"):
                     # every row live at a step > 0 (after the search every utterance is done and the kernel would return at once); the
                     # loop words are put back before the pruning part is timed
                     saved = (done.clone(), nlive.clone())
@@ -823,7 +863,7 @@ class BeamSearch(object):
                     e1.record()
                 torch.cuda.synchronize(dev)
                 parts[name] = round(e0.elapsed_time(e1) / 50 * 1e3, 2)
-                if name in ("ctc", "bias"):
+                if name in ("ngram", "ctc", "bias"):
                     done.copy_(saved[0]); nlive.copy_(saved[1]); step.zero_()
             ks = list(tm)
             self.last_timing = {ks[i + 1]: round(tm[ks[i + 1]] - tm[ks[i]], 4) for i in range(len(ks) - 1)}

@@ -7,6 +7,7 @@
     python transcribe.py --ctc True --align_text refs.txt a.wav ...    (forced alignment: line k of refs.txt is the transcript of file k)
     python transcribe.py --segment True meeting.wav ...                (long recordings: cut at the silences first, one line per file)
     python transcribe.py --hotwords names.txt --hotword_weight 2.0 a.wav ...   (contextual biasing: the search boosts the listed phrases)
+    python transcribe.py --ngram_lm lm.arpa --ngram_weight 0.5 a.wav ...       (n-gram LM shallow fusion: train_ngram.py writes lm.arpa)
 
 With --timestamps the best hypothesis is aligned to the encoder frames by the CTC head (las.align, csrc/ctc_align.hip: a Viterbi pass
 over the head's log-probabilities) and every line is {"text", "score", "words": [{"word", "start", "end"}]}: times in seconds, None when
@@ -67,6 +68,7 @@ def main(argv=None):
     if args.align_text is not None:
         args.timestamps = True
         args.hotwords, args.hotword_weight = "", 0.0              # (no search: nothing to bias)
+        args.ngram_lm, args.ngram_weight = "", 0.0                # (... and nothing to fuse an LM into)
     if args.timestamps and not args.ctc:
         raise ValueError("--timestamps needs the CTC head: decode with --ctc True (a model trained with --ctc)")
     logging.basicConfig(stream=sys.stderr, format='%(asctime)s %(levelname)s:%(message)s', level=logging.INFO, datefmt='%I:%M:%S')

@@ -652,6 +652,38 @@ int las_bias_step(const int* child_off, const int* child_tok, const int* child_n
                   const int* dec_step, int Umax, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K10f  shallow fusion of a back-off n-gram language model into the search.  The model -- order n <= 6 over token ids
+ * [0, V), a log10 probability per stored n-gram and a log10 back-off weight per stored n-gram of order < n, dense unigrams -- is compiled
+ * on the host (las/ngram.py, NgramLM) into a trie with node 0 = root = the empty context; every stored n-gram of order 1 .. n - 1 is a
+ * node, highest-order n-grams are entries only.  Tables, every value PRE-SCALED on the host to fl32(w ln10 log10 x), one rounding:
+ *   child_off int32 [nnodes + 1] (the root's list is empty), child_tok int32 [nchild] (ascending inside a node), child_lp fp32 [nchild],
+ *   child_next int32 [nchild] = the node of the longest suffix of (context . token) that is a node,
+ *   bow fp32 [nnodes], bo int32 [nnodes] = the node of the longest proper suffix that is a node (the root's is the root),
+ *   uni_lp fp32 [V], uni_next int32 [V].
+ * Transition on token c from node p: descend p, bo(p), ... to the first node that has c as a child and take that entry's next; the root
+ * always has c (uni_next); a token outside [0, V) goes to the root.  At most `order` levels are descended before the root is taken.
+ *
+ * las_ngram_step: one search step, launched behind the step's logits (and the RNN LM's addition) and in front of las_ctc_prefix_step,
+ * las_bias_step and las_beam_loop_step, so that the CTC bank cut and the hotword bonus see LM-fused logits; all arguments are fixed
+ * across the search (the step is read from *step: hipGraph friendly).  Live rows exactly as for las_bias_step; rows that are not live
+ * are not written.  Per live row:
+ *   - state_in[row][0] is the gathered parent's node as a float (the root at step 0 whatever the buffer holds -- the entering token is
+ *     then SOS, so the state becomes <s>'s node; a value outside [0, nnodes) or NaN is the root); it is advanced by token[row] and
+ *     written to state_out[row][0].  state_width floats per row, only the first is used (the search passes 4, as for las_bias_step).
+ *   - scores [nutt * beam, V] (the logits) in place, over the chain s0 = s, s1 = bo(s0), ..., root with acc0 = 0: every child v of s_i
+ *     that no deeper level held gets scores[row][v] = fl32(scores[row][v] + fl32(acc_i + child_lp)); acc_{i+1} = fl32(acc_i +
+ *     bow[s_i]); at the root every remaining v takes uni_lp[v] the same way.  Two fp32 adds per token in this order, nothing
+ *     contracted; -inf stays -inf; EOS is an ordinary token.  The result is bit-identical to numpy float32 (tests/ngram_ref.py).
+ * Bounds: child ranges are clamped to [0, nchild), child tokens outside [0, V) are skipped, a next or bo outside [0, nnodes) is the root.
+ * 1 < V <= 16384, 1 <= nnodes <= 2^22, 1 <= order <= 6, state_in != state_out: refused (< 0, las_last_error) before anything is
+ * launched.  No atomics and no reductions: two runs give the same bits.
+ */
+int las_ngram_step(const int* child_off, const int* child_tok, const float* child_lp, const int* child_next, const float* bow,
+                   const int* bo, const float* uni_lp, const int* uni_next, int nnodes, int nchild, int order, float* scores,
+                   int nutt, int beam, int V, const float* state_in, float* state_out, int state_width, const int* token,
+                   const int* step, const int* nlive, const int* done, const int* dec_step, int Umax, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K10d CTC Viterbi (forced) alignment of a token sequence to the encoder frames: token and word times.  The max-plus form
  * of las_ctc_loss's extended-label recursion (states 0 .. 2L: blank, label 0, blank, ..., label L-1, blank) with a back-trace.
  *   lp           las_ctc_log_softmax's output, fp32 [n, Vc, Tp] class-major, blank = class Vc - 1
