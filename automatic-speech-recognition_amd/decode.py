@@ -1,5 +1,7 @@
 """decode.py -- beam-search evaluation entry point (counterpart of the reference's decode.py: utterances
-sorted by token length, one BeamSearch.decode per utterance, per-utterance and corpus WER, same log lines)."""
+sorted by token length, one BeamSearch.decode per utterance, per-utterance and corpus WER, same log lines).
+--mbr True scores the minimum-Bayes-risk hypothesis of every N-best list (las.nbest; posteriors at --nbest_scale) instead of the
+top-scoring one: the effect on the corpus WER is read from the same log lines."""
 import logging
 import os
 import sys
@@ -115,6 +117,11 @@ def main():
                 xs_list.append((audio[None], np.asarray([audio.shape[0]], np.int32)))
             yield xs_list
 
+    ann = None
+    if args.mbr:                                                   # (las.nbest is imported only when the flag is given)
+        from las import nbest as NB
+        args.nbest, args.confidence = 0, False                     # (transcribe.py's: nothing here prints them)
+        ann = NB.Annotator(args, bs.end_id)
     # the model's objects live as long as the process: out of the cyclic collector's way (a full collection walks them all, 30-60 ms --
     # a batch and a half -- every few batches otherwise)
     import gc
@@ -122,8 +129,10 @@ def main():
     gc.freeze()
     # decode_batches: the encoders of the next chunk run under the search of this one
     for chunk, results in zip(chunks, bs.decode_batches(None, batches())):
-        for i, beam_states in zip(chunk, results):
-            hyp = convert_idx_to_string(beam_states[-1].token_ids[1:], id_to_token, args.unit)
+        chosen = [r[-1] for r in results] if ann is None else [a["state"] if a["state"] is not None else r[-1]
+                                                               for a, r in zip(ann.annotate(results), results)]
+        for i, state in zip(chunk, chosen):
+            hyp = convert_idx_to_string(state.token_ids[1:], id_to_token, args.unit)
             ref = convert_idx_to_string(dev_tokens[i], id_to_token, args.unit)
             dist, n = edit_distance(ref.split(" "), hyp.split(" "))
             error += dist

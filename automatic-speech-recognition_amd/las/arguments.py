@@ -99,6 +99,12 @@ _EXTRA = [
     (("--ngram_lm",), str, "", "N-gram LM shallow fusion (las.ngram): a back-off model over the model's own tokens in the ARPA text format "
                                "(train_ngram.py writes one); needs --ngram_weight > 0."),
     (("--ngram_weight",), float, 0.0, "Weight of the n-gram LM's natural-log probabilities in the beam search (0: off)."),
+    # N-best consensus (las.nbest, csrc/nbest.hip): all off by default
+    (("--nbest",), int, 0, "transcribe.py: every JSON line lists the K best hypotheses with their posteriors (K <= --beam_size; 0: off)."),
+    (("--confidence",), str2bool, False, "transcribe.py: every JSON line carries the printed hypothesis' posterior and a confidence per word."),
+    (("--mbr",), str2bool, False, "Print the minimum-Bayes-risk hypothesis of the N-best list (least expected token edit distance under the "
+                                  "posteriors) instead of the top-scoring one."),
+    (("--nbest_scale",), float, 1.0, "Scale of the search's ranking key in the softmax that gives the N-best posteriors."),
     (("--lm_dir",), str, "lang/output/", "Output directory of train_lm.py (result.json, vocab.json, models) for --apply_lm."),
     (("--frontend",), str, "cpu", "Feature extraction of preprocess.py: cpu = the float64 numpy restatement, gpu = the HIP front end "
                                   "(las.frontend.FeatureExtractor, fp32)."),

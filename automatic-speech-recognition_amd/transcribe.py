@@ -8,6 +8,7 @@
     python transcribe.py --segment True meeting.wav ...                (long recordings: cut at the silences first, one line per file)
     python transcribe.py --hotwords names.txt --hotword_weight 2.0 a.wav ...   (contextual biasing: the search boosts the listed phrases)
     python transcribe.py --ngram_lm lm.arpa --ngram_weight 0.5 a.wav ...       (n-gram LM shallow fusion: train_ngram.py writes lm.arpa)
+    python transcribe.py --nbest 5 --confidence True --mbr True a.wav ...      (N-best consensus: alternatives, confidences, MBR choice)
 
 With --timestamps the best hypothesis is aligned to the encoder frames by the CTC head (las.align, csrc/ctc_align.hip: a Viterbi pass
 over the head's log-probabilities) and every line is {"text", "score", "words": [{"word", "start", "end"}]}: times in seconds, None when
@@ -20,6 +21,14 @@ dropped, runs over --max_segment_s -- the training cap -- cut at their quietest 
 goes through the front end and the search --decode_batch at a time, as files do otherwise.  A file's line is its segments' hypotheses
 joined by one space (an empty line for a silent file); with --timestamps it is {"text", "score", "words", "segments": [{"start", "end",
 "text", "score", "words"}]}: word times offset by the segment's start, score = the sum of the segment scores (None if one is None).
+
+With --nbest K, --confidence True or --mbr True (las.nbest, csrc/nbest.hip; any of them switches to JSON lines, none needs the CTC head)
+the search's whole ranked list is used: posteriors = softmax over the list of --nbest_scale x the search's ranking key; --nbest adds
+"nbest": [{"text", "score", "posterior"}], best first; --confidence adds "confidence" = the printed hypothesis' posterior and "words":
+[{"word", "confidence"}] (with --timestamps the same word objects carry start, end and confidence), a word's confidence = the least
+posterior mass that agrees with one of its tokens; --mbr prints the hypothesis of least expected token edit distance instead of the
+top-scoring one, and --timestamps / --confidence then describe that one.  Without --timestamps "score" is the search's score.  With
+--segment a file's confidence is the minimum over its segments, its words are concatenated and "nbest" stays with the segments.
 
 The files are read with preprocess.read_audio (.flac needs `soundfile`), `--decode_batch` of them at a time go through the device front
 end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip; a file at another rate than --sample_rate is resampled
@@ -53,6 +62,48 @@ def synthetic_audio(n, fs, seed):
     return [(0.1 * rng.randn(int(fs * rng.uniform(1.0, 3.0)))).astype(np.float32) for _ in range(n)]
 
 
+def annotated(args, bs, ann, results, id_to_token):
+    """--nbest / --confidence / --mbr: per utterance (tokens of the hypothesis to print, its score, its frame spans or None, the extra
+    JSON fields).  One consensus call for the batch (las.nbest.Annotator), and -- with --timestamps -- one alignment of the chosen
+    hypotheses; score = the alignment's with --timestamps (as without these flags), else the search's."""
+    from las import nbest as NB
+    notes = ann.annotate(results)
+    token_lists = [list(a["state"].token_ids[1:]) if a["state"] is not None else [] for a in notes]
+    if args.timestamps:
+        scores, spans = bs.align_results(results, token_lists)
+    else:
+        scores, spans = [float(a["state"].log_prob) if a["state"] is not None else None for a in notes], [None] * len(notes)
+    out = []
+    for a, tokens, score, span in zip(notes, token_lists, scores, spans):
+        extra = {}
+        if ann.confidence:
+            extra["confidence"] = a["posterior"]
+            extra["word_conf"] = NB.word_confidence(a["tokens"], a["conf"], id_to_token, args.unit)
+        if ann.nbest:
+            extra["nbest"] = [{"text": convert_idx_to_string(t, id_to_token, args.unit), "score": sc if np.isfinite(sc) else None,
+                               "posterior": p} for t, sc, p in a["nbest"]]
+        out.append((tokens, score, span, extra))
+    return out
+
+
+def json_fields(args, tokens, score, span, extra, id_to_token, frame_s, duration):
+    """the JSON object of one utterance (or segment) under --nbest / --confidence / --mbr: text, score, [confidence], [words], [nbest]"""
+    d = {"text": convert_idx_to_string(tokens, id_to_token, args.unit), "score": score if score is not None and np.isfinite(score) else None}
+    words = A.words(tokens, span, id_to_token, args.unit, frame_s, duration) if span is not None else None
+    if "word_conf" in extra:
+        d["confidence"] = extra["confidence"]
+        if words is None:
+            words = extra["word_conf"]
+        else:                                                          # (the same segmentation: the two lists zip)
+            for w, c in zip(words, extra["word_conf"]):
+                w["confidence"] = c["confidence"]
+    if words is not None:
+        d["words"] = words
+    if "nbest" in extra:
+        d["nbest"] = extra["nbest"]
+    return d
+
+
 def main(argv=None):
     import torch
     from decode import load_lm, restore_lm
@@ -71,6 +122,9 @@ def main(argv=None):
         args.ngram_lm, args.ngram_weight = "", 0.0                # (... and nothing to fuse an LM into)
     if args.timestamps and not args.ctc:
         raise ValueError("--timestamps needs the CTC head: decode with --ctc True (a model trained with --ctc)")
+    consensus = bool(args.nbest or args.confidence or args.mbr)
+    if consensus and args.align_text is not None:
+        raise ValueError("--nbest / --confidence / --mbr read the search's N-best list, --align_text skips the search: use one of them")
     logging.basicConfig(stream=sys.stderr, format='%(asctime)s %(levelname)s:%(message)s', level=logging.INFO, datefmt='%I:%M:%S')
     if not args.synthetic and not args.audio:
         parser.error("no audio files (or --synthetic True)")
@@ -102,6 +156,10 @@ def main(argv=None):
             restore_lm(lm, result['best_model'])
     if args.timestamps:
         bs.need_ctc_head("--timestamps")                              # (a checkpoint without the head: refused before any audio is read)
+    ann = None
+    if consensus:                                                      # (las.nbest is imported only when one of its flags is given)
+        from las import nbest as NB
+        ann = NB.Annotator(args, bs.end_id)
     fe = FeatureExtractor(args, device=dev)
     if args.synthetic and not args.audio:
         count = args.max_steps if args.max_steps >= 0 else 8
@@ -146,7 +204,7 @@ def main(argv=None):
                               "words": A.words(tokens, span, id_to_token, args.unit, frame_s, durations.popleft())}))
 
     if args.segment:
-        return transcribe_segmented(args, bs, fe, VAD.VoiceActivity(args, device=dev), load, count, nb, id_to_token, frame_s)
+        return transcribe_segmented(args, bs, fe, VAD.VoiceActivity(args, device=dev), load, count, nb, id_to_token, frame_s, ann)
     if texts is not None:
         # forced alignment: the listener and the head, no search
         done = 0
@@ -160,6 +218,10 @@ def main(argv=None):
         return
     bs.retain_align = bool(args.timestamps)
     for results in bs.decode_batches(None, batches()):
+        if ann is not None:
+            for tokens, score, span, extra in annotated(args, bs, ann, results, id_to_token):
+                print(json.dumps(json_fields(args, tokens, score, span, extra, id_to_token, frame_s, durations.popleft())))
+            continue
         if args.timestamps:
             token_lists = [list(r[-1].token_ids[1:]) if r else [] for r in results]
             timed_lines(token_lists, *bs.align_results(results, token_lists))
@@ -169,9 +231,10 @@ def main(argv=None):
     sys.stdout.flush()
 
 
-def transcribe_segmented(args, bs, fe, va, load, count, nb, id_to_token, frame_s):
+def transcribe_segmented(args, bs, fe, va, load, count, nb, id_to_token, frame_s, ann=None):
     """--segment: every file cut by las.vad at its own sample rate, the segments of all files as one stream through the front end and
-    the search, nb at a time (a batch may span files and rates); one output line per file, in file order"""
+    the search, nb at a time (a batch may span files and rates); one output line per file, in file order.  ann (--nbest / --confidence /
+    --mbr): JSON lines; a file's confidence is the minimum over its segments, its words are concatenated, nbest stays per segment"""
     files = collections.deque()                                        # [segments (start s, end s) of a file, its results so far]
 
     def batches():
@@ -199,6 +262,17 @@ def transcribe_segmented(args, bs, fe, va, load, count, nb, id_to_token, frame_s
         while files and len(files[0][1]) == len(files[0][0]):
             spans, done = files.popleft()
             text = " ".join(d["text"] for d in done)
+            if ann is not None:
+                scores = [d["score"] for d in done]
+                line = {"text": text, "score": None if any(x is None for x in scores) else float(sum(scores))}
+                if ann.confidence:
+                    conf = [d["confidence"] for d in done if d["confidence"] is not None]
+                    line["confidence"] = min(conf) if conf else None
+                if ann.confidence or args.timestamps:
+                    line["words"] = [w for d in done for w in d["words"]]
+                line["segments"] = done
+                print(json.dumps(line))
+                continue
             if not args.timestamps:
                 print(text)
                 continue
@@ -206,12 +280,18 @@ def transcribe_segmented(args, bs, fe, va, load, count, nb, id_to_token, frame_s
             print(json.dumps({"text": text, "score": None if any(x is None for x in scores) else float(sum(scores)),
                               "words": [w for d in done for w in d["words"]], "segments": done}))
 
-    def take(tokens, score=None, span=None):
+    def take(tokens, score=None, span=None, extra=None):
         emit_finished()                                                # (silent files in front of this segment's file)
         spans, done = files[0]                                         # results arrive in stream order: the first unfinished file
         t0, t1 = spans[len(done)]
         d = {"text": convert_idx_to_string(tokens, id_to_token, args.unit)}
-        if args.timestamps:
+        if extra is not None:
+            d = json_fields(args, tokens, score, span, extra, id_to_token, frame_s, t1 - t0)
+            for w in d.get("words", []) if args.timestamps else []:    # file time, clipped to the segment's end
+                if w["start"] is not None:
+                    w["start"], w["end"] = min(t0 + w["start"], t1), min(t0 + w["end"], t1)
+            d = dict([("start", t0), ("end", t1)] + list(d.items()))
+        elif args.timestamps:
             ws = A.words(tokens, span, id_to_token, args.unit, frame_s, t1 - t0)
             for w in ws:                                               # file time, clipped to the segment's end
                 if w["start"] is not None:
@@ -222,6 +302,10 @@ def transcribe_segmented(args, bs, fe, va, load, count, nb, id_to_token, frame_s
 
     bs.retain_align = bool(args.timestamps)
     for results in bs.decode_batches(None, batches()):
+        if ann is not None:
+            for tokens, score, span, extra in annotated(args, bs, ann, results, id_to_token):
+                take(tokens, score, span, extra)
+            continue
         token_lists = [list(r[-1].token_ids[1:]) if r else [] for r in results]
         if args.timestamps:
             for tokens, score, span in zip(token_lists, *bs.align_results(results, token_lists)):

@@ -707,6 +707,47 @@ int las_ctc_align(const float* lp, int Vc, int Tp, const int* enc_len, int n, co
                   int* first, int* last, int* frame_state, double* score, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K10g  consensus over the N-best list a search ends with: minimum-Bayes-risk choice and token confidences from the
+ * unit-cost Levenshtein distances and alignments among the hypotheses of an utterance.  Plain arguments, no struct (as las_ctc_align).
+ * A batch is n utterances with K hypothesis slots of at most U tokens:
+ *   tok  int32 [n, K, U]  token ids; positions at or beyond a length hold anything
+ *   len  int32 [n, K]     0 <= len <= U (clamped); an empty hypothesis is legal
+ *   nhyp int32 [n]        0 <= nhyp <= K (clamped); slots k >= nhyp[u] are absent: nothing of them is read but their len, nothing written
+ *   w    fp32  [n, K]     the posteriors, computed by the host (las/nbest.py); the kernels never exponentiate
+ *
+ * las_nbest_risk
+ *   dist int32 [n, K, K]  the Levenshtein distance of every two live slots (insertion, deletion, substitution cost 1): each unordered
+ *                         pair is computed once and both entries are written, the diagonal is 0; entries of absent slots are not written
+ *   risk fp32  [n, K]     risk[u, i] = sum_k w[u, k] * float(dist[u, i, k]) for live i, added in the order k = 0 .. nhyp - 1 from 0.f, the
+ *                         product and the sum separate fp32 operations (nothing contracted): bit-identical to sequential numpy float32
+ *   pick int32 [n]        the live slot of least risk; on equal risk the larger w, then the lower index (comparisons on the fp32 values as
+ *                         stored; a slot replaces the best so far only by risk < best or risk == best and w > best's); -1 where nhyp = 0
+ *
+ * las_nbest_confidence
+ *   pivot int32 [n]       DEVICE array (las_nbest_risk's pick can be passed straight in): the slot every hypothesis is aligned to; -1, or
+ *                         any value outside [0, nhyp[u]), writes nothing for the utterance
+ *   Every live hypothesis b is aligned to the pivot a by D[i][0] = i, D[0][j] = j, D[i][j] = min(D[i-1][j] + 1, D[i][j-1] + 1,
+ *   D[i-1][j-1] + (a[i-1] != b[j-1])), traced back from (len_a, len_b) by ONE rule at (i, j), checked in this order:
+ *     1. i, j > 0, a[i-1] == b[j-1] and D[i][j] == D[i-1][j-1]: a match, to (i-1, j-1);   2. i, j > 0 and D[i][j] == D[i-1][j-1] + 1: a
+ *     substitution, to (i-1, j-1);   3. i > 0 and D[i][j] == D[i-1][j] + 1: the pivot token stays unmatched, to (i-1, j);   4. to (i, j-1).
+ *   match int8 [n, K, U]  1 where pivot token i was matched in hypothesis k, else 0, for i < len of the pivot and live k (row k = pivot is
+ *                         all ones); entries at or beyond the pivot's length and rows of absent slots are not written
+ *   conf  fp32 [n, U]     conf[u, i] = sum_k w[u, k] * float(match[u, k, i]), same order and separate operations as risk; i < len of the pivot
+ *
+ * Both: integer outputs are exact, no atomics, one wavefront per dynamic programme whatever the batch, so two runs -- and the same
+ * utterance at another place in another batch -- give the same bits; the distances behind the two entry points come from one routine.
+ * CEILING: 1 <= U <= 1024 (a wave keeps the pivot's tokens and one boundary column of D in LDS; the search's Umax for a --max_segment_s
+ * = 17 s recording is 282), 1 <= K <= 64, n <= 65535.  Outside that, or with ws_bytes < las_nbest_workspace_bytes(n, K, U) (the packed
+ * 2-bit directions, n K ceil(U/16) 64 ceil(U/64) words; las_nbest_risk needs none), the call returns < 0 with a las_last_error text
+ * before anything is launched.  Two launches each on `stream`, no synchronisation.
+ */
+size_t las_nbest_workspace_bytes(int n, int K, int U);
+int las_nbest_risk(const int* tok, const int* len, const int* nhyp, const float* w, int n, int K, int U, int* dist, float* risk,
+                   int* pick, void* stream);
+int las_nbest_confidence(const int* tok, const int* len, const int* nhyp, const float* w, const int* pivot, int n, int K, int U,
+                         signed char* match, float* conf, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K10b device-resident BeamSearch.decode loop (las/beam_search.py:94-158) for `nutt` utterances at once: ONE call per
  * step prunes every utterance exactly as las_beam_step does AND keeps the reference's bookkeeping on the device, so
  * the host never waits inside the loop:
