@@ -236,6 +236,15 @@ _SIGS = {
     "las_vad_workspace_bytes": (c_size_t, [c_int, c_longlong]),
     "las_vad": (c_int, [c_void_p, c_int, c_longlong, c_void_p, POINTER(c_int), c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_int,
                         c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "las_reverb_tile": (c_int, []),
+    "las_reverb_tap_chunk": (c_int, []),
+    "las_reverb": (c_int, [c_void_p, c_longlong, c_void_p, POINTER(c_int), c_int, c_void_p, c_longlong, c_void_p, POINTER(c_int),
+                           c_void_p, POINTER(c_int), c_int, c_void_p, POINTER(c_int), c_void_p, c_longlong, c_void_p]),
+    "las_noise_mix_tile": (c_int, []),
+    "las_noise_mix_workspace_bytes": (c_size_t, [c_int, c_longlong]),
+    "las_noise_mix": (c_int, [c_void_p, c_longlong, c_void_p, POINTER(c_int), c_int, c_void_p, c_longlong, c_void_p, POINTER(c_int), c_int,
+                              c_void_p, POINTER(c_int), c_void_p, POINTER(c_int), c_void_p, POINTER(c_float),
+                              c_void_p, c_longlong, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -116,6 +116,18 @@ _EXTRA = [
     (("--specaug_time_masks",), int, 2, "SpecAugment: number of time masks."),
     (("--specaug_time_width",), int, 100, "SpecAugment: maximum time mask width in frames."),
     (("--specaug_time_ratio",), float, 1.0, "SpecAugment: a time mask covers at most this share of the utterance's frames."),
+    # multi-condition data (las.augment, csrc/wave_aug.hip): room reverberation and additive noise; all off by default
+    (("--rir_dir",), str, "", "Directory of room impulse responses (.wav / .npy, resampled to --sample_rate) for --noisy_copies."),
+    (("--noise_dir",), str, "", "Directory of background noise recordings (.wav / .npy, resampled to --sample_rate) for --noisy_copies."),
+    (("--rir_synthetic",), int, 0, "Add N synthetic room responses (seeded Gaussian tails, preprocess.synthetic_rir) to the response bank."),
+    (("--rt60",), str, "0.2,0.8", "lo,hi: the reverberation times in seconds of the --rir_synthetic responses are drawn from this range."),
+    (("--snr_range",), str, "5,20", "lo,hi: the signal-to-noise ratio in dB of every noisy utterance is drawn from this range."),
+    (("--reverb_prob",), float, 0.5, "Share of the utterances of a noisy copy that are reverberated."),
+    (("--noisy_copies",), int, 0, "preprocess.py --augmentation True: additionally write K reverberated / noisy copies of every train "
+                                  "split (noisy_<k>-feats.pkl, noisy_<k>-featlen.npy) beside the speed_* dumps (0: none)."),
+    (("--noise_file",), str, "", "transcribe.py: mix this recording into every file at --snr_db before it is transcribed."),
+    (("--snr_db",), float, 10.0, "transcribe.py: the signal-to-noise ratio in dB of --noise_file."),
+    (("--rir_file",), str, "", "transcribe.py: convolve every file with this room impulse response before it is transcribed."),
 ]
 
 

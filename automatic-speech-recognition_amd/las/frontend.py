@@ -218,7 +218,7 @@ class FeatureExtractor:
         return np.broadcast_to(a, (n,))
 
     # -- the device path ---------------------------------------------------------------------------------------------------------
-    def extract(self, waves, out=None, rate=None, speed=1.0, gain=None):
+    def extract(self, waves, out=None, rate=None, speed=1.0, gain=None, augment=None):
         """waves: list of 1-D numpy arrays / tensors, float or int16 (int16: value / 32767, as read_audio scales 16-bit files).
         -> (cube, lens): cube float32 on the device, [n, Tmax, feat_dim, 3] (with cmvn) or [n, Tmax, feat_dim] (without), zeros behind
         each utterance's frames; lens int32 frame counts on the host.  One upload, launches on the current stream, no synchronisation.
@@ -229,7 +229,10 @@ class FeatureExtractor:
         las_resample, one call per run of consecutive rows at one effective rate, into an fp32 sample buffer that las_frontend then
         reads (it takes one buffer): a row already at self.fs takes the L = M = 1 kernel, which filters nothing -- with no gain a
         bit copy, at the price of one more launch per such run.  Frame counts come from the resampled lengths, on the host, before
-        any launch."""
+        any launch.
+        augment: a las.augment.AugPlan (WaveAugmenter.plan) or None.  With a plan every row takes the resample path too (so the samples
+        are fp32), and the fp32 sample buffer then goes through las_reverb and las_noise_mix (one more small upload, up to four more
+        launches) before las_frontend reads it: room reverberation, then noise at the drawn SNR.  Lengths and frame counts do not change."""
         dev = torch.device(self.device if self.device is not None else "cuda")
         if dev.type != "cuda":
             raise RuntimeError("las.frontend needs a ROCm device (got %s); the CPU statement of the arithmetic is preprocess.process_audios" % dev)
@@ -250,7 +253,7 @@ class FeatureExtractor:
             if eff.min() < 1:
                 raise ValueError("effective sample rates %s" % (eff.tolist(),))
         gains = None if gain is None else self._per_row(gain, n, "gain", np.float32)
-        resampled = gains is not None or bool((eff != self.fs).any())
+        resampled = gains is not None or augment is not None or bool((eff != self.fs).any())
         ns_fe = ns
         if resampled:
             if int(ns.min()) < 1:
@@ -300,6 +303,11 @@ class FeatureExtractor:
                         gain=buf.data_ptr() + _align(4 * n) + 4 * u0 if gains is not None else None, n_out=rs.data_ptr() + 4 * u0)
                     u0 = u1
                 samples, n_samples, i16, ld = rs.data_ptr() + _align(4 * n), rs.data_ptr(), False, ld_fe
+                if augment is not None:
+                    if len(augment) != n or augment.augmenter.fs != self.fs:
+                        raise ValueError("augment: a plan of %d rows at %d Hz for %d utterances at %d Hz" % (len(augment), augment.augmenter.fs, n, self.fs))
+                    clean = rs[_align(4 * n):_align(4 * n) + 4 * n * ld_fe].view(torch.float32).view(n, ld_fe)
+                    samples = augment.augmenter.apply(clean, ns_fe, augment).data_ptr()
             ns_host = (ctypes.c_int * n)(*[int(x) for x in ns_fe])
             a = _hip.FrontendArgs(
                 samples=samples, samples_i16=int(i16), ld_samples=ld, n_samples=n_samples, n_samples_host=ns_host,

@@ -192,14 +192,137 @@ def speed_perturb(x, fs, speed, gain=1.0):
     return resample(x, int(round(fs * speed)), fs, gain)
 
 
-def process_audios(audio_path, args, speed=1.0):
+# ---- multi-condition data: room reverberation and additive noise (csrc/wave_aug.hip evaluates the same in fp32) ----------------------
+RIR_MAX = 16384                                                  # taps las_reverb takes (one second at 16 kHz)
+
+
+def rir_delay(h):
+    """the direct path of a room response: the index of the first sample of largest |h|"""
+    return int(np.argmax(np.abs(np.asarray(h, dtype=float))))
+
+
+def normalize_rir(h):
+    """h scaled in float64 to unit energy (sum h^2 = 1), so that reverberation does not change the level much"""
+    h = np.asarray(h, dtype=float)
+    e = float(np.sum(h * h))
+    if h.ndim != 1 or len(h) < 1 or not e > 0:
+        raise ValueError("a room response is a 1-D array with some energy")
+    return h / math.sqrt(e)
+
+
+def reverberate(x, h, delay):
+    """y[m] = sum_{k < K} h[k] x[m + delay - k] for m in [0, len(x)), x zero outside the recording: the output has the input's length
+    and the direct path (tap `delay`) does not shift the speech"""
+    x, h = np.asarray(x, dtype=float), np.asarray(h, dtype=float)
+    if x.ndim != 1 or h.ndim != 1 or len(h) < 1 or not 0 <= int(delay) < len(h):
+        raise ValueError("reverberate: 1-D arrays and 0 <= delay < len(h) (got %s, %s, %s)" % (x.shape, h.shape, delay))
+    if len(x) == 0:
+        return x.copy()
+    return np.convolve(x, h)[int(delay):int(delay) + len(x)]
+
+
+def _noise_segment(s, noise, offset):
+    s, noise = np.asarray(s, dtype=float), np.asarray(noise, dtype=float)
+    if s.ndim != 1 or noise.ndim != 1 or len(noise) < 1 or not 0 <= int(offset) < len(noise):
+        raise ValueError("mix_noise: 1-D arrays and 0 <= offset < len(noise) (got %s, %s, %s)" % (s.shape, noise.shape, offset))
+    return s, noise[(int(offset) + np.arange(len(s), dtype=np.int64)) % len(noise)]
+
+
+def noise_gain(s, noise, offset, snr_db):
+    """g = sqrt(Ps / (Pn 10^(snr_db / 10))) with Ps = mean(s^2) over the recording and Pn = mean(v^2) over the noise segment actually
+    used, v[m] = noise[(offset + m) mod len(noise)]; 0 when either is silent"""
+    s, v = _noise_segment(s, noise, offset)
+    if len(s) == 0:
+        return 0.0
+    Ps, Pn = float(np.mean(s * s)), float(np.mean(v * v))
+    if Ps == 0 or Pn == 0:
+        return 0.0
+    return math.sqrt(Ps / (Pn * 10.0 ** (float(snr_db) / 10.0)))
+
+
+def mix_noise(s, noise, offset, snr_db):
+    """y = s + g v, g = noise_gain(...): the noise, wrapped around, at snr_db under the recording; a silent recording or a silent
+    segment gives a copy of s"""
+    g = noise_gain(s, noise, offset, snr_db)
+    s, v = _noise_segment(s, noise, offset)
+    return s.copy() if g == 0 else s + g * v
+
+
+def synthetic_rir(fs, rt60, seed, length_s=None):
+    """a room response without a room: a unit direct path at sample 0 and, behind it, seeded Gaussian noise under an exponential
+    envelope that reaches -60 dB at rt60 seconds (Polack's model); length_s defaults to rt60, at most RIR_MAX taps"""
+    fs, rt60 = int(fs), float(rt60)
+    if fs < 1 or not rt60 > 0:
+        raise ValueError("synthetic_rir: fs=%d, rt60=%g" % (fs, rt60))
+    n = int(round(fs * (rt60 if length_s is None else float(length_s))))
+    n = min(max(n, 1), RIR_MAX)
+    t = np.arange(n, dtype=float) / fs
+    h = 0.1 * np.random.RandomState(int(seed)).randn(n) * 10.0 ** (-3.0 * t / rt60)      # amplitude x 10^-3 = -60 dB at t = rt60
+    h[0] = 1.0
+    return h
+
+
+def load_bank(path, fs):
+    """the .wav / .npy files of a directory (sorted by name) as float64 arrays at fs Hz: read_audio, first channel, resampled if need be"""
+    bank = []
+    for name in sorted(os.listdir(path)):
+        if name.endswith(".wav") or name.endswith(".npy"):
+            a, f = read_audio(os.path.join(path, name))
+            if a.ndim > 1:
+                a = a[:, 0]
+            bank.append(resample(a, int(f), int(fs)))
+    if not bank:
+        raise ValueError("no .wav / .npy files in %s" % path)
+    return bank
+
+
+def _pair(text, what):
+    lo, hi = (float(v) for v in str(text).split(","))
+    if hi < lo:
+        raise ValueError("%s is lo,hi (got %s)" % (what, text))
+    return lo, hi
+
+
+def wave_augmenter(args, device=None):
+    """the las.augment.WaveAugmenter of the --rir_dir / --rir_synthetic / --rt60 / --noise_dir / --snr_range / --reverb_prob flags (None
+    when they name no bank).  Its plan is drawn on the host: the CPU and the device front end augment from the same plan."""
+    from las.augment import WaveAugmenter
+    fs = int(args.sample_rate)
+    rirs = load_bank(args.rir_dir, fs) if args.rir_dir else []
+    if int(args.rir_synthetic) > 0:
+        lo, hi = _pair(args.rt60, "--rt60")
+        rng = np.random.RandomState(int(args.seed) + 7)
+        rirs = rirs + [synthetic_rir(fs, rng.uniform(lo, hi), int(args.seed) + 1000 + i) for i in range(int(args.rir_synthetic))]
+    noises = load_bank(args.noise_dir, fs) if args.noise_dir else []
+    if not rirs and not noises:
+        return None
+    return WaveAugmenter(fs, rirs=rirs or None, noises=noises or None, snr_db=_pair(args.snr_range, "--snr_range"), reverb_prob=args.reverb_prob,
+                         seed=int(args.seed), device=device)
+
+
+def augment_wave(audio, aug, plan, u):
+    """row u of a plan applied in float64: reverberate with the bank's (normalised) response, then mix_noise"""
+    if plan.rir_idx[u] >= 0:
+        h = aug.rirs[plan.rir_idx[u]]
+        audio = reverberate(audio, h, aug.rir_delay[plan.rir_idx[u]])
+    if plan.noise_idx[u] >= 0:
+        audio = mix_noise(audio, aug.noises[plan.noise_idx[u]], int(plan.noise_off[u]), float(plan.snr_db[u]))
+    return audio
+
+
+def process_audios(audio_path, args, speed=1.0, augment=None, step=0):
     """reference preprocess.py:50-91.  Returns (feats: list of float32 [L, feat_dim, 3] (or [L, feat_dim] without --cmvn), featlen).
-    speed != 1: every recording through speed_perturb first (the reference's speed augmentation, without the audio files between)."""
+    speed != 1: every recording through speed_perturb first (the reference's speed augmentation, without the audio files between).
+    augment (a las.augment.WaveAugmenter): recording u, brought to --sample_rate, takes row u of augment.plan(len(audio_path), step) in
+    float64 (augment_wave) -- the noisy copies of --noisy_copies."""
     feats, featlen = [], []
-    for p in audio_path:
+    plan = augment.plan(len(audio_path), step) if augment is not None else None
+    for u, p in enumerate(audio_path):
         audio, fs = read_audio(p)
         if speed != 1.0:
             audio = speed_perturb(audio, fs, speed)
+        if plan is not None:
+            audio, fs = augment_wave(resample(audio, fs, args.sample_rate), augment, plan, u), int(args.sample_rate)
         if args.feat_type == 'mfcc':
             feat = mfcc(audio, fs, frame_length=args.frame_length / 1000, frame_stride=args.frame_step / 1000, num_cepstral=args.feat_dim)
         elif args.feat_type == 'fbank':
@@ -214,20 +337,22 @@ def process_audios(audio_path, args, speed=1.0):
     return feats, featlen
 
 
-def process_audios_gpu(audio_path, args, batch=64, speed=1.0):
+def process_audios_gpu(audio_path, args, batch=64, speed=1.0, augment=None, step=0):
     """process_audios through the device front end: `batch` utterances per las_frontend call, the same lists of float32 arrays.  The
     kernels' tables are built for args.sample_rate: a file at another rate is resampled to it on the device (las_resample), and so is
-    every file when speed != 1 (speed_perturb's arithmetic in fp32)"""
+    every file when speed != 1 (speed_perturb's arithmetic in fp32).  augment: the rows [c0, c0 + batch) of the same plan the CPU
+    front end draws, applied by las_reverb and las_noise_mix between the resampler and the front end"""
     from las.frontend import FeatureExtractor
     fe = FeatureExtractor(args)
     feats, featlen = [], []
     for c0 in range(0, len(audio_path), batch):
+        plan = augment.plan(len(audio_path[c0:c0 + batch]), step, row0=c0, rows_global=len(audio_path)) if augment is not None else None
         waves, rates = [], []
         for p in audio_path[c0:c0 + batch]:
             audio, fs = read_audio(p)
             waves.append(audio)
             rates.append(int(fs))
-        cube, lens = fe.extract(waves, rate=rates, speed=speed)
+        cube, lens = fe.extract(waves, rate=rates, speed=speed) if plan is None else fe.extract(waves, rate=rates, speed=speed, augment=plan)
         cube = cube.cpu().numpy()
         for u, t in enumerate(lens):
             feats.append(cube[u, :t].copy())
@@ -289,6 +414,15 @@ def main():
                 joblib.dump(feats, os.path.join(args.feat_dir, "speed_%s-feats.pkl" % s))
                 np.save(os.path.join(args.feat_dir, "speed_%s-featlen.npy" % s), np.asarray(featlen))
                 print("speed_%s: %d utterances -> %s" % (s, len(feats), args.feat_dir))
+            if int(args.noisy_copies) > 0:                       # multi-condition copies: reverberation and noise, drawn per (seed, copy)
+                aug = wave_augmenter(args)
+                if aug is None:
+                    raise ValueError("--noisy_copies needs a bank: --rir_dir, --rir_synthetic N or --noise_dir")
+                for k in range(int(args.noisy_copies)):
+                    feats, featlen = process(audio_path, args, augment=aug, step=k)
+                    joblib.dump(feats, os.path.join(args.feat_dir, "noisy_%d-feats.pkl" % k))
+                    np.save(os.path.join(args.feat_dir, "noisy_%d-featlen.npy" % k), np.asarray(featlen))
+                    print("noisy_%d: %d utterances -> %s" % (k, len(feats), args.feat_dir))
 
 
 if __name__ == "__main__":

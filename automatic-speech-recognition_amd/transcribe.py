@@ -9,6 +9,7 @@
     python transcribe.py --hotwords names.txt --hotword_weight 2.0 a.wav ...   (contextual biasing: the search boosts the listed phrases)
     python transcribe.py --ngram_lm lm.arpa --ngram_weight 0.5 a.wav ...       (n-gram LM shallow fusion: train_ngram.py writes lm.arpa)
     python transcribe.py --nbest 5 --confidence True --mbr True a.wav ...      (N-best consensus: alternatives, confidences, MBR choice)
+    python transcribe.py --noise_file cafe.wav --snr_db 10 --rir_file room.wav a.wav ...   (the files as they would sound in that condition)
 
 With --timestamps the best hypothesis is aligned to the encoder frames by the CTC head (las.align, csrc/ctc_align.hip: a Viterbi pass
 over the head's log-probabilities) and every line is {"text", "score", "words": [{"word", "start", "end"}]}: times in seconds, None when
@@ -29,6 +30,11 @@ the search's whole ranked list is used: posteriors = softmax over the list of --
 posterior mass that agrees with one of its tokens; --mbr prints the hypothesis of least expected token edit distance instead of the
 top-scoring one, and --timestamps / --confidence then describe that one.  Without --timestamps "score" is the search's score.  With
 --segment a file's confidence is the minimum over its segments, its words are concatenated and "nbest" stays with the segments.
+
+With --noise_file and / or --rir_file (las.augment, csrc/wave_aug.hip) every recording is convolved with the room response and mixed
+with the noise at --snr_db on the device, between the resampler and the front end: a model's robustness checked without writing audio
+files.  The noise starts at its first sample and wraps around; both files are resampled to --sample_rate.  Without the two flags
+las.augment is not imported and the output is what it was.
 
 The files are read with preprocess.read_audio (.flac needs `soundfile`), `--decode_batch` of them at a time go through the device front
 end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip; a file at another rate than --sample_rate is resampled
@@ -161,6 +167,26 @@ def main(argv=None):
         from las import nbest as NB
         ann = NB.Annotator(args, bs.end_id)
     fe = FeatureExtractor(args, device=dev)
+    condition = None
+    if args.noise_file or args.rir_file:                               # (las.augment is imported only when one of its flags is given)
+        from las.augment import WaveAugmenter
+        from preprocess import resample
+
+        def bank(path):
+            a, fs = read_audio(path)
+            return [resample(a if a.ndim == 1 else a[:, 0], int(fs), int(args.sample_rate))]
+        if not np.isfinite(args.snr_db):
+            raise ValueError("--snr_db %s" % args.snr_db)
+        condition = WaveAugmenter(args.sample_rate, rirs=bank(args.rir_file) if args.rir_file else None,
+                                  noises=bank(args.noise_file) if args.noise_file else None, device=dev)
+
+    def extract(chunk):
+        waves, rates = [w for w, _ in chunk], [fs for _, fs in chunk]
+        if condition is None:
+            return fe.extract(waves, rate=rates)
+        plan = condition.fixed_plan(len(chunk), rir_idx=0 if args.rir_file else -1, noise_idx=0 if args.noise_file else -1, snr_db=args.snr_db)
+        return fe.extract(waves, rate=rates, augment=plan)
+
     if args.synthetic and not args.audio:
         count = args.max_steps if args.max_steps >= 0 else 8
         waves = synthetic_audio(count, args.sample_rate, args.seed + 2)
@@ -193,7 +219,7 @@ def main(argv=None):
             def make(chunk=chunk):
                 # called by decode_batches on the encoders' stream: one upload + three launches (one more per sample rate that is not
                 # --sample_rate), the cube never leaves the device
-                cube, lens = fe.extract([w for w, _ in chunk], rate=[fs for _, fs in chunk])
+                cube, lens = extract(chunk)
                 return [(cube[u:u + 1, :lens[u]], lens[u:u + 1]) for u in range(len(chunk))]
             yield make
 
@@ -204,7 +230,7 @@ def main(argv=None):
                               "words": A.words(tokens, span, id_to_token, args.unit, frame_s, durations.popleft())}))
 
     if args.segment:
-        return transcribe_segmented(args, bs, fe, VAD.VoiceActivity(args, device=dev), load, count, nb, id_to_token, frame_s, ann)
+        return transcribe_segmented(args, bs, extract, VAD.VoiceActivity(args, device=dev), load, count, nb, id_to_token, frame_s, ann)
     if texts is not None:
         # forced alignment: the listener and the head, no search
         done = 0
@@ -231,7 +257,7 @@ def main(argv=None):
     sys.stdout.flush()
 
 
-def transcribe_segmented(args, bs, fe, va, load, count, nb, id_to_token, frame_s, ann=None):
+def transcribe_segmented(args, bs, extract, va, load, count, nb, id_to_token, frame_s, ann=None):
     """--segment: every file cut by las.vad at its own sample rate, the segments of all files as one stream through the front end and
     the search, nb at a time (a batch may span files and rates); one output line per file, in file order.  ann (--nbest / --confidence /
     --mbr): JSON lines; a file's confidence is the minimum over its segments, its words are concatenated, nbest stays per segment"""
@@ -242,7 +268,7 @@ def transcribe_segmented(args, bs, fe, va, load, count, nb, id_to_token, frame_s
 
         def flush():
             def make(chunk=chunk[:]):
-                cube, lens = fe.extract([w for w, _ in chunk], rate=[fs for _, fs in chunk])
+                cube, lens = extract(chunk)
                 return [(cube[u:u + 1, :lens[u]], lens[u:u + 1]) for u in range(len(chunk))]
             del chunk[:]
             return make

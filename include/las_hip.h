@@ -967,6 +967,52 @@ int       las_vad(const void* samples, int samples_i16, long long ld_samples,
                   double* energy, double* emax, int* runs, int max_runs, int* n_runs,
                   void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K16  multi-condition training data between las_resample and las_frontend: a room impulse response convolved into every
+ * utterance, and background noise mixed in at a given signal-to-noise ratio.  Plain arguments, no struct (as las_vad).  The arithmetic
+ * is preprocess.reverberate's and preprocess.mix_noise's, in fp32.  Both entries APPLY per-utterance choices and draw nothing
+ * (las/augment.py draws on the host).  Every pointer but the *_host ones is a device pointer; a *_host array holds the same values
+ * on the host and is what the entry validates.
+ *
+ * las_reverb   out[u, m] = sum_{k = 0 .. K-1} h[k] * in[u, m + delay - k] for m < n_in[u], `in` zero outside [0, n_in[u]); h = rir[r],
+ *   K = rir_len[r], delay = rir_delay[r], r = rir_idx[u].  The output has the input's length and the direct path (tap `delay`) does
+ *   not shift it.  Direct-form FIR; SUMMATION ORDER: ONE fmaf chain per output, from +0, over the taps in ASCENDING k, followed by up to
+ *   15 zero taps (the last block of 16 taps is padded; they add +-0).  A row gives the bits it gives alone, and the same bits on every
+ *   call: the tile, the batch and the other rows' responses do not matter.  A row with rir_idx[u] = -1 is a bit copy of its input.
+ *   Every element of out [n, ld_out] is written, zeros behind n_in[u]; nothing behind n_in[u] is read.  One launch, no atomics.
+ *   in fp32 [n, ld_in]; rir fp32 [n_rir, ld_rir]; out fp32 [n, ld_out].  las_reverb_tile(): the consecutive outputs of one utterance a
+ *   workgroup owns; las_reverb_tap_chunk(): the taps it stages at a time.
+ *   Refused on the host before the launch (< 0, las_last_error): a NULL pointer; n outside 1..65535; n_rir < 1; a pitch outside
+ *   [1, INT32_MAX]; rir_len_host[r] outside [1, min(16384, ld_rir)]; rir_delay_host[r] outside [0, rir_len_host[r]); rir_idx_host[u]
+ *   outside [-1, n_rir); n_in_host[u] outside [1, min(ld_in, ld_out)]; in and out overlapping.
+ *
+ * las_noise_mix   v[m] = noise[r, (noise_off[u] + m) mod noise_len[r]], r = noise_idx[u] (the index in 64 bits);  Ps = mean of in^2 and
+ *   Pn = mean of v^2 over m < n_in[u], both fixed-order sums in double over the fp32 samples (per tile of las_noise_mix_tile() samples:
+ *   a thread's samples in ascending order, then a fixed tree; then the tiles the same way);  g = sqrt(Ps / (Pn 10^(snr_db[u] / 10))) in
+ *   double, rounded to fp32 once, 0 when Ps or Pn is 0;  out[u, m] = fmaf(g, v[m], in[u, m]).  A row with noise_idx[u] = -1 or g = 0 is
+ *   a bit copy of its input.  Every element of out is written, zeros behind n_in[u]; in == out (with equal pitches) is allowed.
+ *   gain_out fp32 [n] (g; 0 for rows without noise) may be NULL.  Three launches, no atomics: the same bits on every call, and a row
+ *   gives the bits it gives alone.  ws >= las_noise_mix_workspace_bytes(n, the longest n_in_host[u]) (any ld >= that will do), 8-byte
+ *   aligned.
+ *   Refused on the host before anything is launched: a NULL pointer (gain_out excepted); n outside 1..65535; n_noise < 1; a pitch
+ *   outside [1, INT32_MAX]; noise_len_host[r] outside [1, ld_noise]; noise_idx_host[u] outside [-1, n_noise); n_in_host[u] outside
+ *   [1, min(ld_in, ld_out)]; for a row with noise, noise_off_host[u] outside [0, noise_len) or snr_db_host[u] not finite; a workspace
+ *   that is too small; in and out overlapping without being the same buffer.
+ */
+int    las_reverb_tile(void);
+int    las_reverb_tap_chunk(void);
+int    las_reverb(const float* in, long long ld_in, const int* n_in, const int* n_in_host, int n,
+                  const float* rir, long long ld_rir, const int* rir_len, const int* rir_len_host,
+                  const int* rir_delay, const int* rir_delay_host, int n_rir,
+                  const int* rir_idx, const int* rir_idx_host, float* out, long long ld_out, void* stream);
+int    las_noise_mix_tile(void);
+size_t las_noise_mix_workspace_bytes(int n, long long ld);
+int    las_noise_mix(const float* in, long long ld_in, const int* n_in, const int* n_in_host, int n,
+                     const float* noise, long long ld_noise, const int* noise_len, const int* noise_len_host, int n_noise,
+                     const int* noise_idx, const int* noise_idx_host, const int* noise_off, const int* noise_off_host,
+                     const float* snr_db, const float* snr_db_host,
+                     float* out, long long ld_out, float* gain_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
