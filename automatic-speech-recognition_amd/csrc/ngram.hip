@@ -28,41 +28,15 @@
 // index outside its buffers.  No atomics and no reductions: two runs give the same bits, and numpy float32 gives them too
 // (tests/ngram_ref.py).
 #include "las_common.h"
+#include "ngram_trie.h"
 #include <math.h>
 
 namespace {
 
-constexpr int NGRAM_MAX_V = 16384;
-constexpr int NGRAM_MAX_NODES = 1 << 22;
-constexpr int NGRAM_MAX_ORDER = 6;
-
-struct NgramDev {
-    const int *child_off, *child_tok, *child_next, *bo, *uni_next; const float *child_lp, *bow, *uni_lp; int M, E, order;
+struct NgramDev : NgramTrie {                                          // (the tables and ngram_range / ngram_find / ngram_backoff: ngram_trie.h)
     float* scores; const float* st_in; float* st_out; const int *token, *step, *nlive, *done, *dec_step;
     int nutt, beam, V, width, Umax;
 };
-
-// the child list of node s as [lo, hi), inside [0, E) whatever the table holds
-__device__ __forceinline__ void ngram_range(const NgramDev& a, int s, int& lo, int& hi) {
-    lo = a.child_off[s]; hi = a.child_off[s + 1];
-    lo = lo < 0 ? 0 : (lo > a.E ? a.E : lo);
-    hi = hi < lo ? lo : (hi > a.E ? a.E : hi);
-}
-// position of token v in the sorted list [lo, hi), or -1
-__device__ __forceinline__ int ngram_find(const NgramDev& a, int lo, int hi, int v) {
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        const int tk = a.child_tok[mid];
-        if (tk == v) return mid;
-        if (tk < v) lo = mid + 1; else hi = mid;
-    }
-    return -1;
-}
-// bo[s], the root where the table holds no node
-__device__ __forceinline__ int ngram_backoff(const NgramDev& a, int s) {
-    const int q = a.bo[s];
-    return (q < 0 || q >= a.M) ? 0 : q;
-}
 
 __global__ __launch_bounds__(256) void ngram_step_kernel(NgramDev a) {
     __shared__ unsigned char mark[NGRAM_MAX_V];

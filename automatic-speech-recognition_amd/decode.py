@@ -64,6 +64,10 @@ def main():
     rank, world = (dp.rank, dp.world) if dp is not None else (0, 1)
     variables.reset_default_store(device=dev, seed=args.seed)
     las = LAS(args, Listener, Speller, token_to_id)
+    ctc_only = False
+    if args.decoder != "attention":                                # (las.ctc_search is imported only when the flag is given)
+        from las import ctc_search
+        ctc_only = ctc_search.check_args(args)
     lm = None
     if args.apply_lm:                                              # decode.py:68-75
         logging.info("Apply RNNLM...")
@@ -128,7 +132,8 @@ def main():
     gc.collect()
     gc.freeze()
     # decode_batches: the encoders of the next chunk run under the search of this one
-    for chunk, results in zip(chunks, bs.decode_batches(None, batches())):
+    search = bs.ctc_decode_batches if ctc_only else bs.decode_batches          # --decoder: the CTC head alone, or the Speller's search
+    for chunk, results in zip(chunks, search(None, batches())):
         chosen = [r[-1] for r in results] if ann is None else [a["state"] if a["state"] is not None else r[-1]
                                                                for a, r in zip(ann.annotate(results), results)]
         for i, state in zip(chunk, chosen):

@@ -99,6 +99,12 @@ _EXTRA = [
     (("--ngram_lm",), str, "", "N-gram LM shallow fusion (las.ngram): a back-off model over the model's own tokens in the ARPA text format "
                                "(train_ngram.py writes one); needs --ngram_weight > 0."),
     (("--ngram_weight",), float, 0.0, "Weight of the n-gram LM's natural-log probabilities in the beam search (0: off)."),
+    # CTC-only decoding (las.ctc_search, csrc/ctc_search.hip): the default is the Speller's search
+    (("--decoder",), str, "attention", "Search of transcribe.py / decode.py: attention = the Speller's beam search; ctc = the CTC head alone "
+                                       "(needs --ctc True): --beam_size 1 is the greedy collapse, > 1 the prefix beam search, with "
+                                       "--ngram_lm fused."),
+    (("--ctc_cand",), int, 32, "--decoder ctc: classes of largest logit a frame offers the prefix beam search (at most 64)."),
+    (("--ctc_len_bonus",), float, 0.0, "--decoder ctc: added to the score of every token the prefix beam search appends."),
     # N-best consensus (las.nbest, csrc/nbest.hip): all off by default
     (("--nbest",), int, 0, "transcribe.py: every JSON line lists the K best hypotheses with their posteriors (K <= --beam_size; 0: off)."),
     (("--confidence",), str2bool, False, "transcribe.py: every JSON line carries the printed hypothesis' posterior and a confidence per word."),

@@ -385,6 +385,10 @@ class BeamSearch(object):
     def _ctc_log_probs(self, encs, h_one):
         """The CTC head over the encoder frames of a batch (las/las.py:75-77, the product of _CTCHead.forward through las_gemm), then
         las_ctc_log_softmax: class-major log-probabilities [n, V + 1, T'] (frames past T'_u hold values nobody reads)."""
+        return self._ctc_class_major(self._ctc_logits(encs, h_one))
+
+    def _ctc_logits(self, encs, h_one):
+        """the head product alone: frame-major logits [n, T', V + 1] (what the CTC-only search reads, las.ctc_search)"""
         dev = self._las._device()
         P = self.speller._params(head=True)
         Wc, bc = P["Wc"].detach(), P["bc"].detach()
@@ -399,7 +403,11 @@ class BeamSearch(object):
                 enc[u, :Tps[u]] = h[0]
         z = torch.empty(n, Tp, Vc, device=dev)
         _hip.gemm(L._prec(), enc, Wc, z, False, False, n * Tp, Vc, Hd, Hd, Vc, Vc, bias=bc)
-        lp = torch.empty(n, Vc, Tp, device=dev)
+        return z
+
+    def _ctc_class_major(self, z):
+        n, Tp, Vc = z.shape
+        lp = torch.empty(n, Vc, Tp, device=z.device)
         _hip.check(_hip.lib().las_ctc_log_softmax(_hip.p(z), n, Tp, Vc, _hip.p(lp), _hip.stream()), "las_ctc_log_softmax")
         return lp
 
@@ -431,6 +439,17 @@ class BeamSearch(object):
         if token_lists is None:
             token_lists = [list(r[-1].token_ids[1:]) if r else [] for r in results]
         return self.align(k.encs, k.enc_lens, token_lists, h_one=k.h_one, ctc_lp=k.ctc_lp)
+
+    def ctc_decode_batch(self, sess, xs_list):
+        """`--decoder ctc`: the transcripts of a batch from the CTC head alone -- encoders, head product, greedy collapse
+        (beam_size 1) or CTC prefix beam search with the n-gram of set_ngram (las.ctc_search) -- as decode_batch's result lists.  No
+        Speller step runs."""
+        from las import ctc_search
+        return ctc_search.decode_batch(self, sess, xs_list)
+
+    def ctc_decode_batches(self, sess, batches):
+        from las import ctc_search
+        return ctc_search.decode_batches(self, sess, batches)
 
     def decode_batch(self, sess, xs_list, sync_every=32, _pre=None, _after_launch=None, _defer=False):
         """Beam search for several utterances at once (what decode.py's loop over utterances, decode.py:131-149, becomes on

@@ -9,6 +9,7 @@
     python transcribe.py --hotwords names.txt --hotword_weight 2.0 a.wav ...   (contextual biasing: the search boosts the listed phrases)
     python transcribe.py --ngram_lm lm.arpa --ngram_weight 0.5 a.wav ...       (n-gram LM shallow fusion: train_ngram.py writes lm.arpa)
     python transcribe.py --nbest 5 --confidence True --mbr True a.wav ...      (N-best consensus: alternatives, confidences, MBR choice)
+    python transcribe.py --ctc True --decoder ctc --beam_size 16 a.wav ...     (the CTC head alone: prefix beam search, greedy with --beam_size 1)
     python transcribe.py --noise_file cafe.wav --snr_db 10 --rir_file room.wav a.wav ...   (the files as they would sound in that condition)
 
 With --timestamps the best hypothesis is aligned to the encoder frames by the CTC head (las.align, csrc/ctc_align.hip: a Viterbi pass
@@ -126,6 +127,10 @@ def main(argv=None):
         args.timestamps = True
         args.hotwords, args.hotword_weight = "", 0.0              # (no search: nothing to bias)
         args.ngram_lm, args.ngram_weight = "", 0.0                # (... and nothing to fuse an LM into)
+    ctc_only = False
+    if args.decoder != "attention":                                    # (las.ctc_search is imported only when the flag is given)
+        from las import ctc_search
+        ctc_only = ctc_search.check_args(args) and args.align_text is None
     if args.timestamps and not args.ctc:
         raise ValueError("--timestamps needs the CTC head: decode with --ctc True (a model trained with --ctc)")
     consensus = bool(args.nbest or args.confidence or args.mbr)
@@ -187,6 +192,7 @@ def main(argv=None):
         plan = condition.fixed_plan(len(chunk), rir_idx=0 if args.rir_file else -1, noise_idx=0 if args.noise_file else -1, snr_db=args.snr_db)
         return fe.extract(waves, rate=rates, augment=plan)
 
+    search = bs.ctc_decode_batches if ctc_only else bs.decode_batches  # --decoder: the CTC head alone, or the Speller's search
     if args.synthetic and not args.audio:
         count = args.max_steps if args.max_steps >= 0 else 8
         waves = synthetic_audio(count, args.sample_rate, args.seed + 2)
@@ -230,7 +236,8 @@ def main(argv=None):
                               "words": A.words(tokens, span, id_to_token, args.unit, frame_s, durations.popleft())}))
 
     if args.segment:
-        return transcribe_segmented(args, bs, extract, VAD.VoiceActivity(args, device=dev), load, count, nb, id_to_token, frame_s, ann)
+        return transcribe_segmented(args, bs, extract, VAD.VoiceActivity(args, device=dev), load, count, nb, id_to_token, frame_s, ann,
+                                    search)
     if texts is not None:
         # forced alignment: the listener and the head, no search
         done = 0
@@ -243,7 +250,7 @@ def main(argv=None):
         sys.stdout.flush()
         return
     bs.retain_align = bool(args.timestamps)
-    for results in bs.decode_batches(None, batches()):
+    for results in search(None, batches()):
         if ann is not None:
             for tokens, score, span, extra in annotated(args, bs, ann, results, id_to_token):
                 print(json.dumps(json_fields(args, tokens, score, span, extra, id_to_token, frame_s, durations.popleft())))
@@ -257,7 +264,7 @@ def main(argv=None):
     sys.stdout.flush()
 
 
-def transcribe_segmented(args, bs, extract, va, load, count, nb, id_to_token, frame_s, ann=None):
+def transcribe_segmented(args, bs, extract, va, load, count, nb, id_to_token, frame_s, ann=None, search=None):
     """--segment: every file cut by las.vad at its own sample rate, the segments of all files as one stream through the front end and
     the search, nb at a time (a batch may span files and rates); one output line per file, in file order.  ann (--nbest / --confidence /
     --mbr): JSON lines; a file's confidence is the minimum over its segments, its words are concatenated, nbest stays per segment"""
@@ -327,7 +334,7 @@ def transcribe_segmented(args, bs, extract, va, load, count, nb, id_to_token, fr
         emit_finished()
 
     bs.retain_align = bool(args.timestamps)
-    for results in bs.decode_batches(None, batches()):
+    for results in (search or bs.decode_batches)(None, batches()):
         if ann is not None:
             for tokens, score, span, extra in annotated(args, bs, ann, results, id_to_token):
                 take(tokens, score, span, extra)

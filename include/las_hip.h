@@ -684,6 +684,40 @@ int las_ngram_step(const int* child_off, const int* child_tok, const float* chil
                    const int* step, const int* nlive, const int* done, const int* dec_step, int Umax, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K10h CTC-only decoding: greedy and prefix beam search over the CTC head's logits, without the Speller.  Classes as in
+ * K10c: Vc = V + 1, blank = class V.  enc_len int32 [n] (device) = T'_u, clamped to [0, Tp]; frames t >= T'_u are neither read nor written.
+ *
+ * las_ctc_frame_topk: logits fp32 [n, Tp, Vc] frame-major (the head product, before any softmax) ->
+ *   best int32 [n, Tp]        the argmax class over all Vc, ties to the lower id;       best_lp fp32 [n, Tp]   its z - lse
+ *   cand_tok int32 [n, Tp, C] the C non-blank classes of largest logit (ties to the lower id), LISTED IN ASCENDING TOKEN ID
+ *   cand_lp fp32 [n, Tp, C]   their z - lse;                                            blank_lp fp32 [n, Tp]  the blank's
+ *   lse = m + logf(sum expf(z - m)).  0 <= C <= min(64, V); C = 0 selects no candidates (cand_tok / cand_lp may be NULL).  The integer outputs are read off
+ *   the raw logits: they do not depend on libm.
+ * las_ctc_greedy: best / best_lp as above -> tokens int32 [n, Tp] (best[t] where it is not `blank` and differs from best[t - 1]; entries
+ *   beyond lens[u] are not written), lens int32 [n], scores fp64 [n] = the sum of best_lp over the frames, in frame order.
+ * las_ctc_beam_search: cand_tok / cand_lp / blank_lp as above -> per utterance up to K hypotheses, best first:
+ *   tokens int32 [n, K, Tp], lens int32 [n, K], totals fp32 [n, K] = log(p_b + p_nb), nhyp int32 [n]; nothing is written beyond
+ *   nhyp[u] or beyond a length.  The standard CTC prefix beam search; a prefix whose last token is `eos` is closed (never extended);
+ *   a new token adds g = lm + len_bonus, lm = the pre-scaled back-off score las_ngram_step would add for it from the prefix' node
+ *   (tables as K10f; nnodes = 0 and NULL tables: no n-gram, lm = 0; lm_start = the node of <SOS>).  Mass at or below -1e10 is no mass.
+ *   Pruning keeps the K largest totals; ties: entries already in the beam in slot order, then extensions by (parent slot, candidate
+ *   position).  Candidate tokens outside [0, V) are skipped; the n-gram bounds are K10f's.
+ *   ws: las_ctc_beam_workspace_bytes(n, Tp, K, C) bytes (a prefix trie of K Tp + 1 nodes and its (parent, token) table per utterance).
+ * 1 <= K <= 64, 1 <= C <= min(64, V), with an n-gram K10f's limits, a workspace of the full size: otherwise < 0 with a las_last_error
+ * text before anything is launched.  No atomics: two runs give the same bits.  One launch each on `stream`, no synchronisation.
+ */
+int las_ctc_frame_topk(const float* logits, const int* enc_len, int n, int Tp, int Vc, int C, int* cand_tok, float* cand_lp,
+                       float* blank_lp, int* best, float* best_lp, void* stream);
+int las_ctc_greedy(const int* best, const float* best_lp, const int* enc_len, int n, int Tp, int blank, int* tokens, int* lens,
+                   double* scores, void* stream);
+size_t las_ctc_beam_workspace_bytes(int n, int Tp, int K, int C);
+int las_ctc_beam_search(const int* cand_tok, const float* cand_lp, const float* blank_lp, const int* enc_len, int n, int Tp, int V,
+                        int K, int C, int eos, float len_bonus, const int* child_off, const int* child_tok, const float* child_lp,
+                        const int* child_next, const float* bow, const int* bo, const float* uni_lp, const int* uni_next, int nnodes,
+                        int nchild, int order, int lm_start, int* tokens, int* lens, float* totals, int* nhyp, void* ws,
+                        size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K10d CTC Viterbi (forced) alignment of a token sequence to the encoder frames: token and word times.  The max-plus form
  * of las_ctc_loss's extended-label recursion (states 0 .. 2L: blank, label 0, blank, ..., label L-1, blank) with a back-trace.
  *   lp           las_ctc_log_softmax's output, fp32 [n, Vc, Tp] class-major, blank = class Vc - 1
