@@ -65,7 +65,7 @@ def main():
     variables.reset_default_store(device=dev, seed=args.seed)
     las = LAS(args, Listener, Speller, token_to_id)
     ctc_only = False
-    if args.decoder != "attention":                                # (las.ctc_search is imported only when the flag is given)
+    if args.decoder != "attention" or args.rescore != "none":      # (las.ctc_search is imported only when one of the flags is given)
         from las import ctc_search
         ctc_only = ctc_search.check_args(args)
     lm = None

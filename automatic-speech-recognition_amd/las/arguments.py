@@ -105,6 +105,12 @@ _EXTRA = [
                                        "--ngram_lm fused."),
     (("--ctc_cand",), int, 32, "--decoder ctc: classes of largest logit a frame offers the prefix beam search (at most 64)."),
     (("--ctc_len_bonus",), float, 0.0, "--decoder ctc: added to the score of every token the prefix beam search appends."),
+    # two-pass decoding (las.rescore, csrc/rescore.hip): off by default
+    (("--rescore",), str, "none", "--decoder ctc: none, or attention = the Speller scores the prefix beam search's hypotheses under teacher "
+                                  "forcing and the list is re-ranked (needs --beam_size > 1)."),
+    (("--rescore_ctc_weight",), float, 0.5, "--rescore attention: a hypothesis ranks by (1 - w) x attention log-likelihood + w x CTC search "
+                                            "score, w inside [0, 1]."),
+    (("--rescore_rows",), int, 64, "--rescore attention: hypotheses per teacher-forced Speller call (1 to 1024)."),
     # N-best consensus (las.nbest, csrc/nbest.hip): all off by default
     (("--nbest",), int, 0, "transcribe.py: every JSON line lists the K best hypotheses with their posteriors (K <= --beam_size; 0: off)."),
     (("--confidence",), str2bool, False, "transcribe.py: every JSON line carries the printed hypothesis' posterior and a confidence per word."),

@@ -447,6 +447,13 @@ class BeamSearch(object):
         from las import ctc_search
         return ctc_search.decode_batch(self, sess, xs_list)
 
+    def score_hypotheses(self, encs, enc_lens, token_lists, rows=64, return_steps=False):
+        """The attention decoder's log-likelihood of given transcripts: encs / enc_lens as _run_encoders returns them,
+        token_lists[u] = token lists of utterance u (no <SOS>) -> scores[u][k]: the teacher-forced Speller over chunks of `rows`
+        hypotheses and las_rescore_score on its logits.  A list is scored through its first EOS, or with one appended."""
+        from las import rescore
+        return rescore.attention_scores(self, encs, enc_lens, token_lists, rows, return_steps)
+
     def ctc_decode_batches(self, sess, batches):
         from las import ctc_search
         return ctc_search.decode_batches(self, sess, batches)

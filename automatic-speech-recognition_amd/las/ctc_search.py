@@ -11,6 +11,8 @@ from las import _hip
 MAX_BEAM = 64
 MAX_CAND = 64
 DECODERS = ("attention", "ctc")
+RESCORERS = ("none", "attention")
+MAX_RESCORE_ROWS = 1024
 
 
 def check_args(args, force=False):
@@ -19,7 +21,10 @@ def check_args(args, force=False):
     dec = str(getattr(args, "decoder", "attention") or "attention").lower()
     if dec not in DECODERS:
         raise ValueError("--decoder %r: one of %s" % (dec, " | ".join(DECODERS)))
+    res = rescorer(args)
     if dec != "ctc" and not force:
+        if res != "none":
+            raise ValueError("--rescore %s re-ranks the CTC search's N-best list: it needs --decoder ctc" % res)
         return False
     if not getattr(args, "ctc", False):
         raise ValueError("--decoder ctc needs the CTC head: decode with --ctc True (a model trained with --ctc)")
@@ -38,7 +43,24 @@ def check_args(args, force=False):
     _cand_flag(args)
     if not np.isfinite(float(getattr(args, "ctc_len_bonus", 0.0) or 0.0)):
         raise ValueError("--ctc_len_bonus must be finite")
+    if res != "none":
+        if K == 1:
+            raise ValueError("--rescore %s --beam_size 1: the greedy collapse gives one hypothesis, nothing to re-rank" % res)
+        w = float(getattr(args, "rescore_ctc_weight", 0.5))
+        if not np.isfinite(w) or not 0.0 <= w <= 1.0:
+            raise ValueError("--rescore_ctc_weight inside [0, 1] (got %r)" % (w,))
+        rows = int(getattr(args, "rescore_rows", 64))
+        if not 1 <= rows <= MAX_RESCORE_ROWS:
+            raise ValueError("--rescore_rows between 1 and %d (got %d)" % (MAX_RESCORE_ROWS, rows))
     return True
+
+
+def rescorer(args):
+    """--rescore: none | attention"""
+    res = str(getattr(args, "rescore", "none") or "none").lower()
+    if res not in RESCORERS:
+        raise ValueError("--rescore %r: one of %s" % (res, " | ".join(RESCORERS)))
+    return res
 
 
 def _cand_flag(args):
@@ -161,6 +183,9 @@ def decode_batch(bs, sess, xs_list):
             hyps = beam_search(z, T, K, cand(args), bs.end_id, bs.ngram, bs.ngram_weight, float(getattr(args, "ctc_len_bonus", 0.0) or 0.0),
                                bs.start_id)
     _hip.check_status(z.device)
+    if rescorer(args) != "none":                                       # the second pass (las.rescore is imported only here)
+        from las import rescore
+        return rescore.rescored_results(bs, encs, enc_lens, hyps, AlignInputs(encs, enc_lens, h_one, ctc_lp) if bs.retain_align else None)
     results = _Results([BeamState([bs.start_id] + list(tokens), np.float32(score) if K > 1 else score, [], None, None)
                         for tokens, score in reversed(hs)] for hs in hyps)
     results.align_inputs = AlignInputs(encs, enc_lens, h_one, ctc_lp) if bs.retain_align else None

@@ -81,7 +81,8 @@ def annotated(args, bs, ann, results, id_to_token):
     else:
         scores, spans = [float(a["state"].log_prob) if a["state"] is not None else None for a in notes], [None] * len(notes)
     out = []
-    for a, tokens, score, span in zip(notes, token_lists, scores, spans):
+    rescored = getattr(results, "rescored", None)                      # --rescore attention: both passes' scores of every listed hypothesis
+    for u, (a, tokens, score, span) in enumerate(zip(notes, token_lists, scores, spans)):
         extra = {}
         if ann.confidence:
             extra["confidence"] = a["posterior"]
@@ -89,6 +90,10 @@ def annotated(args, bs, ann, results, id_to_token):
         if ann.nbest:
             extra["nbest"] = [{"text": convert_idx_to_string(t, id_to_token, args.unit), "score": sc if np.isfinite(sc) else None,
                                "posterior": p} for t, sc, p in a["nbest"]]
+            if rescored is not None:
+                for j, e in enumerate(extra["nbest"]):                 # (the list is best first, the results ascend)
+                    d = rescored[u][len(rescored[u]) - 1 - j]
+                    e["ctc_score"], e["att_score"] = (x if np.isfinite(x) else None for x in (d["first"], d["att"]))
         out.append((tokens, score, span, extra))
     return out
 
@@ -128,7 +133,7 @@ def main(argv=None):
         args.hotwords, args.hotword_weight = "", 0.0              # (no search: nothing to bias)
         args.ngram_lm, args.ngram_weight = "", 0.0                # (... and nothing to fuse an LM into)
     ctc_only = False
-    if args.decoder != "attention":                                    # (las.ctc_search is imported only when the flag is given)
+    if args.decoder != "attention" or args.rescore != "none":          # (las.ctc_search is imported only when one of the flags is given)
         from las import ctc_search
         ctc_only = ctc_search.check_args(args) and args.align_text is None
     if args.timestamps and not args.ctc:

@@ -718,6 +718,37 @@ int las_ctc_beam_search(const int* cand_tok, const float* cand_lp, const float* 
                         size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K10i two-pass decoding: the attention decoder's log-likelihood of given token strings from the teacher-forced Speller's
+ * logits, and the re-ranking of a first pass' N-best list with it.
+ *
+ * las_rescore_score: logits fp32, element (r, t, v) at logits[r*sb + t*st + v] (strides in elements, last axis contiguous, as
+ *   las_ce_loss: the Speller's time-major [U, R, V] buffer is sb = V, st = R*V; a batch-major [R, U, V] one is sb = U*V, st = V).  No
+ *   alignment beyond the floats' own is asked of the row bases.  y int32 [R, ldy] (ldy >= U), len int32 [R] clamped to [0, U].  For t < len[r]:
+ *     term(r, t) = z[y] - lse,  lse = m + logf(s),  m = the row maximum,  s = sum_v expf(z[v] - m), all fp32;
+ *     m = -inf (no class has mass): term = -inf, never NaN;  y outside [0, V): term = -inf, and nothing is read for it.
+ *   Order of s (part of the contract; tests/rescore_ref.py's float32 mode repeats it): 256 lanes, lane i adds classes i, i + 256, ... in
+ *   ascending order from 0.f, one rounding per add; inside each 64-lane wave a xor butterfly (distances 32, 16, 8, 4, 2, 1); the four
+ *   wave sums added in order from 0.f (las_ctc_frame_topk's order).  Every load is one dword per lane: the order, and with it every bit
+ *   of the result, does not depend on where the logits lie.
+ *   att fp64 [R] = the sum of the row's fp32 terms in step order from 0.0; 0 for len = 0; -inf if a term is.
+ *   step_lp fp32 [R, ldy] or NULL: receives the terms; entries at t >= len[r] are not written.  With step_lp = NULL the terms pass
+ *   through ws, las_rescore_workspace_bytes(R, U) bytes (with step_lp, ws may be NULL).
+ *   One workgroup per (row, step), then one wave per row: two launches on `stream`, no synchronisation.
+ * las_rescore_rank: n utterances of K <= 64 slots, nhyp int32 [n] clamped to [0, K]; first fp32 [n, K] the first pass' scores, att fp64
+ *   [n, K]; w inside [0, 1].  For k < nhyp[u]:
+ *     total[u, k] = (float)((1 - w) * att + w * (double)first), every operation rounded on its own;
+ *     order[u, 0 : nhyp[u]] = the slots by descending total; equal totals: the lower slot (the first pass' rank) first; NaN totals
+ *     last, in slot order.  Slots k >= nhyp[u] are neither read nor written.  One launch.
+ * Null pointers, R, U, V, n < 1, V > 2^30, R*U > 2^31 - 1, ldy < U, a negative stride, K outside [1, 64], w outside [0, 1] or NaN, a missing or
+ * short workspace: < 0 with a las_last_error text before anything is launched.  No atomics: two runs give the same bits.
+ */
+size_t las_rescore_workspace_bytes(int R, int U);
+int las_rescore_score(const float* logits, long long sb, long long st, const int* y, int ldy, const int* len, int R, int U, int V,
+                      double* att, float* step_lp, void* ws, size_t ws_bytes, void* stream);
+int las_rescore_rank(const float* first, const double* att, const int* nhyp, int n, int K, double w, float* total, int* order,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K10d CTC Viterbi (forced) alignment of a token sequence to the encoder frames: token and word times.  The max-plus form
  * of las_ctc_loss's extended-label recursion (states 0 .. 2L: blank, label 0, blank, ..., label L-1, blank) with a back-trace.
  *   lp           las_ctc_log_softmax's output, fp32 [n, Vc, Tp] class-major, blank = class Vc - 1
