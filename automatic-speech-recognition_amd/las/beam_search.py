@@ -440,6 +440,17 @@ class BeamSearch(object):
             token_lists = [list(r[-1].token_ids[1:]) if r else [] for r in results]
         return self.align(k.encs, k.enc_lens, token_lists, h_one=k.h_one, ctc_lp=k.ctc_lp)
 
+    def keyword_search(self, encs, enc_lens, keywords, h_one=None, ctc_lp=None, threshold_per_token=-1.0, max_hits=4, series=False):
+        """Keyword search on the CTC head (las.kws.keyword_search): every phrase of `keywords` (a las.kws.KeywordList) in
+        every utterance -> a KeywordResult.  encs / enc_lens / h_one: _run_encoders'; as in align(), the head runs here whether or not
+        ctc_decode_weight is set, unless the caller hands in the `ctc_lp` a search already computed."""
+        from las.kws import keyword_search
+        self.need_ctc_head("BeamSearch.keyword_search")
+        with torch.no_grad():
+            if ctc_lp is None:
+                ctc_lp = self._ctc_log_probs(encs, h_one)
+            return keyword_search(ctc_lp, [int(x) for x in enc_lens], keywords, threshold_per_token, max_hits=max_hits, series=series)
+
     def ctc_decode_batch(self, sess, xs_list):
         """`--decoder ctc`: the transcripts of a batch from the CTC head alone -- encoders, head product, greedy collapse
         (beam_size 1) or CTC prefix beam search with the n-gram of set_ngram (las.ctc_search) -- as decode_batch's result lists.  No

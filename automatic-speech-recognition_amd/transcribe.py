@@ -11,6 +11,7 @@
     python transcribe.py --nbest 5 --confidence True --mbr True a.wav ...      (N-best consensus: alternatives, confidences, MBR choice)
     python transcribe.py --ctc True --decoder ctc --beam_size 16 a.wav ...     (the CTC head alone: prefix beam search, greedy with --beam_size 1)
     python transcribe.py --noise_file cafe.wav --snr_db 10 --rir_file room.wav a.wav ...   (the files as they would sound in that condition)
+    python transcribe.py --ctc True --keywords names.txt a.wav ...     (keyword search: where the CTC head hears a listed phrase, no search)
 
 With --timestamps the best hypothesis is aligned to the encoder frames by the CTC head (las.align, csrc/ctc_align.hip: a Viterbi pass
 over the head's log-probabilities) and every line is {"text", "score", "words": [{"word", "start", "end"}]}: times in seconds, None when
@@ -36,6 +37,13 @@ With --noise_file and / or --rir_file (las.augment, csrc/wave_aug.hip) every rec
 with the noise at --snr_db on the device, between the resampler and the front end: a model's robustness checked without writing audio
 files.  The noise starts at its first sample and wraps around; both files are resampled to --sample_rate.  Without the two flags
 las.augment is not imported and the output is what it was.
+
+With --keywords FILE (las.kws, csrc/kws.hip; the phrase-file format of --hotwords) the search is skipped, as with --align_text: the
+listener, the head, and one las_kws_search per batch.  Every file's line is {"hits": [{"keyword", "start", "end", "score",
+"confidence"}]}, sorted by start, then by the phrase's place in the list: score = the log-likelihood ratio of the phrase's best path
+against the head's frame-wise best path over the same frames (<= 0), confidence = exp(score / tokens of the phrase).  A hit needs
+score >= --keyword_threshold x tokens (default -1.0 nat per token, not measured on a trained model); --keyword_max_hits (1 to 8) hits
+are kept per file and phrase.  It cannot be combined with --align_text, --segment, --timestamps, --nbest, --confidence or --mbr.
 
 The files are read with preprocess.read_audio (.flac needs `soundfile`), `--decode_batch` of them at a time go through the device front
 end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip; a file at another rate than --sample_rate is resampled
@@ -124,8 +132,33 @@ def main(argv=None):
     parser.add_argument("--timestamps", type=str2bool, default=False, help="One JSON object per line with word times (needs --ctc True).")
     parser.add_argument("--align_text", type=str, default=None, metavar="FILE",
                         help="Forced alignment: one transcript per audio file, in order; skips the search, implies --timestamps True.")
+    parser.add_argument("--keywords", type=str, default=None, metavar="FILE",
+                        help="Keyword search: one phrase per line ('#' comments); skips the search and prints, per audio file, one JSON "
+                             "object with the places the CTC head hears a phrase (needs --ctc True).")
+    parser.add_argument("--keyword_threshold", type=float, default=-1.0,
+                        help="A hit needs a score of at least this many nats per token of its phrase (the score is the phrase's "
+                             "log-likelihood ratio against the head's frame-wise best path: <= 0).  The default of -1.0 is a guess: "
+                             "nobody has measured it on a trained model.")
+    parser.add_argument("--keyword_max_hits", type=int, default=4, help="Hits kept per file and phrase, the strongest (1 to 8).")
     VAD.add_flags(parser, str2bool)
     args = parser.parse_args(argv)
+    if args.keywords is not None:
+        if not args.ctc:
+            raise ValueError("--keywords needs the CTC head: decode with --ctc True (a model trained with --ctc)")
+        for flag, on, why in (("--align_text", args.align_text is not None, "aligns a given transcript"),
+                              ("--segment", args.segment, "cuts the recordings first; searching the segments is not built"),
+                              ("--timestamps", args.timestamps, "times the search's hypothesis"),
+                              ("--nbest", args.nbest, "reads the search's N-best list"),
+                              ("--confidence", args.confidence, "reads the search's N-best list"),
+                              ("--mbr", args.mbr, "reads the search's N-best list")):
+            if on:
+                raise ValueError("--keywords skips the search and prints keyword hits only, %s %s: use one of them" % (flag, why))
+        if not 1 <= args.keyword_max_hits <= 8:
+            raise ValueError("--keyword_max_hits must be in [1, 8] (got %d)" % args.keyword_max_hits)
+        if np.isnan(args.keyword_threshold):
+            raise ValueError("--keyword_threshold is not a number")
+        args.hotwords, args.hotword_weight = "", 0.0              # (no search: nothing to bias)
+        args.ngram_lm, args.ngram_weight = "", 0.0                # (... and nothing to fuse an LM into)
     if args.segment and args.align_text is not None:
         raise ValueError("--segment cuts the recordings, --align_text aligns one transcript per whole file: use one of them")
     if args.align_text is not None:
@@ -149,6 +182,10 @@ def main(argv=None):
     tokenizer = CharEncoder() if args.unit.lower() == "char" else SubwordEncoder(args.subword_dir)
     args.vocab_size = tokenizer.get_vocab_size()
     id_to_token, token_to_id = tokenizer.id_to_token, tokenizer.token_to_id
+    keywords = None
+    if args.keywords is not None:                                      # (las.kws is imported only when the flag is given)
+        from las import kws as KW
+        keywords = KW.KeywordList.from_file(args.keywords, tokenizer, args.vocab_size)
     layers.set_cell(args.cell)
     layers.set_precision(args.dtype)
     torch.cuda.set_device(0)
@@ -172,6 +209,8 @@ def main(argv=None):
             restore_lm(lm, result['best_model'])
     if args.timestamps:
         bs.need_ctc_head("--timestamps")                              # (a checkpoint without the head: refused before any audio is read)
+    if keywords is not None:
+        bs.need_ctc_head("--keywords")
     ann = None
     if consensus:                                                      # (las.nbest is imported only when one of its flags is given)
         from las import nbest as NB
@@ -243,6 +282,17 @@ def main(argv=None):
     if args.segment:
         return transcribe_segmented(args, bs, extract, VAD.VoiceActivity(args, device=dev), load, count, nb, id_to_token, frame_s, ann,
                                     search)
+    if keywords is not None:
+        # keyword search: the listener and the head, no search; one JSON object per file
+        for make in batches():
+            with torch.no_grad():
+                encs, enc_lens, _, h_one, ctc_lp = bs._run_encoders(None, make())
+            found = bs.keyword_search(encs, enc_lens, keywords, h_one=h_one, ctc_lp=ctc_lp, threshold_per_token=args.keyword_threshold,
+                                      max_hits=args.keyword_max_hits)
+            for hits in found.hits:
+                print(json.dumps({"hits": KW.timed_hits(hits, keywords, frame_s, durations.popleft())}))
+        sys.stdout.flush()
+        return
     if texts is not None:
         # forced alignment: the listener and the head, no search
         done = 0

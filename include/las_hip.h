@@ -772,6 +772,49 @@ int las_ctc_align(const float* lp, int Vc, int Tp, const int* enc_len, int n, co
                   int* first, int* last, int* frame_state, double* score, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K10j keyword search (spoken-term detection) on the CTC head: where in a recording is a listed phrase said, and how sure
+ * is the model?  It asks the posteriors, not a 1-best.  Plain arguments, no struct (as las_ctc_align).
+ *   lp           las_ctc_log_softmax's output, fp32 [n, Vc, Tp] class-major, blank = class Vc - 1; finite values
+ *   enc_len [n]  frames of utterance u, clamped to [1, Tp] (as las_ctc_align)
+ *   y, y_len     P phrases shared by all utterances: the labels of phrase p are y[p, 0 : y_len[p]] (int32, pitch ldy >= U), L = y_len[p]
+ *                in [1, min(U, 32)], labels in [0, Vc - 2]
+ *   thr [P]      fp32, one threshold per phrase
+ * The score (part of the contract).  m[u, t] = max_c lp[u, c, t] (fp32: exact in any order); e(c, t) = (double)lp[u, c, t] -
+ * (double)m[u, t] <= 0, exactly 0.0 where c is the frame's arg-max.  A path's score is its log-likelihood ratio against the frame-wise
+ * best path over the same window: <= 0, and exactly 0.0 when the phrase IS the greedy path there.  States s = 0 .. 2L - 2: even s = 2j
+ * is label j, odd s the blank between labels j and j + 1; no leading or trailing blank (the window starts on the first label and ends
+ * on the last), S = 2L - 1 <= 63.  Every state carries a pair (best, start).  In front of t = 0 every state is (-inf, -1).  For
+ * t < T_u the candidates are taken in this order, a later one replacing an earlier one only if it is STRICTLY greater:
+ *   1. stay (best(t-1, s), start(t-1, s));   2. s - 1, for s >= 1;   3. s - 2, for even s >= 2 whose label differs from the label
+ *   before it;   4. the fresh start (0.0, t), for s = 0 only;
+ * then best(t, s) = chosen + e(label_s, t) and the start is carried (at t = 0 only state 0 is alive, from the fresh start (0.0, 0)).
+ * One fp64 subtraction and one fp64 addition per state and frame, in frame order, no products: a float64 restatement that does the same
+ * gives the same bits (tests/kws_ref.py), and so do two runs (no atomics).  The tie rule gives a phrase that is the greedy path over
+ * frames [a, b] start = a: staying in a 0-scoring first label beats a fresh start on the tie.
+ *   end_score fp64 [n, P, Tp], end_start int32 [n, P, Tp], or both NULL: best(t, 2L - 2) and its start; -inf / -1 for t >= T_u.
+ * Hits, from the end series while it is produced.  Frame t is a candidate (sc, st, t) when sc = end_score[t] > -inf and sc >=
+ * (double)thr[p].  One open hit is kept at a time.  A candidate overlaps it when st <= open.end: it then replaces the open hit if sc >=
+ * open.score (the later end on a tie: a hit ends on the last frame of its last label's run) and is dropped otherwise.  A candidate that
+ * does not overlap (or finds no open hit) closes the open hit and opens a new one; at t = T_u the open hit is closed.  Closed hits go into
+ * a kept list of capacity H in [1, 8], in time order; when it is full, the closing hit replaces the weakest kept hit (the smallest score,
+ * the earliest among equals) only if it scores strictly greater -- the survivors are shifted and the new hit is appended -- and is
+ * dropped otherwise.
+ *   hit_start, hit_end int32 [n, P, H], hit_score fp64 [n, P, H]: the kept hits; entries at or beyond `kept` are not written
+ *   count int32 [n, P, 2] = (kept, total closed)
+ *   best_score fp64 [n, P], best_span int32 [n, P, 2]: independently of thr, the maximum of the end series with its (start, end); on
+ *   equal values the later end; -inf, -1, -1 when no end state is ever reached (L + repeats > T_u)
+ * A phrase that cannot be searched -- y_len[p] outside [1, min(U, 32)] or a label outside [0, Vc - 2] -- gets count = (0, 0), best =
+ * -inf / -1 / -1 and a -inf / -1 series in every utterance; the other phrases are unaffected and the call returns 0.
+ * Refused on the host with a las_last_error text before anything is launched: U > 32, Tp > 2048, H outside [1, 8], n > 65535, P > 65535,
+ * exactly one of end_score / end_start NULL, ws_bytes < las_kws_workspace_bytes(n, Tp) (the frame maxima).  Two launches on `stream`
+ * (frame maxima; one wavefront per utterance and phrase), no synchronisation.
+ */
+size_t las_kws_workspace_bytes(int n, int Tp);
+int las_kws_search(const float* lp, int Vc, int Tp, const int* enc_len, int n, const int* y, int ldy, const int* y_len, const float* thr,
+                   int P, int U, int H, int* hit_start, int* hit_end, double* hit_score, int* count, double* best_score, int* best_span,
+                   double* end_score, int* end_start, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K10g  consensus over the N-best list a search ends with: minimum-Bayes-risk choice and token confidences from the
  * unit-cost Levenshtein distances and alignments among the hypotheses of an utterance.  Plain arguments, no struct (as las_ctc_align).
  * A batch is n utterances with K hypothesis slots of at most U tokens:
