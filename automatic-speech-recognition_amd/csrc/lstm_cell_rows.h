@@ -1,6 +1,5 @@
 // lstm_cell_rows.h -- the device body of las_lstm_cell_rows (one LSTM cell step for a block of 32 rows x 16 units), shared by the kernels of
-// loss_opt.hip (the cell alone, two cells as one grid) and speller.hip (round 5: the LM's first layer as extra workgroups of the beam
-// search's attention-row launch).  reference lang/char_rnn_model.py:57-66 (BasicLSTMCell gate math), las/beam_search.py:109-116.
+// loss_opt.hip (the cell alone, two cells as one grid).  reference lang/char_rnn_model.py:57-66 (BasicLSTMCell gate math), las/beam_search.py:109-116.
 #pragma once
 #include "las_common.h"
 #include <type_traits>

@@ -13,7 +13,6 @@
 // the gate backward of step t) + one las_gemm (dG.W^T) per step; every weight gradient is a single
 // tall contraction after the loop (split-K, deterministic).  No atomics anywhere.
 #include "las_common.h"
-#include "lstm_cell_rows.h"
 #include <type_traits>
 #include <math.h>
 
@@ -1459,27 +1458,6 @@ __global__ __launch_bounds__(RNT) void dec_beam_rows4_kernel(DecDev a) {
         }
     }
     STAMPB(8);
-}
-
-// Round 5, beam search (las/beam_search.py:94-158 is ONE loop): the attention rows of a search step and ANOTHER cell step that depends on
-// the step's tokens only -- the LM's first layer (las/beam_search.py:109-116) -- as one grid.  The first `nlm` workgroups run the LM cell
-// (32 rows x 16 units each, 512 of the 1024 threads; the others leave at once), the rest one attention row each.  The LM's second layer
-// then rides with the Speller's cell (las_speller_fwd_args.companion): a search step is three dependent launches instead of five.
-constexpr int PF_LM_LDS = 32 * LC_LD * 2 + 2 * 4 * 64 * 4 * 4;      // the cell workgroups' row tile + gate exchange
-template <int CELL, int NE>
-__global__ __launch_bounds__(RNT) void dec_step_fwd_pf_lm_kernel(DecDev a, int t, LstmCellLaunch lm, int nlm) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    if ((int)blockIdx.x < nlm) {
-        if (threadIdx.x >= 512) return;
-        const int nu = lm.H >> 4;
-        float (&gates)[2][4][64][4] = *reinterpret_cast<float (*)[2][4][64][4]>(sm + 32 * LC_LD / 2);
-        lstm_cell_rows_body<false, false, false>(lm, reinterpret_cast<unsigned short*>(sm), gates, (int)blockIdx.x % nu, ((int)blockIdx.x / nu) * 32);
-        return;
-    }
-    float ccar = 0.f;
-    const int b = xcd_local_row((int)blockIdx.x - nlm, nlm, a.row_group, a.B);
-    if (b < 0) return;
-    pf_fwd_row<CELL, NE, false>(a, t, b, threadIdx.x, sm, ccar, false);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3266,16 +3244,7 @@ static int speller_fwd_impl(const las_speller_fwd_args* f, DecDev d, hipStream_t
             const size_t lds_bf = p.lds_bf;
             switch (pf && t == U ? LAS_SPELLER_RAN_BF_ROWS : p.family) {
             case LAS_SPELLER_RAN_PF_ROWS:
-                if (t == 0 && f->companion_rows && (d.flags & LAS_SPELLER_NO_LOGITS)) {
-                    // beam-search step: the LM's first layer as extra workgroups of the attention-row launch
-                    const LstmCellLaunch& lm = *f->companion_rows;
-                    if (int rc = las_lstm_cell_check(lm)) return rc;
-                    LAS_ARG(!lm.fast && !lm.x_bf16, "las_speller_fwd: companion_rows must be an exact (fast = 0) cell with fp32 rows");
-                    const int nlm = (lm.H / 16) * cdiv(lm.M, 32);
-                    const size_t ldsc = lds_bf > (size_t)PF_LM_LDS ? lds_bf : (size_t)PF_LM_LDS;
-                    GEMM_OK(with_ne(d.Tp, [&](auto ne) { hipLaunchKernelGGL((dec_step_fwd_pf_lm_kernel<CELL, decltype(ne)::value>),
-                                                                   dim3(nlm + xcd_local_grid(B, d.row_group)), dim3(RNT), ldsc, st, d, t, lm, nlm); return 0; }));
-                } else if (t == 0 && U == 1 && f->keep_state0 && (d.flags & LAS_SPELLER_ROWS_SHARE4) && (d.flags & LAS_SPELLER_NO_LOGITS)) {
+                if (t == 0 && U == 1 && f->keep_state0 && (d.flags & LAS_SPELLER_ROWS_SHARE4) && (d.flags & LAS_SPELLER_NO_LOGITS)) {
                     // beam-search step over many rows: four hypotheses of an utterance per workgroup, shared operands read once
                     LAS_ARG((B % BR4) == 0 && d.tok_in, "speller: LAS_SPELLER_ROWS_SHARE4 needs a row count that is a multiple of 4");
                     GEMM_OK(with_ne(d.Tp, [&](auto ne) { LAS_LDS_LAUNCH((dec_beam_rows4_kernel<decltype(ne)::value>),

@@ -13,13 +13,14 @@ last step.
 Scores are RAW logits summed in float32 and ranked by sum/len, as the reference does."""
 import collections.abc
 import ctypes
-
 import os
+import time
 
 import numpy as np
 import torch
 
 from las import _hip
+from las import beam_step as S
 from las import layers as L
 
 NORM = True
@@ -89,6 +90,11 @@ class AlignInputs(object):
         self.encs, self.enc_lens, self.h_one, self.ctc_lp = encs, enc_lens, h_one, ctc_lp
 
 
+# what _run_encoders makes of a batch: encs [per utterance: [1, T'_u, Hd] views], enc_lens, dec_steps, h_one (the encoder output of all
+# utterances when they form one group, else None), ctc_lp (class-major CTC log-probabilities [n, V + 1, max T'_u], or None)
+EncodedBatch = collections.namedtuple("EncodedBatch", "encs enc_lens dec_steps h_one ctc_lp")
+
+
 class _Results(list):
     """decode_batch's result list; `align_inputs` is the batch's AlignInputs when BeamSearch.retain_align was set, else None"""
     align_inputs = None
@@ -137,12 +143,6 @@ class BeamSearch(object):
         self._head_absent = None            # restore_las: (checkpoint path, the CTC head's variables it lacks)
         self.use_graph = os.environ.get("LAS_NO_DECODE_GRAPH") != "1"     # decode_batch replays one captured step
         self.fuse_projection = os.environ.get("LAS_NO_DECODE_FUSED_PROJ") != "1"   # decode_batch: cell in one launch, projection inside the beam kernel
-        # decode_batch (round 5): rows + LM 1 | Speller cell + LM 2 | pruning + gather -- three dependent launches instead of five.  OFF by
-        # default: measured in the replayed graph (profiles/r5_decode_three_launches.txt) the three launches take 73-80 us of kernel time per
-        # step against 59 us for the five (14.3 + 12.7 + 11.2 + 15.9 + 4.8): every kernel of the step fills the machine by itself (256 rows = 256
-        # workgroups of 16 waves), so rows + LM 1 run one after the other inside their launch (22-26 us), and 16 pruning workgroups gather
-        # 207 KB each more slowly (30-34 us) than 256 x ntens gather workgroups do (4.8 us); dependent launches cost ~0 us in a replayed graph
-        self.three_launches = os.environ.get("LAS_DECODE_3_LAUNCHES") == "1"
         # decode_batch (round 5): the attention rows of FOUR hypotheses of an utterance in one workgroup (LAS_SPELLER_ROWS_SHARE4: Ws, keys and
         # encoder rows read once for the four) from this many hypothesis rows on (0 = never); bit-identical to one row per workgroup
         self.share_rows_from = int(os.environ.get("LAS_DECODE_SHARE_ROWS_FROM", "512"))
@@ -189,15 +189,6 @@ class BeamSearch(object):
             h, _, enc_len = self.listener(a, np.asarray(audiolen), encoder=self.args.enc_type.lower(), is_training=False)
         return h, enc_len
 
-    def _get_dec_init(self, sess):
-        return self.speller.zero_state(1, self._las._device())
-
-    def _get_decode(self, sess, enc_out, enc_len, prev_token_id, prev_align, dec_states, keys=None):
-        """One step for N hypotheses.  enc_out/keys are already tiled to N rows on device."""
-        with torch.no_grad():
-            return self.speller.decode(enc_out, enc_len, dec_states, None, prev_align, False, keys=keys,
-                                       token_ids=torch.as_tensor(prev_token_id, dtype=torch.int32))
-
     # -- the search ----------------------------------------------------------------------------------------
     def decode(self, sess, xs):
         """xs = (audio [1,T,feat_dim,3], audiolen [1]) -> list of BeamState, ascending (best last),
@@ -232,18 +223,17 @@ class BeamSearch(object):
             ev = torch.cuda.Event()
             ev.record(es)
             seen = set()
-            for h in pre[0]:                 # allocated on `es`, read by the search on `main`
+            for h in pre.encs:               # allocated on `es`, read by the search on `main`
                 if h.untyped_storage().data_ptr() not in seen:
                     seen.add(h.untyped_storage().data_ptr())
                     h.record_stream(main)
-            if pre[4] is not None:           # (the CTC log-probabilities, likewise)
-                pre[4].record_stream(main)
+            if pre.ctc_lp is not None:       # (the CTC log-probabilities, likewise)
+                pre.ctc_lp.record_stream(main)
             return xs_list, pre, ev
 
         it = iter(batches)
         first = next(it, None)
         cur = launch(first) if first is not None else None
-        pending = None                       # the previous batch's back-tracking / read-back / host objects, not yet run
         try:
             yield from self._decode_batches_loop(sess, it, cur, launch, main, sync_every)
         finally:
@@ -277,8 +267,8 @@ class BeamSearch(object):
 
     def _run_encoders(self, sess, xs_list):
         """The encoders of a batch of utterances on the CURRENT stream, without waiting for the device (the encoded lengths are host
-        values): -> (encs [per utterance: [1, T'_u, Hd] views], enc_lens, dec_steps, h_one, ctc_lp).  ctc_lp: the CTC head's class-major
-        log-probabilities [n, V + 1, max T'_u] when ctc_decode_weight > 0, else None.  decode_batch's first phase; decode_batches runs it
+        values): -> EncodedBatch (encs, enc_lens, dec_steps, h_one, ctc_lp).  ctc_lp: the CTC head's class-major log-probabilities when
+        ctc_decode_weight > 0, else None.  decode_batch's first phase; decode_batches runs it
         for the NEXT batch on a second stream under the search of the current one.
         An utterance's audio is a host array or a device tensor (FeatureExtractor's cube rows); device tensors are stacked and padded
         on the device, with the values the host path would upload."""
@@ -380,7 +370,18 @@ class BeamSearch(object):
             for us in glist[1:]:
                 encode_group(us)
         ctc_lp = self._ctc_log_probs(encs, h_one) if self.ctc_weight > 0 else None
-        return encs, enc_lens, dec_steps, h_one, ctc_lp
+        return EncodedBatch(encs, enc_lens, dec_steps, h_one, ctc_lp)
+
+    def _stack_encs(self, encs, h_one):
+        """the encoder outputs of a batch as ONE block [n, max T'_u, Hd], zero behind an utterance's last frame (h_one when the utterances
+        form one encoder group: equal lengths, nothing to pad)"""
+        n = len(encs)
+        if h_one is not None and h_one.shape[0] == n:
+            return h_one.contiguous()
+        enc = torch.zeros(n, max(h.shape[1] for h in encs), encs[0].shape[2], device=self._las._device())
+        for u, h in enumerate(encs):
+            enc[u, :h.shape[1]] = h[0]
+        return enc
 
     def _ctc_log_probs(self, encs, h_one):
         """The CTC head over the encoder frames of a batch (las/las.py:75-77, the product of _CTCHead.forward through las_gemm), then
@@ -392,15 +393,8 @@ class BeamSearch(object):
         dev = self._las._device()
         P = self.speller._params(head=True)
         Wc, bc = P["Wc"].detach(), P["bc"].detach()
-        n = len(encs)
-        Tps = [h.shape[1] for h in encs]
-        Tp, Hd, Vc = max(Tps), encs[0].shape[2], Wc.shape[1]
-        if h_one is not None and h_one.shape[0] == n:
-            enc = h_one.contiguous()
-        else:
-            enc = torch.zeros(n, Tp, Hd, device=dev)
-            for u, h in enumerate(encs):
-                enc[u, :Tps[u]] = h[0]
+        enc = self._stack_encs(encs, h_one)
+        (n, Tp, Hd), Vc = enc.shape, Wc.shape[1]
         z = torch.empty(n, Tp, Vc, device=dev)
         _hip.gemm(L._prec(), enc, Wc, z, False, False, n * Tp, Vc, Hd, Hd, Vc, Vc, bias=bc)
         return z
@@ -476,332 +470,89 @@ class BeamSearch(object):
         Every utterance is ENCODED on its own, at its own length (the reference's encoder has no sequence mask, so its
         output depends on the padded length -- SURVEY fact 4 -- and decode.py feeds unpadded utterances); the search then
         runs all utterances x beam hypotheses as ONE batch of rows per step: fused Speller step (las_speller_fwd, U = 1)
-        [+ LM step + shallow fusion] + las_beam_loop_step (pruning, EOS retirement, termination, state gather -- all on
-        the device).  The host replays the launches without waiting and reads the back-pointer records once at the end
-        (plus one `done` poll every `sync_every` steps to stop early)."""
-        import ctypes
-        from las.las import _alloc_bufs, _fill_fwd_args
-        a = self.args
-        dev = self._las._device()
-        n, beam, V_, A, NL, D = len(xs_list), self.beam_size, a.vocab_size, a.attention_size, a.num_dec_layers, a.dec_units
-        sp = self.speller
-        lstm = sp.cell == "lstm"
-        prec = L._prec()
-        P = sp._params()
-        # ---- encoders (one per utterance) and the hoisted key projection
-        import time
-        tm = {}
+        [+ LM step + shallow fusion] [+ n-gram, CTC prefix, hotword scores] + las_beam_loop_step (pruning, EOS retirement, termination,
+        state gather -- all on the device; the parts of a step: las/beam_step.py).  The host replays the launches without waiting and
+        reads the back-pointer records once at the end (plus one `done` poll every `sync_every` steps to stop early)."""
+        a, dev, prec, tm = self.args, self._las._device(), L._prec(), {}
         def mark(name):                                  # wall-clock marks (with a device sync) only when asked for
             if self.measure:
                 torch.cuda.synchronize(dev)
                 tm[name] = time.perf_counter()
         mark("start")
+        # ---- encoders (one per utterance) and the hoisted key projection
         if _pre is None:
             _pre = self._run_encoders(sess, xs_list)
         encs, enc_lens, dec_steps, h_one, ctc_lp = _pre
         kept = AlignInputs(encs, enc_lens, h_one, ctc_lp) if self.retain_align else None
-        lam = self.ctc_weight
         Tps = [h.shape[1] for h in encs]
-        Tp, Hd = max(Tps), encs[0].shape[2]
-        N = n * beam
-        # Round 6: ONE operand block per utterance, resident for the whole search (frames past T'_u are masked).  The reference feeds
-        # np.tile(h) -- a copy of the encoder output per hypothesis (las/beam_search.py:216) -- and so did rounds 1-5: 16 copies of every
-        # utterance's keys and encoder rows, each read through its own addresses at every step (54 MB per step at 256 rows, r5_decode_pmc.json).
-        # The search step's row kernels now take the utterance's block (LAS_SPELLER_SHARED_OPERANDS); the tiled copies are only made for
-        # the long form of the step (kernel families that index per row).
-        Wh = P["Wh"].detach()
+        n, Tp, Hd, A = len(xs_list), max(Tps), encs[0].shape[2], a.attention_size
+        Wh = self.speller._params()["Wh"].detach()
+        enc_u = self._stack_encs(encs, h_one)
         if h_one is not None and h_one.shape[0] == n:
-            # every utterance in ONE encoder group (equal lengths): the hoisted key projection as one product
-            enc_u = h_one.contiguous()
-            keys_u = torch.empty(n, Tp, A, device=dev)
+            keys_u = torch.empty(n, Tp, A, device=dev)                 # every utterance in ONE encoder group: the projection as one product
             _hip.gemm(prec, enc_u, Wh, keys_u, False, False, n * Tp, A, Hd, Hd, A, A)
         else:
-            enc_u = torch.zeros(n, Tp, Hd, device=dev)
             keys_u = torch.zeros(n, Tp, A, device=dev)
             for u, h in enumerate(encs):
                 k = torch.empty(1, Tps[u], A, device=dev)
                 _hip.gemm(prec, h.contiguous(), Wh, k, False, False, Tps[u], A, Hd, Hd, A, A)
-                enc_u[u, :Tps[u]] = h[0]
                 keys_u[u, :Tps[u]] = k[0]
-        tiled_ops = []
-
-        def tiled():
-            """the per-row copies [N, Tp, .] (made once, on demand)"""
-            if not tiled_ops:
-                enc_t = torch.empty(N, Tp, Hd, device=dev)
-                keys_t = torch.empty(N, Tp, A, device=dev)
-                enc_t.view(n, beam, Tp, Hd).copy_(enc_u.unsqueeze(1).expand(n, beam, Tp, Hd))
-                keys_t.view(n, beam, Tp, A).copy_(keys_u.unsqueeze(1).expand(n, beam, Tp, A))
-                tiled_ops.extend([enc_t, keys_t])
-            return tiled_ops
-        enc_len_i32 = torch.tensor(np.repeat(np.asarray(enc_lens, np.float64), beam)).to(torch.int32).to(dev)
-        Umax = max(max(dec_steps), 1)
-        # ---- device-resident loop state
-        i32 = dict(dtype=torch.int32, device=dev)
-        selcap = 3 * beam
-        score = torch.zeros(n, beam, device=dev)
-        length = torch.zeros(n, beam, **i32)
-        nlive = torch.full((n,), beam, **i32)
-        nsel = torch.zeros(n, **i32)
-        done = torch.zeros(n, **i32)
-        dstep = torch.tensor(dec_steps, **i32)
-        step = torch.zeros(2, **i32)                       # [0] the device step counter, [1] arrival counter of the folded gather (fold_gather)
-        hist_parent = torch.zeros(Umax, n, beam, **i32)
-        hist_token = torch.zeros(Umax, n, beam, **i32)
-        hist_slot = torch.zeros(Umax, n, beam, **i32)
-        hist_score = torch.zeros(Umax, n, beam, device=dev)
-        hist_n = torch.zeros(Umax, n, **i32)
-        sel_t = torch.zeros(n, selcap, **i32)
-        sel_j = torch.zeros(n, selcap, **i32)
-        src_row = torch.zeros(n, beam, **i32)
-        next_token = torch.full((N,), self.start_id, **i32)
-        alphas_hist = torch.zeros(Umax + 1, N, Tp, device=dev)      # [Umax] stays zero: item 0 of every hypothesis' att
-        align_prev = torch.zeros(N, Tp, device=dev)
-        # ---- the fused Speller step for all rows: slot 0 of hs / cs = state entering the step, slot 1 = state leaving it
-        dims = sp._dims(N, Tp, 1)
-        bufs = _alloc_bufs(dims, dev)
-        bufs["hs"].zero_()
-        if lstm:
-            bufs["cs"].zero_()
-        tokens_out = torch.zeros(1, N, **i32)
-        Pd = {k: (v.detach() if torch.is_tensor(v) else [t.detach() for t in v]) for k, v in P.items()}
-        fa = _hip.SpellerFwdArgs()
-        keep = _fill_fwd_args(fa, dims, Pd, enc_u, keys_u, enc_len_i32, next_token, tokens_out, bufs, True, 0, keep_state0=True,
-                              align0=align_prev)
-        lib = _hip.lib()
-        nbytes = lib.las_speller_workspace_bytes(N, Tp, Hd, A, D, NL, a.embedding_size, V_, 1, dims["cell"])
-        ws = _hip.workspace(dev, nbytes, "speller")
-        fa.ws, fa.ws_bytes = ws.data_ptr(), ws.numel()
-        logits = bufs["logits"][0]                                                      # [N, V]
-        # ---- state tensors that follow their hypotheses (gathered by las_beam_loop_step)
-        st_in, st_out = [], []
-        for l in range(NL):
-            st_in.append(bufs["hs"][l, 1]); st_out.append(bufs["hs"][l, 0])
-            if lstm:
-                st_in.append(bufs["cs"][l, 1]); st_out.append(bufs["cs"][l, 0])
-        k_align = len(st_in)
-        st_in.append(alphas_hist[0]); st_out.append(align_prev)
-        lm = self.lm if a.apply_lm else None
-        lm_w = np.float32(a.lm_weight) if lm is not None else None
-        lm_plan = lm.fusion_plan(lm_w) if lm is not None else None
-        lm_hb = None
-        if lm is not None:
-            Hl, NLl = lm.hidden_size, lm.num_layers
-            lm_c = [torch.zeros(N, Hl, device=dev) for _ in range(NLl)]
-            lm_h = [torch.zeros(N, Hl, device=dev) for _ in range(NLl)]
-            k_lm = len(st_in)
-            # bf16 copies of the LM's recurrent state (round 5): from 384 rows on the cells read them -- and the layer below's copy -- instead
-            # of converting the fp32 rows while staging them (half the bytes through a CU that is bound by its ingest); the copies follow
-            # their hypotheses through the gather as rows of H / 2 floats -- INSTEAD of the fp32 h rows, which nobody reads then (the
-            # projection takes the step's fresh h).  Bit-identical: the copy is the staging's own rounding.
-            if self.lm_state_copies and prec == _hip.PREC_BF16 and not self.three_launches and lm.twins_ok(lm_plan, N):
-                lm_hb = [torch.zeros(N, Hl, dtype=torch.bfloat16, device=dev) for _ in range(NLl)]
-                for l in range(NLl):
-                    st_in.append(lm_c[l]); st_out.append(lm_c[l])                  # inputs are re-pointed every step
-                k_tw = len(st_in)
-                for l in range(NLl):
-                    st_in.append(lm_hb[l].view(torch.float32)); st_out.append(lm_hb[l].view(torch.float32))
-            else:
-                for l in range(NLl):
-                    st_in += [lm_c[l], lm_h[l]]; st_out += [lm_c[l], lm_h[l]]
-        ba = _hip.BeamLoopArgs()
-        for name, t in (("logits", logits), ("score", score), ("length", length), ("nlive", nlive), ("nsel", nsel), ("done", done),
-                        ("dec_step", dstep), ("step", step), ("hist_parent", hist_parent), ("hist_token", hist_token),
-                        ("hist_slot", hist_slot), ("hist_score", hist_score), ("hist_n", hist_n), ("sel_t", sel_t), ("sel_j", sel_j),
-                        ("src_row", src_row), ("next_token", next_token)):
-            setattr(ba, name, t.data_ptr())
-        ba.nutt, ba.beam, ba.V, ba.Umax, ba.selcap, ba.topn = n, beam, V_, Umax, selcap, self.TOPN
-        if lam > 0:
-            # joint CTC-attention (DESIGN 7d): las_ctc_prefix_step advances every live row's CTC state (r^n, r^b, psi, last label) from
-            # its gathered parent `ctc_par` into `ctc_cur` and writes the joint scores of the row's candidates into `joint`, which the pruning
-            # ranks instead of the logits; `ctc_cur` follows its hypotheses through the gather like the recurrent state
-            assert ctc_lp is not None and ctc_lp.shape == (n, V_ + 1, Tp), "decode_batch: the encoder stage made no CTC log-probabilities"
-            ctc_w = 4 * ((2 * Tp + 2 + 3) // 4)
-            ctc_par = torch.zeros(N, ctc_w, device=dev)
-            ctc_cur = torch.zeros(N, ctc_w, device=dev)
-            joint = torch.zeros(N, V_, device=dev)
-            ctc_len = torch.tensor([int(x) for x in enc_lens], **i32)
-            st_in.append(ctc_cur); st_out.append(ctc_par)
-            ba.logits = joint.data_ptr()
+        # ---- the parts of a step
+        g = S.Geometry(dev, n, self.beam_size, n * self.beam_size, Tp, Hd, max(max(dec_steps), 1), a.vocab_size, A, a.num_dec_layers, a.dec_units,
+                       a.embedding_size, self.speller.cell == "lstm", prec)
+        loop, rows = S.LoopState(g, dec_steps, self.start_id, self.end_id, self.TOPN), S.StateRows()
+        lam = self.ctc_weight
         ctx = self.context if (self.context is not None and self.context.active) else None
-        if ctx is not None:
-            # contextual biasing (DESIGN 7j): las_bias_step advances every live row's trie node from its gathered parent `bias_par` into
-            # `bias_cur` and adds the candidates' gains to the scores the pruning ranks (the logits, or `joint`), in place; `bias_cur` follows
-            # its hypotheses through the gather.  Rows of 4 floats (the node is the first): a row of one float would take every state
-            # tensor of the gather off its 16-byte path
-            bias_w = 4
-            bias_tab = ctx.to(dev)
-            bias_par = torch.zeros(N, bias_w, device=dev)
-            bias_cur = torch.zeros(N, bias_w, device=dev)
-            bias_scores = joint if lam > 0 else logits
-            st_in.append(bias_cur); st_out.append(bias_par)
         ng = self.ngram if (self.ngram is not None and self.ngram_weight > 0) else None
-        if ng is not None:
-            # n-gram LM shallow fusion (DESIGN 7k): las_ngram_step advances every live row's trie node from its gathered parent `ng_par`
-            # into `ng_cur` and adds the candidates' weighted log-probabilities to the logits, in place, in front of the CTC bank cut and
-            # the hotword bonus; `ng_cur` follows its hypotheses through the gather (rows of 4 floats, as the hotword state)
-            ng_w = 4
-            ng_tab = ng.to(dev, self.ngram_weight)
-            ng_par = torch.zeros(N, ng_w, device=dev)
-            ng_cur = torch.zeros(N, ng_w, device=dev)
-            st_in.append(ng_cur); st_out.append(ng_par)
-        if len(st_in) > 16:
-            raise ValueError("decode_batch: %d state tensors follow the hypotheses (decoder and LM state, alignment, CTC, hotword and "
-                             "n-gram LM state); las_beam_loop_step gathers at most 16" % len(st_in))
-        ba.start_id, ba.end_id, ba.ntens = self.start_id, self.end_id, len(st_in)
-        for k, (ti, to) in enumerate(zip(st_in, st_out)):
-            ba.state_in[k], ba.state_out[k], ba.state_width[k] = ti.data_ptr(), to.data_ptr(), ti.shape[-1]
+        lm = S.LmFusion(self.lm, a.lm_weight, g, loop, self.lm_state_copies) if a.apply_lm else None
+        speller = S.SpellerStep(self, g, loop, rows, enc_u, keys_u, enc_lens, lm, ng, ctx, lam)
+        if lm is not None:
+            lm.attach(rows, speller)
+        scorers, ranked = S.make_scorers(g, loop, rows, speller.logits, self.end_id, ctc_lp, enc_lens, lam, ctx, ng, self.ngram_weight)
+        loop.ba.logits = ranked.data_ptr()
+        rows.write(loop.ba)
         mark("encoded")
-        # the step's alignments land in a fixed buffer and are filed under the DEVICE step counter, so that one step is the
-        # same sequence of launches with the same arguments every time: it is captured into a HIP graph after the first
-        # (eager) step and replayed -- the loop is bound by the host's launch rate otherwise (5-8 launches and their Python glue per step)
-        alphas_cur = torch.zeros(N, Tp, device=dev)
-        fa.alphas = alphas_cur.data_ptr()
-        # rows u beam .. (u + 1) beam - 1 are the hypotheses of utterance u (same enc / keys): the row launches keep them on one XCD
-        fa.row_group = beam if self.xcd_local_rows else 0
-        ba.state_in[k_align] = alphas_cur.data_ptr()
-        ba.file_in, ba.file_out, ba.file_width = alphas_cur.data_ptr(), alphas_hist.data_ptr(), Tp
-        held = []
+        # One step = Speller, LM, the active scorers, the pruning: five launches in the short form (rows | cell + LM 1 | LM 2 | pruning | gather).
+        # tried: three dependent launches -- LM 1 as extra workgroups of the row launch, LM 2 beside the Speller's cell, the gather inside the
+        # pruning launch.  result: 73-80 us of kernel time per replayed step against 59 us for the five (14.3 + 12.7 + 11.2 + 15.9 + 4.8):
+        # every kernel of the step fills the machine by itself (256 rows = 256 workgroups of 16 waves), so rows + LM 1 ran one after the other
+        # inside their launch (22-26 us), and dependent launches cost ~0 us in a replayed graph (profiles/r5_decode_three_launches.txt).
+        # tried: the LM's cells (they depend only on the tokens) as a parallel branch on a second stream beside the Speller step.
+        # result: 111 against 99.5 us per captured step -- the cross-queue joins cost more than the overlap gives.
+        parts = [speller] + ([lm] if lm is not None else []) + scorers + [loop]
+        one_step = lambda: [part.launch() for part in parts]
+        steps_run, graph_used = self._run_steps(one_step, loop, sync_every, _after_launch)
+        mark("searched")
+        if _defer and not self.measure:
+            # decode_batches: everything behind the search -- back-tracking, the alignment gather, the read-back, the host objects -- as a closure
+            # (it holds the loop state) that runs on a side stream behind THIS point of the launch stream: the caller launches the next batch's
+            # search first and calls it while the device is busy with that (the read-back waits for the side stream only).
+            ev = torch.cuda.Event()
+            ev.record()
+            if self._tail_stream is None:
+                self._tail_stream = torch.cuda.Stream()
 
-        mode = {"fused": False}
+            def finish():
+                self._tail_stream.wait_event(ev)
+                with torch.cuda.stream(self._tail_stream):
+                    return self._decode_tail(loop, Tps, mark, kept)
+            return finish
+        results = self._decode_tail(loop, Tps, mark, kept)
+        mark("done")
+        if tm:
+            live_steps, parts_us = self._time_parts(parts, loop)
+            ks = list(tm)
+            self.last_timing = {ks[i + 1]: round(tm[ks[i + 1]] - tm[ks[i]], 4) for i in range(len(ks) - 1)}
+            self.last_timing.update(steps=steps_run, live_steps=live_steps, rows=g.N, frames=Tp, graph=graph_used, short_form=bool(speller.fused), parts_us=parts_us)
+            if a.verbose > 0:
+                print("decode_batch timing (s):", self.last_timing)
+        return results
 
-        def speller_part():
-            rc = lib.las_speller_fwd(ctypes.byref(fa), _hip.stream())
-            if rc < 0 and mode["fused"] and not (fa.flags & _hip.SPELLER_REUSE_PREP):
-                # the library refuses the short form for this geometry (it needs its prefetching row kernels): the long form it is
-                mode["fused"] = False
-                mode.pop("three", None)
-                fa.flags &= ~(_hip.SPELLER_NO_LOGITS | _hip.SPELLER_ROWS_SHARE4 | _hip.SPELLER_SHARED_OPERANDS)
-                fa.enc, fa.keys = (t.data_ptr() for t in tiled())       # (the long form's kernel families index enc / keys per row)
-                fa.companion = None
-                fa.companion_rows = None
-                ba.proj_w = None
-                ba.fold_gather = 0
-                rc = lib.las_speller_fwd(ctypes.byref(fa), _hip.stream())
-            _hip.check(rc, "las_speller_fwd")
-            fa.flags |= _hip.SPELLER_REUSE_PREP      # enc / keys / weights are fixed for the search: their bf16 copies are made once
-
-        # ---- the short form of a step (speed mode, one LSTM layer): the Speller call stops after its cell (LAS_SPELLER_NO_LOGITS: attention
-        # rows + ONE cell launch) and the vocabulary projection -- the Speller's output layer and, concatenated along K, the LM's softmax
-        # layer scaled by lm_weight and shifted to its token columns -- happens inside las_beam_loop_step: 5 launches per step instead of 8
-        E_ = a.embedding_size
-        # (not with the CTC prefix scores, a hotword context or an n-gram LM: they are placed between the materialised logits and the pruning
-        #  launch)
-        fused_proj = (ng is None and ctx is None and lam == 0 and prec == _hip.PREC_BF16 and lstm and NL == 1 and self.fuse_projection and D % 32 == 0 and (E_ + Hd + D) % 32 == 0 and
-                      ((beam + 15) // 16) * ((V_ + 15) // 16) <= 8 and (lm is None or (lm.hidden_size % 32 == 0 and "packs" in lm_plan)))
-        proj_keep = None
-        mode["fused"] = fused_proj
-        shared = fused_proj and self.shared_operands and self.xcd_local_rows
-        if not shared:
-            fa.enc, fa.keys = (t.data_ptr() for t in tiled())          # np.tile(enc, beam) of the reference (las/beam_search.py:60-63), physically
-        if fused_proj:
-            Wcat, bcat = Pd["Wv"].contiguous(), Pd["bv"].clone()
-            if lm is not None:
-                Wl = torch.zeros(lm.hidden_size, V_, device=dev)
-                Wl[:, 2:2 + lm.vocab_size] = lm_plan["sw"]
-                bcat[2:2 + lm.vocab_size] += lm_plan["sb"]
-                Wcat = torch.cat([Wcat, Wl], 0)
-            Wcat = Wcat.contiguous()
-            proj_keep = (_hip.skinny_pack(Wcat, Wcat.shape[0], V_), bcat.contiguous())
-            fa.flags |= _hip.SPELLER_NO_LOGITS
-            if shared:
-                fa.flags |= _hip.SPELLER_SHARED_OPERANDS     # enc / keys: one block per utterance (fa.row_group = beam rows share it)
-            if self.share_rows_from and N >= self.share_rows_from and beam % 4 == 0 and a.mode == "add":
-                fa.flags |= _hip.SPELLER_ROWS_SHARE4         # rows 4g .. 4g+3 are hypotheses of ONE utterance: same enc / keys / length
-            ba.proj_w, ba.proj_b = proj_keep[0].data_ptr(), proj_keep[1].data_ptr()
-            ba.proj_h0, ba.proj_k0 = bufs["hs"][NL - 1, 1].data_ptr(), D
-            ba.proj_h1, ba.proj_k1 = None, (lm.hidden_size if lm is not None else 0)
-            if lm is not None:
-                lm0 = (torch.empty(N, lm.hidden_size, device=dev), torch.empty(N, lm.hidden_size, device=dev))
-                lm0_hb = torch.empty(N, lm.hidden_size, dtype=torch.bfloat16, device=dev) if lm_hb is not None else None
-                lm0_args = lm.first_cell_args(lm_plan, next_token, 2, lm_c[0], lm_h[0], lm0[0], lm0[1],
-                                              hb_prev=lm_hb[0] if lm_hb is not None else None, hb_out=lm0_hb)
-                lm1 = lm1_args = None
-                if self.three_launches and lm0_args is not None and NLl == 2:
-                    lm1 = (torch.empty(N, lm.hidden_size, device=dev), torch.empty(N, lm.hidden_size, device=dev))
-                    lm1_args = lm.cell_args(lm_plan, 1, lm0[1], lm_c[1], lm_h[1], lm1[0], lm1[1])
-                if lm1_args is not None:
-                    # Round 5: a search step in THREE dependent launches (las/beam_search.py:94-158 is one loop).  The LM's first layer depends
-                    # on the step's tokens only: it runs as extra workgroups of the attention-row launch; its second layer rides with the
-                    # Speller's cell (two problems of one grid); the pruning launch gathers the survivors' state rows itself.  All state in
-                    # fixed buffers: the captured step is the same three launches every time.
-                    fa.companion_rows = ctypes.pointer(lm0_args)
-                    fa.companion = ctypes.pointer(lm1_args)
-                    mode["three"] = (lm0, lm1)
-                    for l, (cn, hn) in enumerate((lm0, lm1)):
-                        ba.state_in[k_lm + 2 * l], ba.state_in[k_lm + 2 * l + 1] = cn.data_ptr(), hn.data_ptr()
-                    ba.proj_h1 = lm1[1].data_ptr()
-                    ba.fold_gather = 1
-                elif lm0_args is not None:
-                    # the LM's first layer depends on the tokens only: it rides with the Speller's cell as the second problem of one grid
-                    fa.companion = ctypes.pointer(lm0_args)
-                    mode["lm0"] = lm0
-                    mode["lm0_hb"] = lm0_hb
-
-        def lm_cells():
-            # evident intent of the (syntactically broken) branch at las/beam_search.py:109-116,131-135:
-            # LM ids = LAS ids - 2, SOS (-> -1) fed as id 0; logits[:, 2:] += lm_weight * lm_logits
-            layer0 = mode.get("lm0") if mode["fused"] else None
-            tw = None
-            if lm_hb is not None:
-                tw = {"prev": lm_hb, "layer0": mode.get("lm0_hb") if layer0 is not None else None}
-            cs_new, hs_new = lm.step_fused(lm_plan, next_token, lm_c, lm_h, logits, 2, id_shift=2, project=False, layer0=layer0, twins=tw)
-            for l in range(NLl):
-                if tw is not None:
-                    ba.state_in[k_lm + l], ba.state_in[k_tw + l] = cs_new[l].data_ptr(), tw["new"][l].data_ptr()
-                else:
-                    ba.state_in[k_lm + 2 * l], ba.state_in[k_lm + 2 * l + 1] = cs_new[l].data_ptr(), hs_new[l].data_ptr()
-            if tw is not None:
-                cs_new = cs_new + tw["new"]                                       # (kept alive with the rest)
-            if mode["fused"]:
-                ba.proj_h1 = hs_new[-1].data_ptr()
-            held[:] = [cs_new, hs_new]                                            # alive until the gather has been enqueued
-
-        def lm_part():
-            if mode["fused"] and mode.get("three"):
-                return                               # both LM layers ran inside the Speller call's two launches
-            lm_cells()
-            if not mode["fused"]:
-                lm.project_fused(lm_plan, held[1][-1], logits, 2)
-
-        def ctc_part():                                  # CTC state advance and joint scores of the step (reads the device step counter)
-            _hip.check(lib.las_ctc_prefix_step(_hip.p(ctc_lp), _hip.p(ctc_len), n, beam, Tp, V_, self.end_id, _hip.p(logits), _hip.p(joint),
-                                               lam, _hip.p(ctc_par), _hip.p(ctc_cur), ctc_w, _hip.p(next_token), _hip.p(step),
-                                               _hip.p(nlive), _hip.p(done), _hip.p(dstep), Umax, _hip.stream()), "las_ctc_prefix_step")
-
-        def ngram_part():                                # n-gram state advance and LM scores of the step (reads the device step counter)
-            _hip.check(lib.las_ngram_step(_hip.p(ng_tab["child_off"]), _hip.p(ng_tab["child_tok"]), _hip.p(ng_tab["child_lp"]),
-                                          _hip.p(ng_tab["child_next"]), _hip.p(ng_tab["bow"]), _hip.p(ng_tab["bo"]), _hip.p(ng_tab["uni_lp"]),
-                                          _hip.p(ng_tab["uni_next"]), ng.num_nodes, ng.num_entries, ng.order, _hip.p(logits), n, beam, V_,
-                                          _hip.p(ng_par), _hip.p(ng_cur), ng_w, _hip.p(next_token), _hip.p(step), _hip.p(nlive),
-                                          _hip.p(done), _hip.p(dstep), Umax, _hip.stream()), "las_ngram_step")
-
-        def bias_part():                                 # hotword state advance and bonus of the step (reads the device step counter)
-            _hip.check(lib.las_bias_step(_hip.p(bias_tab["child_off"]), _hip.p(bias_tab["child_tok"]), _hip.p(bias_tab["child_next"]),
-                                         _hip.p(bias_tab["gdef"]), _hip.p(bias_tab["groot"]), float(ctx.beta), ctx.num_nodes,
-                                         int(ctx.child_tok.size), _hip.p(bias_scores), n, beam, V_, _hip.p(bias_par), _hip.p(bias_cur), bias_w,
-                                         _hip.p(next_token), _hip.p(step), _hip.p(nlive), _hip.p(done), _hip.p(dstep), Umax, _hip.stream()),
-                       "las_bias_step")
-
-        def beam_part():                                 # files alphas_cur under the device step counter, prunes, gathers, advances the counter
-            _hip.check(lib.las_beam_loop_step(ctypes.byref(ba), _hip.stream()), "las_beam_loop_step")
-
-        def one_step():
-            # (the LM's cells depend only on the tokens, but running them as a parallel branch on a second stream beside the Speller
-            # step LOSES on this device: 111 against 99.5 us per captured step -- the cross-queue joins cost more than the overlap gives)
-            speller_part()
-            if lm is not None:
-                lm_part()
-            if ng is not None:
-                ngram_part()
-            if lam > 0:
-                ctc_part()
-            if ctx is not None:
-                bias_part()
-            beam_part()
-
-        steps_run = 0
-        graph = None
+    def _run_steps(self, one_step, loop, sync_every, _after_launch):
+        """The steps of a search: step 0 eagerly, then -- captured once, at step 1 -- replays of a HIP graph of `steps_per_graph` steps (the
+        loop is bound by the host's launch rate otherwise: 5-8 launches and their Python glue per step).  `_after_launch` (decode_batches: the
+        next batch's host work and encoder launches) is called once, at the first `done` poll.  -> (steps run, whether the graph was used)"""
+        dev, Umax, steps_run, graph = loop.g.dev, loop.g.Umax, 0, None
         use_graph = self.use_graph and Umax > 2
         # One hipGraphLaunch costs the host more than a 3-launch step costs the device (r5 probe: 75-85 us per replayed step whatever the
         # step's kernels added up to -- 55-62 us): the captured graph holds K consecutive steps.  Every launch of a step reads the DEVICE
@@ -847,72 +598,47 @@ class BeamSearch(object):
                 steps_run = min(t, Umax)
                 if t >= next_check:                                                     # the only host wait inside the loop
                     next_check += sync_every
-                    if _after_launch is not None:                                       # (decode_batches: the next batch's host work and encoder
-                        _after_launch(); _after_launch = None                          #  launches, while the device runs the steps enqueued so far)
-                    if bool(done.all()):
+                    if _after_launch is not None:                                       # (while the device runs the steps enqueued so far)
+                        _after_launch(); _after_launch = None
+                    if bool(loop.done.all()):
                         break
         if _after_launch is not None:
             _after_launch()
-        del keep
-        mark("searched")
-        if _defer and not self.measure:
-            # decode_batches: everything behind the search -- back-tracking, the alignment gather, the read-back, the host objects -- as a
-            # closure that runs on a side stream behind THIS point of the launch stream: the caller launches the next batch's search first and
-            # calls it while the device is busy with that (the read-back waits for the side stream only).  This batch's tensors live in the
-            # closure until then.
-            ev = torch.cuda.Event()
-            ev.record()
-            if self._tail_stream is None:
-                self._tail_stream = torch.cuda.Stream()
+        return steps_run, graph is not None
 
-            alive = (hist_parent, hist_token, hist_slot, hist_score, hist_n, sel_t, sel_j, nsel, score, length, nlive, done, dstep, step,
-                     src_row, next_token)                 # `ba` holds their addresses
+    def _time_parts(self, parts, loop):
+        """LAS_DECODE_TIMING: device time of the parts of a decode step (HIP events, 50 eager repetitions each, after the search)
+        -> (live_steps, {part name: us})"""
+        dev, beam, done, nlive, step = loop.g.dev, loop.g.beam, loop.done, loop.nlive, loop.step
+        live_steps = int((loop.hist_n.sum(1) > 0).sum())              # steps in which some utterance still had a live hypothesis
+        step.zero_()
+        parts_us = {}
+        for part in parts:
+            forced = isinstance(part, S.Scorer)
+            if forced:
+                # every row live at a step > 0 (after the search every utterance is done and the kernel would return at once); the
+                # loop words are put back before the pruning part is timed
+                saved = (done.clone(), nlive.clone())
+                done.zero_(); nlive.fill_(beam); step[0] = 1
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.no_grad():
+                part.launch(); e0.record()
+                for _ in range(50):
+                    part.launch()
+                    if part is loop:
+                        step.zero_()
+                e1.record()
+            torch.cuda.synchronize(dev)
+            parts_us[part.name] = round(e0.elapsed_time(e1) / 50 * 1e3, 2)
+            if forced:
+                done.copy_(saved[0]); nlive.copy_(saved[1]); step.zero_()
+        return live_steps, parts_us
 
-            def finish(alive=alive):
-                ts_ = self._tail_stream
-                ts_.wait_event(ev)
-                with torch.cuda.stream(ts_):
-                    return self._decode_tail(dev, n, selcap, Umax, i32, ba, lib, alphas_hist, Tps, mark, kept)
-            return finish
-        results = self._decode_tail(dev, n, selcap, Umax, i32, ba, lib, alphas_hist, Tps, mark, kept)
-        mark("done")
-        parts = {}
-        if tm:        # device time of the parts of a decode step (HIP events, 50 eager repetitions each, after the search)
-            live_steps = int((hist_n.sum(1) > 0).sum())              # steps in which some utterance still had a live hypothesis
-            step.zero_()
-            for name, fn in (("speller", speller_part), ("lm", lm_part if lm is not None else None),
-                             ("ngram", ngram_part if ng is not None else None), ("ctc", ctc_part if lam > 0 else None),
-                             ("bias", bias_part if ctx is not None else None), ("beam", beam_part)):
-                if fn is None:
-                    continue
-                if name in ("ngram", "ctc", "bias"):
-                    # every row live at a step > 0 (after the search every utterance is done and the kernel would return at once); the
-                    # loop words are put back before the pruning part is timed
-                    saved = (done.clone(), nlive.clone())
-                    done.zero_(); nlive.fill_(beam); step[0] = 1
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                with torch.no_grad():
-                    fn(); e0.record()
-                    for _ in range(50):
-                        fn()
-                        if name == "beam":
-                            step.zero_()
-                    e1.record()
-                torch.cuda.synchronize(dev)
-                parts[name] = round(e0.elapsed_time(e1) / 50 * 1e3, 2)
-                if name in ("ngram", "ctc", "bias"):
-                    done.copy_(saved[0]); nlive.copy_(saved[1]); step.zero_()
-            ks = list(tm)
-            self.last_timing = {ks[i + 1]: round(tm[ks[i + 1]] - tm[ks[i]], 4) for i in range(len(ks) - 1)}
-            self.last_timing.update(steps=steps_run, live_steps=live_steps, rows=N, frames=Tp, graph=graph is not None, short_form=bool(mode["fused"]), parts_us=parts)
-            if self.args.verbose > 0:
-                print("decode_batch timing (s):", self.last_timing)
-        return results
-
-    def _decode_tail(self, dev, n, selcap, Umax, i32, ba, lib, alphas_hist, Tps, mark, kept=None):
+    def _decode_tail(self, loop, Tps, mark, kept=None):
         """What follows a search (decode_batch; on the current stream): the back pointers are walked on the device (las_beam_backtrack), one
         read-back, then the reference's host-side objects (las/beam_search.py:136-158, :297-312)."""
-        import ctypes
+        ba, selcap, alphas_hist, lib, dev, n, Umax = loop.ba, loop.selcap, loop.alphas_hist, _hip.lib(), loop.g.dev, loop.g.n, loop.g.Umax
+        i32 = dict(dtype=torch.int32, device=dev)
         # ---- the back pointers are walked on the device (las_beam_backtrack); one read-back, then the reference's host-side objects
         W = n * selcap
         w_ids = torch.zeros(W, Umax, **i32)
@@ -963,14 +689,3 @@ class BeamSearch(object):
             raise ValueError("--ctc_decode_weight %g: checkpoint %s holds no CTC head (%s); it was not trained with --ctc True"
                              % (self.ctc_weight, path, ", ".join(absent)))
         return path
-
-    def _select_best_k(self, beam_set, norm=False):
-        """reference las/beam_search.py:297-312 (host-side: used for the final ranking of <= 2*beam items)."""
-        if not beam_set:
-            return []
-        if norm:
-            log_prob = [b.log_prob / (len(b.token_ids) - 1) for b in beam_set]
-        else:
-            log_prob = [b.log_prob for b in beam_set]
-        idx = np.argsort(np.asarray(log_prob), kind="stable")[-self.beam_size:]
-        return [beam_set[i] for i in idx]

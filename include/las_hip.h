@@ -37,7 +37,7 @@ enum { LAS_ACT_NONE = 0, LAS_ACT_TANH = 1 };
 enum { LAS_ATT_ADD = 0, LAS_ATT_LOC = 1 };      /* las/las.py:44-49 */
 enum { LAS_DT_F32 = 0, LAS_DT_BF16 = 1 };       /* element type of a tensor in HBM (see las_gemm_kk) */
 
-#define LAS_HIP_ABI_VERSION 606      /* bumped whenever an argument struct or a signature changes: las_version() of a library
+#define LAS_HIP_ABI_VERSION 607      /* bumped whenever an argument struct or a signature changes: las_version() of a library
                                         built from another header differs, and the Python loader refuses it */
 int         las_version(void);
 const char* las_last_error(void);
@@ -371,11 +371,6 @@ typedef struct {
     const struct las_lstm_cell_args* companion;   /* optional, LAS_SPELLER_NO_LOGITS calls only: ANOTHER cell step (the LM's first layer in a beam
                                       search -- it depends on the tokens only) that is launched together with the Speller's cell, as
                                       the second problem of one grid: two dependent-launch slots of a search step become one */
-    const struct las_lstm_cell_args* companion_rows;   /* optional, LAS_SPELLER_NO_LOGITS calls only (round 5): a cell step that depends on the
-                                      step's TOKENS only (the LM's first layer, las/beam_search.py:109-116; exact transcendentals, fp32 or
-                                      one-hot input) launched as extra workgroups of the attention-row launch.  With the LM's SECOND layer as
-                                      `companion` and the state gather inside las_beam_loop_step (fold_gather) a search step is three
-                                      dependent launches: rows + LM 1, Speller cell + LM 2, beam. */
     int row_group;                 /* optional (0 = none; round 6): rows g row_group .. (g + 1) row_group - 1 have IDENTICAL enc / keys / enc_len -- a beam
                                       search's hypotheses of one utterance (las/beam_search.py:216 tiles the encoder output over them).  The
                                       per-step attention-row launches then place an utterance's rows on ONE XCD (workgroup id -> row mapping,
@@ -889,10 +884,6 @@ typedef struct {
      * proj_h1 NULL = no second part), proj_h0 / proj_h1 fp32 [nutt*beam, proj_k0 / proj_k1] (multiples of 32), fp32 accumulation.
      * ceil(beam/16) * ceil(V/16) <= 8.  `logits` (may be NULL then) additionally receives the values. */
     const float* proj_h0; int proj_k0; const float* proj_h1; int proj_k1; const void* proj_w; const float* proj_b;
-    /* round 5: fold_gather != 0 -- the state gather runs INSIDE the pruning launch (an utterance's workgroup copies the rows of its own
-     * surviving parents as soon as it has ranked them: rows of different utterances never mix) and the step counter is advanced by the
-     * workgroup that finishes last; `step` then points to TWO ints (step[1]: arrival counter, caller-zeroed).  One launch per step. */
-    int fold_gather;
 } las_beam_loop_args;
 int las_beam_loop_step(const las_beam_loop_args* a, void* stream);
 /* After the last step: walk the back-pointer records of every retired hypothesis on the device (the reference carries whole token

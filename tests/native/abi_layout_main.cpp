@@ -43,7 +43,7 @@ int main() {
     FIELD(las_speller_fwd_args, align0); FIELD(las_speller_fwd_args, emb_mask); FIELD(las_speller_fwd_args, emb_noise);
     FIELD(las_speller_fwd_args, hs); FIELD(las_speller_fwd_args, cs); FIELD(las_speller_fwd_args, gates); FIELD(las_speller_fwd_args, xin0);
     FIELD(las_speller_fwd_args, act_save); FIELD(las_speller_fwd_args, ws); FIELD(las_speller_fwd_args, ws_bytes);
-    FIELD(las_speller_fwd_args, status); FIELD(las_speller_fwd_args, companion); FIELD(las_speller_fwd_args, companion_rows);
+    FIELD(las_speller_fwd_args, status); FIELD(las_speller_fwd_args, companion);
     FIELD(las_speller_fwd_args, row_group);
     STRUCT(las_speller_bwd_args);
     FIELD(las_speller_bwd_args, f); FIELD(las_speller_bwd_args, dlogits); FIELD(las_speller_bwd_args, d_enc); FIELD(las_speller_bwd_args, d_keys);
@@ -73,7 +73,7 @@ int main() {
     FIELD(las_beam_loop_args, state_out); FIELD(las_beam_loop_args, state_width); FIELD(las_beam_loop_args, file_in);
     FIELD(las_beam_loop_args, file_out); FIELD(las_beam_loop_args, file_width); FIELD(las_beam_loop_args, proj_h0);
     FIELD(las_beam_loop_args, proj_k0); FIELD(las_beam_loop_args, proj_h1); FIELD(las_beam_loop_args, proj_k1); FIELD(las_beam_loop_args, proj_w);
-    FIELD(las_beam_loop_args, proj_b); FIELD(las_beam_loop_args, fold_gather);
+    FIELD(las_beam_loop_args, proj_b);
     STRUCT(las_input_config);
     FIELD(las_input_config, feat_dim); FIELD(las_input_config, is_training); FIELD(las_input_config, n_bounds); FIELD(las_input_config, bounds);
     FIELD(las_input_config, batch_limit); FIELD(las_input_config, max_tokenlen); FIELD(las_input_config, shuffle_buffer);

@@ -23,12 +23,11 @@ bs = BeamSearch(args, las, tok.token_to_id, lm)
 NUTT = int(os.environ.get("NUTT", "16"))
 utts = [synthetic_batch(1, 1274, 8, 30, seed=100 + k)[0] for k in range(NUTT)]
 bs.decode_batch(None, utts[:2]); bs.decode_batch(None, utts)
-for three, spg in ((False, 0), (False, 1), (False, 0), (False, 1)):
+for spg in (0, 1, 0, 1):
     bs.share_rows_from = spg
-    bs.three_launches = three
     bs.measure = True
     bs.decode_batch(None, utts)
-    print(three, spg, bs.last_timing)
+    print(spg, bs.last_timing)
     bs.measure = False
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(4): bs.decode_batch(None, utts)
