@@ -1,7 +1,8 @@
 // nbest.hip -- consensus over the N-best list a search ends with: the unit-cost Levenshtein distances among the hypotheses of
 // an utterance, the expected distance (risk) of each under the posteriors and the hypothesis of least risk (las_nbest_risk); the alignment
 // of every hypothesis to a pivot and the posterior mass that agrees with each pivot token (las_nbest_confidence).  The reference has
-// nothing of this kind; the yardstick is the numpy restatement tests/nbest_ref.py.
+// nothing of this kind; the yardstick is the numpy restatement tests/nbest_ref.py.  At the end of the file: the list's confusion
+// network (las_nbest_network; yardstick tests/confnet_ref.py), which shares the scan and the direction packing below.
 //
 // One wavefront per dynamic programme, no atomics, nothing depends on the launch geometry:
 //   nb_edit_dp            rows i = tokens of a, columns j = tokens of b, 64 columns (one per lane) at a time, all rows of a column chunk
@@ -270,6 +271,253 @@ extern "C" int las_nbest_confidence(const int* tok, const int* len, const int* n
     hipLaunchKernelGGL(nbest_align_kernel, dim3(cdiv(K, NB_WAVES), n), dim3(64 * NB_WAVES), 0, s, tok, len, nhyp, pivot, K, U, (unsigned*)ws);
     LAS_LAUNCHED();
     hipLaunchKernelGGL(nbest_trace_kernel, dim3(n), dim3(64 * NB_WAVES), 0, s, len, nhyp, w, pivot, K, U, (const unsigned*)ws, match, conf);
+    LAS_LAUNCHED();
+    return 0;
+}
+
+// ---- las_nbest_network (include/las_hip.h K10h) ------------------------------------------------------------------------------
+// One workgroup of ONE wave per utterance: the merges of an utterance are sequential, the utterances run side by side.  A bin is a ROW of
+// the workspace that never moves -- [slot symbols | distinct symbols in order of their first contributing slot], 4 ceil(K/4) words each --
+// and the network is the order of the rows: ord (LDS) maps a bin's place to its row, cnt (LDS, per row) holds the length of the
+// distinct-symbol list and whether EPS is in it.  Per merge of hypothesis b into the B bins so far:
+//   pre-pass   lane = bin: cup(i) and the first column D[i][0] (a wave prefix sum, carried over the 64-bin blocks) into LDS
+//   per chunk of 64 columns
+//     masks    lane = bin: has(i, b_j) for the chunk's 64 columns as one 64-bit word per bin, from the bin's distinct symbols (a few
+//              entries, four to a load, the next load in flight under the compares; scanning the slots merged so far would be up to 63).
+//              The loads of 64 bins are in flight together and nothing of this sits on the row-to-row chain
+//     rows     nb_edit_dp's row step: lane = column, the up move costs the row-uniform cup(i), the diagonal asks bit `lane` of the bin's mask
+//   walk       lane 0 over the staged direction words (nbest_trace_kernel's staging); step t describes the new network's bin B + ins - 1 - t:
+//              the place it had (or, for a new bin, the row it gets), b's token or EPS, and whether that symbol is new to the bin -- which
+//              the rule that fired already says (a match: no; a cost-1 diagonal: yes; EPS: cup(i); a new bin: yes).  The tails along
+//              i = 0 / j = 0 need no table and are written by all lanes
+//   rebuild    lane = step, all steps independent: the bin's row gets b's symbol in slot k (a new row EPS in the slots before) and, where it
+//              is new, one more distinct symbol; the new order goes into the other half of ord.  Stores only: no row is read or moved
+// At the end cols is the rows' slot symbols gathered in bin order, and one lane per bin adds the masses in slot order.
+namespace {
+
+constexpr int CN_MAX_BINS = 2048;
+constexpr int CN_EPS = -1;
+constexpr int CN_NEW = 0x4000;                                                 // in a step's token word: the symbol is new to its bin
+
+__host__ __device__ inline int cn_kp(int K) { return (K + 3) & ~3; }           // a row's two halves start 16-byte aligned
+__host__ __device__ inline size_t cn_dir_words(int U, int max_bins) { return (size_t)nb_rows(max_bins) * nb_pitch(U); }
+__host__ __device__ inline size_t cn_utt_words(int K, int U, int max_bins) { return cn_dir_words(U, max_bins) + (size_t)max_bins * 2 * cn_kp(K); }
+
+// grid n, 64 threads
+__global__ __launch_bounds__(64) void nbest_network_kernel(const int* __restrict__ sym, const int* __restrict__ len, const int* __restrict__ nhyp,
+                                                           const float* __restrict__ w, int K, int U, int max_bins, unsigned* ws, int* cols,
+                                                           int* nbins, signed char* merged, int* best, float* post) {
+    __shared__ unsigned long long smask[CN_MAX_BINS];                          // has(i, b_j) of the chunk in flight, bit = lane
+    __shared__ int col[CN_MAX_BINS + 1];                                       // the boundary column D[., j0-1]
+    __shared__ __attribute__((aligned(16))) int sb[NB_MAX_U];                  // b, negatives read as 0 (read four tokens at a time)
+    __shared__ unsigned stage[NB_STAGE];
+    __shared__ short psrc[CN_MAX_BINS], ptok[CN_MAX_BINS];                     // the walk's steps, back to front
+    __shared__ short ord[2][CN_MAX_BINS];                                      // place -> row, the current and the next network
+    __shared__ unsigned char cnt[CN_MAX_BINS], scup[CN_MAX_BINS];              // per row: distinct symbols, bit 7 = EPS among them; per place: cup
+    __shared__ float sw[NB_MAX_K];
+    const int u = blockIdx.x, lane = threadIdx.x;
+    const int nh = __builtin_amdgcn_readfirstlane(nb_clamp(nhyp[u], K));
+    const size_t r = (size_t)u * K;
+    const int Kp = cn_kp(K);
+    unsigned* dirs = ws + (size_t)u * cn_utt_words(K, U, max_bins);
+    int* rows = (int*)(dirs + cn_dir_words(U, max_bins));                      // row p: slot symbols at rows[p 2 Kp], distinct symbols Kp behind
+    const int pitch = nb_pitch(U);
+    int B = 0, nmerged = 0, cur = 0;
+    unsigned long long mmask = 0;                                              // bit k: slot k was merged
+    if (lane < nh) sw[lane] = w[r + lane];
+    for (int k = 0; k < nh; ++k) {
+        const int L = __builtin_amdgcn_readfirstlane(nb_clamp(len[r + k], U));
+        const int* b = sym + (r + k) * U;
+        __syncthreads();                                                       // the merge before is done with the LDS, and its stores are visible
+        for (int j = lane; j < L; j += 64) sb[j] = max(b[j], 0);
+        int carry = 0;
+        for (int i0 = 0; i0 < B; i0 += 64) {
+            const int i = i0 + lane;
+            const int cu = (i < B && !(cnt[ord[cur][i]] & 0x80)) ? 1 : 0;
+            int sc = cu;
+            for (int o = 1; o < 64; o <<= 1) {
+                const int v = __shfl_up(sc, o);
+                if (lane >= o) sc += v;
+            }
+            if (i < B) {
+                scup[i] = (unsigned char)cu;
+                col[i + 1] = carry + sc;
+            }
+            carry += __shfl(sc, 63);
+        }
+        if (lane == 0) col[0] = 0;
+        __syncthreads();
+        if (B > 0 && L > 0) {
+            for (int j0 = 1; j0 <= L; j0 += 64) {
+                // all 64 columns of the chunk, four tokens to an LDS read, a fixed trip count so that the reads run ahead of the compares;
+                // columns beyond L hold whatever sb held before (written or not): their bits are computed and never used
+                const int4* tb = (const int4*)(sb + j0 - 1);
+                for (int i = lane; i < B; i += 64) {
+                    const int row = ord[cur][i], n = cnt[row] & 0x7f;
+                    const int4* ds = (const int4*)(rows + ((size_t)row * 2 + 1) * Kp);
+                    unsigned long long m = 0;
+                    int4 v = ds[0];
+                    for (int c = 0; c < n; c += 4) {
+                        int4 nx = v;
+                        if (c + 4 < n) nx = ds[(c >> 2) + 1];
+                        const int e0 = v.x, e1 = c + 1 < n ? v.y : -2, e2 = c + 2 < n ? v.z : -2, e3 = c + 3 < n ? v.w : -2;    // (-2: no symbol)
+#pragma unroll 4
+                        for (int g = 0; g < 16; ++g) {
+                            const int4 t = tb[g];
+                            const unsigned h = (unsigned)((t.x == e0) | (t.x == e1) | (t.x == e2) | (t.x == e3)) |
+                                               (unsigned)((t.y == e0) | (t.y == e1) | (t.y == e2) | (t.y == e3)) << 1 |
+                                               (unsigned)((t.z == e0) | (t.z == e1) | (t.z == e2) | (t.z == e3)) << 2 |
+                                               (unsigned)((t.w == e0) | (t.w == e1) | (t.w == e2) | (t.w == e3)) << 3;
+                            m |= (unsigned long long)h << (4 * g);
+                        }
+                        v = nx;
+                    }
+                    smask[i] = m;
+                }
+                __syncthreads();
+                const int j = j0 + lane;
+                const bool act = j <= L;
+                int dprev = j0 - 1;
+                unsigned bits = 0;
+                int up = j;
+                for (int i = 1; i <= B; ++i) {
+                    const unsigned long long m = smask[i - 1];                 // (uniform addresses: broadcasts)
+                    const int cu = scup[i - 1], cin = col[i];
+                    int diag = __builtin_amdgcn_update_dpp(up, up, 0x138, 0xf, 0xf, false);    // wave_shr:1
+                    if (lane == 0) diag = dprev;
+                    const bool eq = (m >> lane) & 1ull;
+                    const int t = min(up + cu, diag + (eq ? 0 : 1));
+                    const int x = wave_prefix_min(act ? t - j : NB_BIG);
+                    const int d = j + min(cin - (j0 - 1), x);
+                    const unsigned dk = (eq && d == diag) ? 0u : (d == diag + 1 ? 1u : (d == up + cu ? 2u : 3u));
+                    bits |= dk << (2 * ((i - 1) & 15));
+                    if (((i - 1) & 15) == 15 || i == B) {
+                        if (act) dirs[(size_t)((i - 1) >> 4) * pitch + (j - 1)] = bits;
+                        bits = 0;
+                    }
+                    dprev = cin;
+                    up = d;
+                    if (lane == 63) col[i] = d;
+                }
+                __syncthreads();
+            }
+        }
+        // the walk from (B, L): step t describes the new network's bin B + ins - 1 - t
+        int i = B, j = L, t = 0, ins = 0;
+        while (i > 0 && j > 0) {                                               // (wave-uniform)
+            const int hi = (i - 1) >> 4, jw = j;
+            const int fit = NB_STAGE / jw;                                     // >= 2
+            const int lo = hi + 1 - fit > 0 ? hi + 1 - fit : 0;
+            for (int rb = lo; rb <= hi; ++rb)
+                for (int c = lane; c < jw; c += 64) stage[(rb - lo) * jw + c] = dirs[(size_t)rb * pitch + c];
+            __syncthreads();
+            if (lane == 0) {
+                while (i > 0 && j > 0 && ((i - 1) >> 4) >= lo) {
+                    const unsigned d = (stage[(((i - 1) >> 4) - lo) * jw + (j - 1)] >> (2 * ((i - 1) & 15))) & 3u;
+                    if (t < CN_MAX_BINS) {
+                        psrc[t] = (short)(d == 3 ? -1 - ins : i - 1);
+                        ptok[t] = (short)(d == 2 ? -1 : (d == 0 ? j : j | CN_NEW));
+                    }
+                    ++t;
+                    if (d == 3) ++ins;
+                    if (d <= 2) --i;
+                    if (d != 2) --j;
+                }
+            }
+            i = __builtin_amdgcn_readfirstlane(i);
+            j = __builtin_amdgcn_readfirstlane(j);
+            t = __builtin_amdgcn_readfirstlane(t);
+            ins = __builtin_amdgcn_readfirstlane(ins);
+            __syncthreads();
+        }
+        for (int q = lane; q < i; q += 64)                                     // column 0: the remaining bins get EPS
+            if (t + q < CN_MAX_BINS) {
+                psrc[t + q] = (short)(i - 1 - q);
+                ptok[t + q] = -1;
+            }
+        for (int q = lane; q < j; q += 64)                                     // row 0: the remaining tokens become new bins at the front
+            if (t + q < CN_MAX_BINS) {
+                psrc[t + q] = (short)(-1 - ins - q);
+                ptok[t + q] = (short)((j - q) | CN_NEW);
+            }
+        ins += j;
+        __syncthreads();
+        const int Bn = B + ins;
+        if (Bn > max_bins) continue;                                           // the overflow rule: the network stays as it is
+        for (int q = lane; q < Bn; q += 64) {
+            const int src = psrc[q], tk = ptok[q];
+            const int s = tk < 0 ? CN_EPS : sb[(tk & (CN_NEW - 1)) - 1];
+            int row;
+            if (src >= 0) {
+                row = ord[cur][src];
+                int* rp = rows + (size_t)row * 2 * Kp;
+                rp[k] = s;
+                if (tk < 0 ? scup[src] != 0 : (tk & CN_NEW) != 0) {            // one more distinct symbol
+                    const int c = cnt[row], n = c & 0x7f;
+                    if (n < K) rp[Kp + n] = s;
+                    cnt[row] = (unsigned char)((c & 0x80) | (n < K ? n + 1 : n) | (tk < 0 ? 0x80 : 0));
+                }
+            } else {                                                           // a new bin in the row B + (its number among the new ones)
+                row = B - 1 - src;
+                int* rp = rows + (size_t)row * 2 * Kp;
+                for (int l = 0; l < k; ++l) rp[l] = CN_EPS;
+                rp[k] = s;
+                if (nmerged > 0) rp[Kp] = CN_EPS;                              // EPS for every slot merged before
+                rp[Kp + (nmerged > 0 ? 1 : 0)] = s;
+                cnt[row] = (unsigned char)(nmerged > 0 ? 0x82 : 1);
+            }
+            ord[cur ^ 1][Bn - 1 - q] = (short)row;
+        }
+        cur ^= 1;
+        B = Bn;
+        ++nmerged;
+        mmask |= 1ull << k;
+    }
+    __syncthreads();
+    if (lane == 0) nbins[u] = B;
+    if (lane < nh) merged[r + lane] = (signed char)((mmask >> lane) & 1ull);
+    for (int k = 0; k < nh; ++k) {
+        if (!((mmask >> k) & 1ull)) continue;
+        for (int i = lane; i < B; i += 64) cols[(r + k) * max_bins + i] = rows[(size_t)ord[cur][i] * 2 * Kp + k];
+    }
+    for (int i = lane; i < B; i += 64) {
+        const int row = ord[cur][i], n = cnt[row] & 0x7f;
+        const int* rp = rows + (size_t)row * 2 * Kp;
+        int bs = CN_EPS;
+        float bm = 0.f;
+        for (int c = 0; c < n; ++c) {                                          // the list is in order of the first contributing slot
+            const int s = rp[Kp + c];
+            float acc = 0.f;
+            for (int k = 0; k < nh; ++k)
+                if (((mmask >> k) & 1ull) && rp[k] == s) acc = acc + sw[k];
+            if (c == 0 || acc > bm) {
+                bs = s;
+                bm = acc;
+            }
+        }
+        best[(size_t)u * max_bins + i] = bs;
+        post[(size_t)u * max_bins + i] = bm;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t las_nbest_network_workspace_bytes(int n, int K, int U, int max_bins) {
+    if (n <= 0 || K <= 0 || U <= 0 || max_bins <= 0) return 0;
+    return (size_t)n * cn_utt_words(K, U, max_bins) * sizeof(unsigned);
+}
+
+extern "C" int las_nbest_network(const int* sym, const int* len, const int* nhyp, const float* w, int n, int K, int U, int max_bins, int* cols,
+                                 int* nbins, signed char* merged, int* best, float* post, void* ws, size_t ws_bytes, void* stream) {
+    LAS_ARG(sym && len && nhyp && w && cols && nbins && merged && best && post,
+            "las_nbest_network: sym, len, nhyp, w, cols, nbins, merged, best and post must be given");
+    if (nb_check_sizes("las_nbest_network", n, K, U)) return -1;
+    LAS_ARG(max_bins >= 1 && max_bins <= CN_MAX_BINS, "las_nbest_network: max_bins=%d, 1 <= max_bins <= %d", max_bins, CN_MAX_BINS);
+    LAS_ARG(ws && ws_bytes >= las_nbest_network_workspace_bytes(n, K, U, max_bins), "las_nbest_network: workspace too small (%zu < %zu)",
+            ws_bytes, las_nbest_network_workspace_bytes(n, K, U, max_bins));
+    LAS_ARG(((uintptr_t)ws & 15) == 0, "las_nbest_network: the workspace must be 16-byte aligned");
+    hipLaunchKernelGGL(nbest_network_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, sym, len, nhyp, w, K, U, max_bins, (unsigned*)ws, cols,
+                       nbins, merged, best, post);
     LAS_LAUNCHED();
     return 0;
 }

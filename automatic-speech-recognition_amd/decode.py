@@ -1,7 +1,8 @@
 """decode.py -- beam-search evaluation entry point (counterpart of the reference's decode.py: utterances
 sorted by token length, one BeamSearch.decode per utterance, per-utterance and corpus WER, same log lines).
 --mbr True scores the minimum-Bayes-risk hypothesis of every N-best list (las.nbest; posteriors at --nbest_scale) instead of the
-top-scoring one: the effect on the corpus WER is read from the same log lines."""
+top-scoring one: the effect on the corpus WER is read from the same log lines.  --cn_decode True scores the consensus of every list's
+confusion network (las_nbest_network) in the same way; the two cannot be combined."""
 import logging
 import os
 import sys
@@ -10,7 +11,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from las import checkpoint, layers, variables                      # noqa: E402
-from las.arguments import parse_args                               # noqa: E402
+from las.arguments import check_confusion_flags, parse_args       # noqa: E402
 from las.beam_search import BeamSearch                             # noqa: E402
 from las.las import LAS, Listener, Speller                         # noqa: E402
 from las.utils import convert_idx_to_string, edit_distance        # noqa: E402
@@ -48,6 +49,7 @@ def restore_lm(lm, save_path):
 def main():
     import torch
     args = parse_args()
+    check_confusion_flags(args)
     logging.basicConfig(stream=sys.stdout, format='%(asctime)s %(levelname)s:%(message)s', level=logging.INFO, datefmt='%I:%M:%S')
     tokenizer = CharEncoder() if args.unit.lower() == "char" else SubwordEncoder(args.subword_dir)
     args.vocab_size = tokenizer.get_vocab_size()
@@ -122,10 +124,10 @@ def main():
             yield xs_list
 
     ann = None
-    if args.mbr:                                                   # (las.nbest is imported only when the flag is given)
+    if args.mbr or args.cn_decode:                                 # (las.nbest is imported only when one of the flags is given)
         from las import nbest as NB
-        args.nbest, args.confidence = 0, False                     # (transcribe.py's: nothing here prints them)
-        ann = NB.Annotator(args, bs.end_id)
+        args.nbest, args.confidence, args.confusion_network = 0, False, False      # (transcribe.py's: nothing here prints them)
+        ann = NB.Annotator(args, bs.end_id, id_to_token)
     # the model's objects live as long as the process: out of the cyclic collector's way (a full collection walks them all, 30-60 ms --
     # a batch and a half -- every few batches otherwise)
     import gc
@@ -134,10 +136,14 @@ def main():
     # decode_batches: the encoders of the next chunk run under the search of this one
     search = bs.ctc_decode_batches if ctc_only else bs.decode_batches          # --decoder: the CTC head alone, or the Speller's search
     for chunk, results in zip(chunks, search(None, batches())):
+        notes = ann.annotate(results) if ann is not None else [None] * len(results)
         chosen = [r[-1] for r in results] if ann is None else [a["state"] if a["state"] is not None else r[-1]
-                                                               for a, r in zip(ann.annotate(results), results)]
-        for i, state in zip(chunk, chosen):
-            hyp = convert_idx_to_string(state.token_ids[1:], id_to_token, args.unit)
+                                                               for a, r in zip(notes, results)]
+        for i, state, a in zip(chunk, chosen, notes):
+            if a is not None and "consensus" in a:                 # --cn_decode: the network's consensus, a text no search produced
+                hyp = a["consensus"]["text"]
+            else:
+                hyp = convert_idx_to_string(state.token_ids[1:], id_to_token, args.unit)
             ref = convert_idx_to_string(dev_tokens[i], id_to_token, args.unit)
             dist, n = edit_distance(ref.split(" "), hyp.split(" "))
             error += dist

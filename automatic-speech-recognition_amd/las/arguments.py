@@ -117,6 +117,13 @@ _EXTRA = [
     (("--mbr",), str2bool, False, "Print the minimum-Bayes-risk hypothesis of the N-best list (least expected token edit distance under the "
                                   "posteriors) instead of the top-scoring one."),
     (("--nbest_scale",), float, 1.0, "Scale of the search's ranking key in the softmax that gives the N-best posteriors."),
+    # N-best confusion network (las.nbest, las_nbest_network): all off by default
+    (("--confusion_network",), str2bool, False, "transcribe.py: every JSON line carries \"network\", the word alternatives per position "
+                                                "(the N-best list merged into a confusion network) with their posterior masses."),
+    (("--cn_decode",), str2bool, False, "Print the consensus of the confusion network (the most probable word at every position) instead "
+                                        "of the top-scoring hypothesis."),
+    (("--cn_alternatives",), int, 3, "--confusion_network: alternatives listed per position (1 to 8)."),
+    (("--cn_unit",), str, "word", "Symbols of the confusion network: word (a word is its printed text) or token."),
     (("--lm_dir",), str, "lang/output/", "Output directory of train_lm.py (result.json, vocab.json, models) for --apply_lm."),
     (("--frontend",), str, "cpu", "Feature extraction of preprocess.py: cpu = the float64 numpy restatement, gpu = the HIP front end "
                                   "(las.frontend.FeatureExtractor, fp32)."),
@@ -154,6 +161,27 @@ def build_parser(extra=True):
 def parse_args(argv=None):
     """reference las/arguments.py:12 (argv=None -> sys.argv[1:])."""
     return build_parser().parse_args(argv)
+
+
+def check_confusion_flags(args):
+    """--confusion_network / --cn_decode against the flags they cannot go with: a ValueError before anything is built.  Reads every flag
+    with a default, so a namespace from before these flags (or without transcribe.py's own) passes.  -> True when one of the two is on"""
+    cn, dec = bool(getattr(args, "confusion_network", False)), bool(getattr(args, "cn_decode", False))
+    if not (cn or dec):
+        return False
+    top, unit = int(getattr(args, "cn_alternatives", 3)), str(getattr(args, "cn_unit", "word"))
+    if not 1 <= top <= 8:
+        raise ValueError("--cn_alternatives must be in [1, 8] (got %d)" % top)
+    if unit not in ("word", "token"):
+        raise ValueError("--cn_unit %s: word or token" % unit)
+    if getattr(args, "keywords", None) is not None:
+        raise ValueError("--keywords skips the search and prints keyword hits only, --confusion_network / --cn_decode read the search's "
+                         "N-best list: use one of them")
+    if dec and getattr(args, "mbr", False):
+        raise ValueError("--cn_decode prints the network's consensus, --mbr the listed hypothesis of least risk: use one of them")
+    if dec and (getattr(args, "timestamps", False) or getattr(args, "align_text", None) is not None):
+        raise ValueError("--cn_decode prints a hypothesis no search produced; aligning it (--timestamps / --align_text) is not built")
+    return True
 
 
 def reference_flag_names():

@@ -9,6 +9,7 @@
     python transcribe.py --hotwords names.txt --hotword_weight 2.0 a.wav ...   (contextual biasing: the search boosts the listed phrases)
     python transcribe.py --ngram_lm lm.arpa --ngram_weight 0.5 a.wav ...       (n-gram LM shallow fusion: train_ngram.py writes lm.arpa)
     python transcribe.py --nbest 5 --confidence True --mbr True a.wav ...      (N-best consensus: alternatives, confidences, MBR choice)
+    python transcribe.py --confusion_network True --cn_decode True a.wav ...   (word alternatives per position, and their consensus)
     python transcribe.py --ctc True --decoder ctc --beam_size 16 a.wav ...     (the CTC head alone: prefix beam search, greedy with --beam_size 1)
     python transcribe.py --noise_file cafe.wav --snr_db 10 --rir_file room.wav a.wav ...   (the files as they would sound in that condition)
     python transcribe.py --ctc True --keywords names.txt a.wav ...     (keyword search: where the CTC head hears a listed phrase, no search)
@@ -33,6 +34,14 @@ posterior mass that agrees with one of its tokens; --mbr prints the hypothesis o
 top-scoring one, and --timestamps / --confidence then describe that one.  Without --timestamps "score" is the search's score.  With
 --segment a file's confidence is the minimum over its segments, its words are concatenated and "nbest" stays with the segments.
 
+With --confusion_network True (las.nbest.network, las_nbest_network; JSON lines) the ranked list is merged, best first, into a confusion
+network and every line carries "network": [[{"word", "p"}, ...], ...]: per position the --cn_alternatives (1 to 8, default 3) words of
+largest posterior mass, "" = no word here; --cn_unit token keeps the tokenizer's pieces instead of words.  --cn_decode True prints the
+network's consensus -- the first alternative of every position, "" left out, joined by one space -- instead of the 1-best; no search
+produced that text, so "score" is null, and with --confidence "words" carry the positions' masses and "confidence" is their minimum.
+Both go with either decoder, --rescore, --segment (a file's network is its segments' positions in order) and --nbest / --confidence /
+--mbr; --cn_decode cannot be combined with --mbr, --timestamps or --align_text, neither flag with --keywords.
+
 With --noise_file and / or --rir_file (las.augment, csrc/wave_aug.hip) every recording is convolved with the room response and mixed
 with the noise at --snr_db on the device, between the resampler and the front end: a model's robustness checked without writing audio
 files.  The noise starts at its first sample and wraps around; both files are resampled to --sample_rate.  Without the two flags
@@ -43,7 +52,8 @@ listener, the head, and one las_kws_search per batch.  Every file's line is {"hi
 "confidence"}]}, sorted by start, then by the phrase's place in the list: score = the log-likelihood ratio of the phrase's best path
 against the head's frame-wise best path over the same frames (<= 0), confidence = exp(score / tokens of the phrase).  A hit needs
 score >= --keyword_threshold x tokens (default -1.0 nat per token, not measured on a trained model); --keyword_max_hits (1 to 8) hits
-are kept per file and phrase.  It cannot be combined with --align_text, --segment, --timestamps, --nbest, --confidence or --mbr.
+are kept per file and phrase.  It cannot be combined with --align_text, --segment, --timestamps, --nbest, --confidence, --mbr,
+--confusion_network or --cn_decode.
 
 The files are read with preprocess.read_audio (.flac needs `soundfile`), `--decode_batch` of them at a time go through the device front
 end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip; a file at another rate than --sample_rate is resampled
@@ -62,7 +72,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from las import layers, variables                                  # noqa: E402
 from las import align as A                                         # noqa: E402
 from las import vad as VAD                                         # noqa: E402
-from las.arguments import build_parser, str2bool                   # noqa: E402
+from las.arguments import build_parser, check_confusion_flags, str2bool   # noqa: E402
 from las.beam_search import BeamSearch                             # noqa: E402
 from las.frontend import FeatureExtractor                          # noqa: E402
 from las.las import LAS, Listener, Speller                         # noqa: E402
@@ -92,7 +102,15 @@ def annotated(args, bs, ann, results, id_to_token):
     rescored = getattr(results, "rescored", None)                      # --rescore attention: both passes' scores of every listed hypothesis
     for u, (a, tokens, score, span) in enumerate(zip(notes, token_lists, scores, spans)):
         extra = {}
-        if ann.confidence:
+        if ann.cn:
+            extra["network"] = a.get("network", [])
+        if ann.cn_decode:                                              # the consensus: a text no search produced, so it has no score
+            cons = a.get("consensus", dict(words=[], conf=[], tokens=[], text=""))
+            extra["text"], score = cons["text"], None
+            if ann.confidence:
+                extra["confidence"] = min(cons["conf"]) if cons["conf"] else None
+                extra["word_conf"] = [{"word": w, "confidence": c} for w, c in zip(cons["words"], cons["conf"])]
+        elif ann.confidence:
             extra["confidence"] = a["posterior"]
             extra["word_conf"] = NB.word_confidence(a["tokens"], a["conf"], id_to_token, args.unit)
         if ann.nbest:
@@ -121,6 +139,10 @@ def json_fields(args, tokens, score, span, extra, id_to_token, frame_s, duration
         d["words"] = words
     if "nbest" in extra:
         d["nbest"] = extra["nbest"]
+    if "text" in extra:                                                # --cn_decode
+        d["text"] = extra["text"]
+    if "network" in extra:
+        d["network"] = extra["network"]
     return d
 
 
@@ -142,6 +164,7 @@ def main(argv=None):
     parser.add_argument("--keyword_max_hits", type=int, default=4, help="Hits kept per file and phrase, the strongest (1 to 8).")
     VAD.add_flags(parser, str2bool)
     args = parser.parse_args(argv)
+    network = check_confusion_flags(args)
     if args.keywords is not None:
         if not args.ctc:
             raise ValueError("--keywords needs the CTC head: decode with --ctc True (a model trained with --ctc)")
@@ -171,9 +194,10 @@ def main(argv=None):
         ctc_only = ctc_search.check_args(args) and args.align_text is None
     if args.timestamps and not args.ctc:
         raise ValueError("--timestamps needs the CTC head: decode with --ctc True (a model trained with --ctc)")
-    consensus = bool(args.nbest or args.confidence or args.mbr)
+    consensus = bool(args.nbest or args.confidence or args.mbr or network)
     if consensus and args.align_text is not None:
-        raise ValueError("--nbest / --confidence / --mbr read the search's N-best list, --align_text skips the search: use one of them")
+        raise ValueError("--nbest / --confidence / --mbr%s read the search's N-best list, --align_text skips the search: use one of them"
+                         % (" / --confusion_network" if network else ""))
     logging.basicConfig(stream=sys.stderr, format='%(asctime)s %(levelname)s:%(message)s', level=logging.INFO, datefmt='%I:%M:%S')
     if not args.synthetic and not args.audio:
         parser.error("no audio files (or --synthetic True)")
@@ -214,7 +238,7 @@ def main(argv=None):
     ann = None
     if consensus:                                                      # (las.nbest is imported only when one of its flags is given)
         from las import nbest as NB
-        ann = NB.Annotator(args, bs.end_id)
+        ann = NB.Annotator(args, bs.end_id, id_to_token)
     fe = FeatureExtractor(args, device=dev)
     condition = None
     if args.noise_file or args.rir_file:                               # (las.augment is imported only when one of its flags is given)
@@ -358,6 +382,8 @@ def transcribe_segmented(args, bs, extract, va, load, count, nb, id_to_token, fr
                     line["confidence"] = min(conf) if conf else None
                 if ann.confidence or args.timestamps:
                     line["words"] = [w for d in done for w in d["words"]]
+                if ann.cn:                                             # a file's network: its segments' bins in order
+                    line["network"] = [b for d in done for b in d["network"]]
                 line["segments"] = done
                 print(json.dumps(line))
                 continue

@@ -851,6 +851,42 @@ int las_nbest_confidence(const int* tok, const int* len, const int* nhyp, const 
                          signed char* match, float* conf, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K10h  confusion network over the N-best list: the hypotheses of an utterance merged one after the other into a word
+ * transition network (ROVER, Fiscus 1997) by a minimum-cost alignment with 0/1 costs; per bin the symbol of largest posterior mass.
+ * Plain arguments; sym / len / nhyp / w as tok / len / nhyp / w of K10g (len and nhyp clamped the same way), except that symbols are
+ * >= 0: a negative value is read as 0.  EPS = -1 is "no word here".  max_bins = the bins an utterance's network may have.
+ * Per utterance the live slots are merged in the order k = 0 .. nhyp - 1 (the host passes them best first), starting from an empty
+ * network, B = 0 bins.  To merge hypothesis b (length L) into B bins, with has(i, s) = symbol s was put into bin i by a hypothesis
+ * merged before, cup(i) = 0 if has(i, EPS) else 1:
+ *   D[0][j] = j,  D[i][0] = D[i-1][0] + cup(i),
+ *   D[i][j] = min(D[i-1][j] + cup(i), D[i][j-1] + 1, D[i-1][j-1] + (has(i, b[j-1]) ? 0 : 1)),
+ * traced back from (B, L) by ONE rule at (i, j), checked in this order:
+ *   1. i, j > 0, has(i, b[j-1]) and D[i][j] == D[i-1][j-1]: b's token joins bin i as a match, to (i-1, j-1);
+ *   2. i, j > 0 and D[i][j] == D[i-1][j-1] + 1: b's token becomes a new alternative of bin i, to (i-1, j-1);
+ *   3. i > 0 and D[i][j] == D[i-1][j] + cup(i): b contributes EPS to bin i, to (i-1, j);
+ *   4. otherwise a NEW BIN is inserted directly behind bin i, holding b's token for this slot and EPS for every slot merged before, to
+ *      (i, j-1).
+ * Overflow: with ins = the number of rule-4 steps, if B + ins > max_bins the hypothesis is NOT merged: the network stays as it is,
+ * merged[u, k] = 0, and the later hypotheses are still tried.
+ *   cols   int32 [n, K, max_bins]  cols[u, k, i] = the symbol slot k put into bin i, or EPS: the multi-alignment matrix.  Row k without its
+ *                                  EPS entries is hypothesis k.  Rows of slots that were not merged are not written
+ *   nbins  int32 [n]               the bins of the utterance's network (0 where nhyp = 0)
+ *   merged int8  [n, K]            1 where the live slot was merged, else 0
+ *   best   int32 [n, max_bins]     per bin the symbol (EPS included) of largest mass, mass(s) = sum over merged k with cols[k][i] == s of
+ *   post   fp32  [n, max_bins]     w[k], added in k order from 0.f, one fp32 add each (bit-identical to sequential numpy float32); on equal
+ *                                  mass the symbol whose first contributing slot is lower wins; post = that mass
+ * Nothing is written beyond nbins[u], for absent slots, or -- but nbins = 0 -- for an utterance with nhyp = 0.  Integer outputs are
+ * exact, no atomics, one wavefront per utterance whatever the batch: two runs, and the same utterance anywhere in any batch, give the
+ * same bits.  CEILING: 1 <= K <= 64, 1 <= U <= 1024, 1 <= max_bins <= 2048, n <= 65535; outside that, or with ws_bytes <
+ * las_nbest_network_workspace_bytes(n, K, U, max_bins) (per utterance the packed directions of the one table in flight, ceil(max_bins/16)
+ * 64 ceil(U/64) words, and max_bins 8 ceil(K/4) words of network) or a workspace that is not 16-byte aligned, the call returns < 0 with
+ * a las_last_error text before anything is launched.  One launch on `stream`, no synchronisation.
+ */
+size_t las_nbest_network_workspace_bytes(int n, int K, int U, int max_bins);
+int las_nbest_network(const int* sym, const int* len, const int* nhyp, const float* w, int n, int K, int U, int max_bins, int* cols,
+                      int* nbins, signed char* merged, int* best, float* post, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K10b device-resident BeamSearch.decode loop (las/beam_search.py:94-158) for `nutt` utterances at once: ONE call per
  * step prunes every utterance exactly as las_beam_step does AND keeps the reference's bookkeeping on the device, so
  * the host never waits inside the loop:
