@@ -10,40 +10,9 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from las import checkpoint, layers, variables                      # noqa: E402
 from las.arguments import check_confusion_flags, parse_args       # noqa: E402
-from las.beam_search import BeamSearch                             # noqa: E402
-from las.las import LAS, Listener, Speller                         # noqa: E402
+from las.cli import build_search, load_lm, restore_lm              # noqa: E402,F401
 from las.utils import convert_idx_to_string, edit_distance        # noqa: E402
-from utils.tokenizer import CharEncoder, SubwordEncoder            # noqa: E402
-
-
-def load_lm(init_dir, store=None):
-    """reference decode.py:27-39: build the inference CharRNN from `result.json` (hyper-parameters written by
-    train_lm.py:270-272) and `vocab.json` of the LM output directory."""
-    import json
-    from lang.char_rnn_model import CharRNN
-    with open(os.path.join(init_dir, 'result.json'), 'r') as f:
-        result = json.load(f)
-    params = dict(result['params'])
-    with open(os.path.join(init_dir, 'vocab.json'), 'r') as f:
-        vocab_index_dict = json.load(f)
-    params["vocab_size"] = len(vocab_index_dict)
-    params["num_unrollings"] = 1
-    params["batch_size"] = 1
-    logging.info('Creating rnnlm graph')
-    lm = CharRNN(is_training=False, use_batch=True, store=store, **params)
-    return lm, result
-
-
-def restore_lm(lm, save_path):
-    """reference decode.py:41-53: restore the LM's variables (this build: a torch-saved {name: array} dictionary written
-    by train_lm.py; the names are the reference's TF variable names under the `lm` scope)."""
-    import torch
-    sd = torch.load(save_path, map_location="cpu", weights_only=True)
-    lm.params()                                     # create the variables, then overwrite them
-    lm.store.load({k: v for k, v in sd["params"].items() if k.startswith(lm.scope + "/")})
-    logging.info("Rnnlm restored: {}".format(save_path))
 
 
 def main():
@@ -51,11 +20,6 @@ def main():
     args = parse_args()
     check_confusion_flags(args)
     logging.basicConfig(stream=sys.stdout, format='%(asctime)s %(levelname)s:%(message)s', level=logging.INFO, datefmt='%I:%M:%S')
-    tokenizer = CharEncoder() if args.unit.lower() == "char" else SubwordEncoder(args.subword_dir)
-    args.vocab_size = tokenizer.get_vocab_size()
-    id_to_token, token_to_id = tokenizer.id_to_token, tokenizer.token_to_id
-    layers.set_cell(args.cell)
-    layers.set_precision(args.dtype)
     # replicas only: under torch.distributed.run every rank decodes its round-robin share of the
     # length-sorted utterance list and the (errors, words) counts are all-reduced at the end
     from las import parallel
@@ -64,29 +28,12 @@ def main():
     dev = torch.device("cuda", local_rank)
     dp = parallel.init_from_env(dev)
     rank, world = (dp.rank, dp.world) if dp is not None else (0, 1)
-    variables.reset_default_store(device=dev, seed=args.seed)
-    las = LAS(args, Listener, Speller, token_to_id)
     ctc_only = False
     if args.decoder != "attention" or args.rescore != "none":      # (las.ctc_search is imported only when one of the flags is given)
         from las import ctc_search
         ctc_only = ctc_search.check_args(args)
-    lm = None
-    if args.apply_lm:                                              # decode.py:68-75
-        logging.info("Apply RNNLM...")
-        st = variables.default_store()
-        if args.synthetic and not os.path.exists(os.path.join(args.lm_dir, "result.json")):
-            from lang.char_rnn_model import CharRNN              # smoke / bench runs: the shipped LM shape, random weights
-            lm = CharRNN(False, 1, 1, 28, 512, embedding_size=0, num_layers=2, store=st)
-            lm.params()
-        else:
-            lm, result = load_lm(args.lm_dir, st)
-            lm.params()
-    las.build_variables()
-    bs = BeamSearch(args, las, token_to_id, lm)
-    ckpt = bs.restore_las(None, args.save_dir, args.restore_epoch)
-    logging.info("LAS restored: {}".format(ckpt))
-    if lm is not None and os.path.exists(os.path.join(args.lm_dir, "result.json")):
-        restore_lm(lm, result['best_model'])
+    tokenizer, bs, _, search = build_search(args, dev, ctc_only, restore_las=True, restore_lm_weights=True, log_lm=True)
+    id_to_token = tokenizer.id_to_token
     if args.synthetic:
         from data import SyntheticBatches
         (audio, audiolen), (y, tokenlen) = next(SyntheticBatches(args.feat_dim, args.vocab_size, seed=args.seed + 2, batch_scale=0.1, max_frames=700))
@@ -133,8 +80,7 @@ def main():
     import gc
     gc.collect()
     gc.freeze()
-    # decode_batches: the encoders of the next chunk run under the search of this one
-    search = bs.ctc_decode_batches if ctc_only else bs.decode_batches          # --decoder: the CTC head alone, or the Speller's search
+    # decode_batches: the encoders of the next chunk run under the search of this one (--decoder ctc: the CTC head's search)
     for chunk, results in zip(chunks, search(None, batches())):
         notes = ann.annotate(results) if ann is not None else [None] * len(results)
         chosen = [r[-1] for r in results] if ann is None else [a["state"] if a["state"] is not None else r[-1]
