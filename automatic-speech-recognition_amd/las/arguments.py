@@ -147,6 +147,17 @@ _EXTRA = [
     (("--noise_file",), str, "", "transcribe.py: mix this recording into every file at --snr_db before it is transcribed."),
     (("--snr_db",), float, 10.0, "transcribe.py: the signal-to-noise ratio in dB of --noise_file."),
     (("--rir_file",), str, "", "transcribe.py: convolve every file with this room impulse response before it is transcribed."),
+    # minimum word error rate training (las.mwer, csrc/mwer.hip): off by default
+    (("--mwer",), str2bool, False, "Train on the expected number of word errors over K hypotheses per utterance (MWER) plus a weighted "
+                                   "cross entropy on the reference, instead of the cross entropy alone."),
+    (("--mwer_hyps",), int, 4, "--mwer: hypotheses K per utterance (1 to 63), drawn inside the Speller loop unless LAS.train gets hyps=."),
+    (("--mwer_ce_weight",), float, 0.01, "--mwer: weight of the reference's cross entropy beside the expected word errors."),
+    (("--mwer_unit",), str, "word", "--mwer: errors are counted in words (one device-to-host read-back per step for the word mapping) or "
+                                    "in tokens (none)."),
+    (("--mwer_norm",), str, "", "--mwer: sample = every hypothesis weighs 1 / K (the default for drawn hypotheses: duplicates would be "
+                                "counted twice under nbest), nbest = the model's posterior renormalised over the list (the default "
+                                "with hyps=)."),
+    (("--mwer_extra_steps",), int, 4, "--mwer: drawn hypotheses may be this many steps longer than the reference."),
 ]
 
 

@@ -530,15 +530,18 @@ class _CELoss(torch.autograd.Function):
         return dl * g, None, None, None, None
 
 
-def _ce_loss(logits_bt, y_i32, V_, smooth, scale):
+def _ce_loss(logits_bt, y_i32, V_, smooth, scale, out=None):
     """-> (loss = sum(ce * mask) * scale as a 0-d view, dlogits with `scale` already in it, sums [3]).  One kernel pair: the sums are
-    written (no fill in front), the scaled loss is sums[2] (no multiply behind)."""
+    written (no fill in front), the scaled loss is sums[2] (no multiply behind).  out: a view with the logits' strides that receives the
+    gradient instead of a fresh buffer (the --mwer step: the reference rows of the gradient las_mwer_loss has written); False: the
+    value alone, no gradient."""
     B, U, _ = logits_bt.shape
     sb, st_, sv = logits_bt.stride()
     assert sv == 1
     dev = logits_bt.device
     sums = torch.empty(3, device=dev)
-    dl = torch.empty_strided(logits_bt.shape, logits_bt.stride(), device=dev)
+    dl = torch.empty_strided(logits_bt.shape, logits_bt.stride(), device=dev) if out is None else (None if out is False else out)
+    assert dl is None or (dl.shape == logits_bt.shape and dl.stride() == logits_bt.stride())
     nb = _hip.lib().las_ce_loss_workspace_bytes(B, U)
     ws = _hip.workspace(dev, nb, "ce")
     _hip.check(_hip.lib().las_ce_loss(_hip.p(logits_bt), sb, st_, _hip.p(y_i32), y_i32.shape[1], B, U, V_, 0.01,
@@ -640,6 +643,8 @@ class LAS:
         self.recovered_steps = 0  # steps re-run after a time-out status (tests / logs)
         self.last_out = None      # what the newest train step returned -- of its RE-RUN when the step was lost and recovered
         self.specaug = None       # las.specaug.SpecAugment, built by the first train step under --spec_augment True
+        self.last_mwer = None     # --mwer: the newest step's labels, lengths, error counts, log-likelihoods, risk (las.mwer.loss_rows)
+        self.keep_mwer_logits = False   # (tests: last_mwer also holds the step's [n S, U, V] logits and their gradient)
 
     # -- helpers -----------------------------------------------------------------------------------
     @staticmethod
@@ -703,8 +708,11 @@ class LAS:
         return max(self.args.lr * decay_rate ** (gs / decay_step), min_rate * self.args.lr)
 
     # -- one optimisation step ---------------------------------------------------------------------
-    def train(self, xs, ys, coins=None, sampled=None):
+    def train(self, xs, ys, coins=None, sampled=None, hyps=None):
         """reference las/las.py:226-304, executed eagerly.
+
+        hyps (--mwer True only): per utterance at most --mwer_hyps token id lists -- an N-best list -- whose expected word
+        errors the step minimises; None under --mwer: the hypotheses are drawn inside the Speller loop.
 
         Returns (loss, train_op, global_step, logits, alphas, summaries, sample_rate) -- `train_op`
         is None (the update has already been applied), `summaries` a dict of the quantities the
@@ -715,7 +723,12 @@ class LAS:
         device skips that step's update and -- the word is sticky -- every later one.  Instead of raising, a single-process run
         re-runs the lost steps: the first of them on the schedule that needs no co-residency (per-step Speller launches, no
         cross-stream hand-overs), the others as usual -- see _recover."""
-        out = self._train_step(xs, ys, coins, sampled)
+        if hyps is not None and not getattr(self.args, "mwer", False):
+            raise ValueError("LAS.train: hyps= belongs to --mwer True")
+        if getattr(self.args, "mwer", False) and (coins is not None or sampled is not None):
+            raise ValueError("LAS.train: coins= / sampled= steer scheduled sampling; a --mwer step teacher-forces its rows or draws them "
+                             "whole (pass hyps= for strings of your own)")
+        out = self._train_step(xs, ys, coins, sampled, hyps)
         code = self._pending_status
         self._pending_status = 0
         if code:
@@ -763,8 +776,8 @@ class LAS:
         out = None
         self._in_recovery = True
         try:
-            for gs, xs, ys, coins, sampled in todo:
-                out = self._train_step(xs, ys, coins, sampled)
+            for gs, xs, ys, coins, sampled, hyps in todo:
+                out = self._train_step(xs, ys, coins, sampled, hyps)
         finally:
             self._in_recovery = False
         torch.cuda.synchronize(dev)                  # the re-run steps must have gone through before anything is built on them
@@ -776,7 +789,7 @@ class LAS:
                                "recurrent sweeps' clusters beside what else is running on it")
         return out
 
-    def _train_step(self, xs, ys, coins=None, sampled=None):
+    def _train_step(self, xs, ys, coins=None, sampled=None, hyps=None):
         if RECOVER_STEPS and self.dp is not None and not self._in_recovery:
             # data parallel: every rank looks at the ALL-REDUCED guard slot of the step DP_LAG steps back (a pinned copy enqueued behind
             # that step's exchange; its event is long past in steady state) -- the same value on every rank, examined at the same call,
@@ -789,10 +802,16 @@ class LAS:
                     self._recover(int(_hip.status_word(dev)[0].item()) or 3, first=gs)
                     break
         with L.fallback_schedule(V.default_store().global_step < self._fallback_until):
-            return self._train_step_impl(xs, ys, coins, sampled)
+            return self._train_step_impl(xs, ys, coins, sampled, hyps)
 
-    def _train_step_impl(self, xs, ys, coins=None, sampled=None):
+    def _train_step_impl(self, xs, ys, coins=None, sampled=None, hyps=None, evaluate=False):
+        """evaluate (LAS.mwer_risk): the --mwer forward and loss only -- no gradient, no update, no step count; -> las.mwer.loss_rows' dict"""
         ctc = bool(self.args.ctc)
+        mw = None
+        if getattr(self.args, "mwer", False):
+            from las import mwer as MW
+            # (data parallel, --ctc, K, a hypothesis outside the vocabulary: refused before anything is enqueued)
+            mwer_strings = MW.check_step(self, hyps, int(np.asarray(torch.as_tensor(ys[1]).cpu()).size))
         if ctc:
             # tf.nn.ctc_loss (ignore_longer_outputs_than_inputs=False) refuses a row with more labels than frames: refused here, on the
             # host, before anything is enqueued (both lengths are host values)
@@ -811,7 +830,7 @@ class LAS:
         dev = self._device()
         st = V.default_store()
         self.build_variables()
-        if RECOVER_STEPS and self.dp is None:
+        if RECOVER_STEPS and self.dp is None and not evaluate:
             # the host may run ahead of the device, but not further than _recover can reach back: wait for the end of the step four
             # steps ago (normally long past -- the host is one or two steps ahead -- so this costs nothing; behind a time-out, whose
             # bounded polls take a second to drain, it keeps the host from enqueueing hundreds of steps that will all be skipped)
@@ -831,15 +850,17 @@ class LAS:
         # ... and on the auxiliary ("chain") stream: a dozen tiny kernels (0.1 ms back to back) that only the Speller and the
         # backward pass need run next to the first Listener sweep instead of in front of it
         with _hip.on_chain_stream():
-            if RECOVER_STEPS:
+            if RECOVER_STEPS and not evaluate:
                 # what _recover needs to re-run this step: the batch as it is NOW.  A caller may hand in device tensors that it overwrites
                 # a few steps later (las.input_pipeline.DeviceFeeder keeps a ring of three device slots): those are copied -- here, on the
                 # auxiliary stream beside the first Listener sweep, off the dependency chain; tensors this call made itself are held as is
                 a_hold = audio.clone() if (torch.is_tensor(xs[0]) and xs[0].is_cuda) else audio
                 y_hold = y.clone() if (torch.is_tensor(ys[0]) and ys[0].is_cuda) else y
                 hostcopy = lambda v: None if v is None else (v.detach().cpu().numpy().copy() if torch.is_tensor(v) else np.array(v, copy=True))
-                self._recent.append((st.global_step, (a_hold, hostcopy(audiolen)), (y_hold, hostcopy(tokenlen)), hostcopy(coins), hostcopy(sampled)))
-            st.zero_grad()
+                self._recent.append((st.global_step, (a_hold, hostcopy(audiolen)), (y_hold, hostcopy(tokenlen)), hostcopy(coins), hostcopy(sampled),
+                                     None if hyps is None else [[list(map(int, h)) for h in hs] for hs in hyps]))
+            if not evaluate:
+                st.zero_grad()
             n_local = (y[:, :dec_steps] != 0).sum().to(torch.float32)
             n_total = self.dp.all_reduce_scalar(n_local) if self.dp is not None else n_local
             loss_scale = self._loss_scale(n_total)
@@ -850,8 +871,15 @@ class LAS:
                 b_total = self.dp.all_reduce_scalar(b_local) if self.dp is not None else b_local
                 ctc_scale = (float(self.args.ctc_weight) / b_total.reshape(-1)).reshape(1).to(torch.float32)
             # the Speller's host-side preparation: token schedule, encoder lengths, masks
-            prep = self.speller.prepare(audio.shape[0], self.listener.output_length(audiolen, enc_type), dec_steps, dev, y,
-                                        True, coins, sampled)
+            if getattr(self.args, "mwer", False):
+                # --mwer: every utterance is S = K + 1 Speller rows (its hypotheses, then the reference) over mw.U steps
+                mw = MW.plan_rows(self, y, tokenlen, dec_steps, mwer_strings, dev)
+                prep = MW.prepare_speller(mw, self.speller, self.listener.output_length(audiolen, enc_type), dev)
+                mwer_scale = torch.full((1,), 1.0 / audio.shape[0], device=dev)
+                ce_scale = (float(self.args.mwer_ce_weight) * loss_scale).to(torch.float32)
+            else:
+                prep = self.speller.prepare(audio.shape[0], self.listener.output_length(audiolen, enc_type), dec_steps, dev, y,
+                                            True, coins, sampled)
         if getattr(self.args, "spec_augment", False):
             # SpecAugment on the launch stream in front of the Listener.  The plan is drawn from (seed, global step) alone and `_recent`
             # holds the RAW batch, so a re-run of this step warps and masks as this run does.  Data parallel: rank r holds rows
@@ -867,12 +895,30 @@ class LAS:
             h, enc_state, enc_len = self.listener(audio, audiolen, enc_type)              # is_training default True
         _hip.join_chain_stream()
         with _hip.roctx_range("speller fwd"):
-            logits, ctc_logits, alphas = self.speller(h, enc_len, dec_steps, y, coins=coins, sampled=sampled, prepared=prep)
+            if mw is not None:
+                try:
+                    # the encoder output once per row (the gradient's sum over an utterance's rows is the repeat's backward)
+                    logits, ctc_logits, alphas = self.speller(h.repeat_interleave(mw.S, 0), None, mw.U, prepared=prep)
+                except RuntimeError as e:
+                    # only the library's own refusal of the arguments (a negative return code, before anything is launched): a HIP
+                    # error, a time-out status or a failed allocation stays what it is
+                    if "las_speller_fwd failed (rc=-" not in str(e):
+                        raise
+                    raise ValueError("--mwer: the Speller refuses the step's geometry (%d rows = %d utterances x (%d hypotheses + the "
+                                     "reference), %d encoder frames, %d steps): %s" % (mw.n * mw.S, mw.n, mw.K, h.shape[1], mw.U, e)) from e
+            else:
+                logits, ctc_logits, alphas = self.speller(h, enc_len, dec_steps, y, coins=coins, sampled=sampled, prepared=prep)
 
         with _hip.roctx_range("loss"):
             # the loss is the root of the graph: its gradient w.r.t. the logits (scale included) comes out of the same kernel pair and is
             # handed to the Speller's node directly -- no ones_like fill, no [B, U, V] multiply by 1.0, no scalar multiply on the chain
-            loss, dlogits, _ = _ce_loss(logits.detach(), y_u, logits.shape[2], self.args.label_smoothing, loss_scale)   # sum_local / n_total
+            if mw is not None:
+                res = self._mwer_loss(mw, logits.detach(), loss_scale, mwer_scale, ce_scale, evaluate)
+                if evaluate:
+                    return res
+                loss, dlogits = res["total"], res["dlogits"]
+            else:
+                loss, dlogits, _ = _ce_loss(logits.detach(), y_u, logits.shape[2], self.args.label_smoothing, loss_scale)   # sum_local / n_total
             if ctc:
                 # the CTC term (las/las.py:259-261, 335-349): value and gradient in one call, on the launch stream behind the head
                 att_loss = loss
@@ -946,8 +992,45 @@ class LAS:
         if ctc:
             summaries["att_loss"] = att_loss.detach()
             summaries["ctc_loss"] = ctc_nll.sum() / b_total.reshape(-1)[0]            # mean_b nll_b over the global batch (this rank's share)
+        if mw is not None:
+            summaries["mwer_risk"] = res["loss"][0]             # mean over the utterances of their expected word errors (scale = 1 / n)
+            summaries["mwer_ce"] = res["ce"]                    # the reference's cross entropy per token, unweighted
+            logits, alphas = logits[mw.K::mw.S], alphas[mw.K::mw.S]          # what the step returns: the teacher-forced reference rows
         self.last = {"logits": logits, "y": y}
         return loss_val, None, st.global_step, logits.detach(), alphas.detach(), summaries, sample_rate
+
+    def _mwer_loss(self, mw, logits, loss_scale, mwer_scale, ce_scale, evaluate):
+        """The --mwer loss behind the Speller, in this order: the expected word errors over all n S rows (las_mwer_loss with
+        K := S and nhyp <= S - 1: the reference's slot is absent, its gradient rows zeros), then the reference rows' cross entropy into
+        those zeros (las_ce_loss through base + K rows and a row stride of S rows).  -> las.mwer.loss_rows' dict with total = mwer +
+        mwer_ce_weight * ce, ce (unweighted) and the rows' labels, lengths and error counts."""
+        from las import mwer as MW
+        MW.resolve_samples(mw, self.speller.last_tokens_in)
+        err = MW.row_errors(mw, self.id_to_token, str(self.args.unit).lower())
+        res = MW.loss_rows(logits, mw.y, mw.lens, mw.nhyp, err, mw.S, mw.mode, mwer_scale, grad=not evaluate)
+        ref_rows = logits[mw.K::mw.S]
+        dref = res["dlogits"][mw.K::mw.S] if not evaluate else False
+        ce_scaled, _, ce_sums = _ce_loss(ref_rows, mw.y_ref, logits.shape[2], self.args.label_smoothing, ce_scale, out=dref)
+        res.update(total=res["loss"][0] + ce_scaled, ce=ce_sums[0] * loss_scale[0], y=mw.y, lens=mw.lens, err=err, nhyp=mw.nhyp)
+        # what the step leaves to look at: the small tensors; the [n S, U, V] logits and their gradient only for a test that asks
+        self.last_mwer = {k: v for k, v in res.items() if k != "dlogits"}
+        if self.keep_mwer_logits:
+            self.last_mwer.update(logits=logits, dlogits=res["dlogits"])
+        return res
+
+    def mwer_risk(self, xs, ys, hyps=None):
+        """The --mwer step's forward and loss with no gradient and no update (the evaluation hook): -> (loss = mean expected word errors +
+        mwer_ce_weight * ce, risk [n] the expected word errors per utterance, seq_lp float64 [n, K + 1] the hypotheses' log-likelihoods,
+        NaN in absent slots and in the reference's), device tensors.  SpecAugment, dropout and drawn hypotheses follow the global step,
+        as the train step at that count would."""
+        if not getattr(self.args, "mwer", False):
+            raise ValueError("LAS.mwer_risk needs --mwer True")
+        with torch.no_grad():
+            res = self._train_step_impl(xs, ys, hyps=hyps, evaluate=True)
+        _hip.join_side_stream()
+        _hip.check_status(self._device())
+        n = res["risk"].shape[0]
+        return res["total"], res["risk"], res["seq_lp"].view(n, -1)
 
     def _apply_adam(self, st, lr, beta1=0.9, beta2=0.999, eps=1e-8):
         """clip_by_global_norm + Adam (las/las.py:272-283; TF epsilon-hat form)."""
@@ -980,6 +1063,8 @@ class LAS:
         weights) and the loss is the token sum over ALL rows divided by their token count (las/las.py:329-331), so this IS the update
         of k data-parallel ranks that hold one of the batches each (las/parallel.py) -- on one GPU, where the recurrent sweeps are
         latency-bound on a fifth of the compute units and k times the rows cost them (almost) nothing.  Returns what train() does."""
+        if getattr(self.args, "mwer", False):
+            raise ValueError("--mwer: train_stacked is not built for it (an utterance is already K + 1 Speller rows); use train")
         if len(batches) == 1:
             return self.train(batches[0][0], batches[0][1], coins=coins, sampled=sampled)
         dev = self._device()

@@ -97,9 +97,11 @@ def main():
     loss_ = []
 
     def report(info, value):                                       # runs when the step's loss has reached the host (lagged)
-        gs, tfrate = info
+        gs, tfrate, risk = info
         loss_.append(value)
-        if rank == 0:
+        if rank == 0 and risk is not None:                         # --mwer: the mean expected word errors of the step's hypotheses
+            logging.info("Step: {}, Loss: {:.3f}, tf rate: {:.3f}, Risk: {:.3f}".format(gs, value, tfrate, float(risk[0])))
+        elif rank == 0:
             logging.info("Step: {}, Loss: {:.3f}, tf rate: {:.3f}".format(gs, value, tfrate))
 
     log = LaggedLog(report)
@@ -107,9 +109,13 @@ def main():
     t_loop, n_utt = time.perf_counter(), 0
     for step in range(training_steps):
         xs, ys = next(batches)
-        batch_loss, _, gs, logits, alphas, _, tfrate = las.train(xs, ys)
+        batch_loss, _, gs, logits, alphas, summ, tfrate = las.train(xs, ys)
         n_utt += int(xs[0].shape[0])
-        log.push((gs, tfrate), batch_loss)
+        risk = None
+        if args.mwer:                                              # (copied in front of the loss: there when the loss' event has passed)
+            risk = torch.empty(1, dtype=torch.float32).pin_memory()
+            risk.copy_(summ["mwer_risk"].detach().reshape(1), non_blocking=True)
+        log.push((gs, tfrate, risk), batch_loss)
         if rank == 0 and args.verbose > 0:                         # (the text summaries synchronise: debugging aid, as in the reference)
             logging.info("HYP: {}".format(convert_idx_to_string(torch.argmax(logits[0], -1).cpu().numpy(), id_to_token, args.unit)))
             logging.info("REF: {}\n".format(convert_idx_to_string(ys[0][0].cpu().numpy(), id_to_token, args.unit)))

@@ -744,6 +744,40 @@ int las_rescore_rank(const float* first, const double* att, const int* nhyp, int
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K10j minimum word error rate training: the expected number of word errors over the hypotheses of every utterance, from the
+ * Speller's logits of those hypotheses, and its gradient with respect to the logits (Prabhavalkar et al. 2018).
+ *
+ * las_mwer_loss: n utterances of K <= 64 slots; row r = u*K + k is slot k of utterance u.  logits fp32, element (r, t, v) at
+ *   logits[r*sb + t*st + v] (strides in elements, last axis contiguous, as las_ce_loss / las_rescore_score: the Speller's time-major
+ *   buffer is consumed in place); dlogits has the same strides.  y int32 [n K, ldy >= U]: the token scored at each step; len int32 [n K]
+ *   clamped to [0, U]: steps t >= len[r] are never read; nhyp int32 [n] clamped to [0, K]: slots k >= nhyp[u] are absent, nothing of them
+ *   (logits, y, len, err) is read and their seq_lp / post / coef are not written; err fp32 [n K]: the row's word error count, the
+ *   caller's; scale_ptr: one fp32 on the device.  mode 0: N-best renormalisation; 1: sampling estimate.
+ *     term(r, t) = z[y] - lse,  lse = m + logf(s),  m = the row maximum,  s = sum_v expf(z[v] - m), all fp32; m = -inf, or y outside
+ *       [0, V): term = -inf (never NaN; nothing is read for such a label).  Order of s (part of the contract; tests/mwer_ref.py's float32
+ *       mode repeats it): 64 lanes, lane i adds classes i, i + 64, ... in ascending order from 0.f, then a xor butterfly (32, 16, 8, 4, 2, 1).
+ *     seq_lp[r] fp64 = the sum of the row's fp32 terms in step order from 0.0 (as las_rescore_score's att); 0 for len = 0.
+ *   Everything per utterance is fp64, sums in slot order from 0.0 over the live slots, rounded to fp32 once where it is stored:
+ *     mode 0: post = exp(seq_lp - max) / sum of those (all 0 if every live seq_lp is -inf);  risk[u] = sum_j post_j err_j;
+ *             coef[r] = scale * post[r] * sum_j post_j (err[r] - err_j)   ( = scale post (err - risk), and exactly 0 when the errors are equal);
+ *     mode 1: post = 1 / nhyp;  risk[u] = (sum_j err_j) / nhyp;  coef[r] = scale * (err[r] - risk[u]) / nhyp.
+ *     risk[u] = 0 for nhyp[u] = 0.  loss[0] = (float)(scale * sum_u risk[u]): lane i of 64 adds utterances i, i + 64, ... in order, then
+ *     the 64 partial sums in lane order.
+ *   dlogits[r, t, v] = coef[r] * (onehot(y_t)[v] - expf(z[v] - lse)) in fp32 for t < len[r].  It is exactly 0.f -- stored without a look
+ *   at the logits, so that no -inf / NaN of theirs leaks in -- for every v at t >= len[r], in every row of an absent slot, in every row
+ *   whose fp32 coef or fp32 post is 0, and at a step without mass (lse = -inf).  Every element of [n K, U, V] is written; nothing else is.
+ *   dlogits = NULL: no gradient.  seq_lp / post / coef / risk may each be NULL.
+ * Refused before anything is launched (< 0 with a las_last_error text): a null pointer among the others, n or V < 1, K outside [1, 64], U
+ * outside [1, 1024], n K U > 2^31 - 1, ldy < U, a negative stride, another mode, ws missing, not 8-byte aligned or shorter than
+ * las_mwer_workspace_bytes(n, K, U).  Three launches on `stream` (one wave per (row, step); one workgroup per utterance; one wave per
+ * (row, step)): the logits are read twice and written once.  No atomics: two runs give the same bits.
+ */
+size_t las_mwer_workspace_bytes(int n, int K, int U);
+int las_mwer_loss(const float* logits, long long sb, long long st, int V, const int* y, int ldy, const int* len, const int* nhyp,
+                  const float* err, int n, int K, int U, int mode, const float* scale_ptr, double* seq_lp, float* post, float* coef,
+                  float* risk, float* loss, float* dlogits, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K10d CTC Viterbi (forced) alignment of a token sequence to the encoder frames: token and word times.  The max-plus form
  * of las_ctc_loss's extended-label recursion (states 0 .. 2L: blank, label 0, blank, ..., label L-1, blank) with a back-trace.
  *   lp           las_ctc_log_softmax's output, fp32 [n, Vc, Tp] class-major, blank = class Vc - 1
