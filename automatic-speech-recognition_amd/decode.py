@@ -2,7 +2,9 @@
 sorted by token length, one BeamSearch.decode per utterance, per-utterance and corpus WER, same log lines).
 --mbr True scores the minimum-Bayes-risk hypothesis of every N-best list (las.nbest; posteriors at --nbest_scale) instead of the
 top-scoring one: the effect on the corpus WER is read from the same log lines.  --cn_decode True scores the consensus of every list's
-confusion network (las_nbest_network) in the same way; the two cannot be combined."""
+confusion network (las_nbest_network) in the same way; the two cannot be combined.  With --coverage_weight /
+--overattend_weight / --coverage_report (las.coverage) a last line logs the scored hypotheses' mean shares of covered and
+over-attended encoder frames."""
 import logging
 import os
 import sys
@@ -56,6 +58,7 @@ def main():
         tokenlen = np.asarray([r[1][1] for r in recs])
     order = np.argsort(tokenlen)                                   # decode.py:122-124
     error, N, count = 0, 0, 0
+    cov_sum, cov_n = np.zeros(2), 0                                # --coverage_*: the chosen hypotheses' covered / over-attended shares
     logging.info("Decoding...")
     limit = args.max_steps if args.max_steps >= 0 else (8 if args.synthetic else len(order))
     todo = parallel.shard(list(order[:limit]), rank, world)
@@ -90,6 +93,10 @@ def main():
                 hyp = a["consensus"]["text"]
             else:
                 hyp = convert_idx_to_string(state.token_ids[1:], id_to_token, args.unit)
+                if getattr(state, "coverage", None) is not None:
+                    covered, over, frames = state.coverage
+                    cov_sum += np.array([covered, over]) / max(frames, 1)
+                    cov_n += 1
             ref = convert_idx_to_string(dev_tokens[i], id_to_token, args.unit)
             dist, n = edit_distance(ref.split(" "), hyp.split(" "))
             error += dist
@@ -100,6 +107,9 @@ def main():
                 logging.info("REF | {}".format(ref))
                 logging.info("HYP | {}\n".format(hyp))
     error, N = parallel.reduce_error_counts(dp, error, N, dev)
+    if cov_n:                                                      # (this rank's share of the utterances)
+        logging.info("Coverage: {:.4f} of the encoder frames attended, {:.4f} over-attended ({} utterances)".format(
+            cov_sum[0] / cov_n, cov_sum[1] / cov_n, cov_n))
     if rank == 0:
         logging.info("Dev WER: {}".format(error / N))
 

@@ -182,6 +182,9 @@ _SIGS = {
     "las_ngram_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_int, c_void_p]),
+    "las_coverage_step": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p,
+                                  c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "las_coverage_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p]),
     "las_ctc_frame_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "las_ctc_greedy": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "las_ctc_beam_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
@@ -266,7 +269,7 @@ _SIGS = {
 }
 
 
-ABI_VERSION = 607      # include/las_hip.h LAS_HIP_ABI_VERSION
+ABI_VERSION = 608      # include/las_hip.h LAS_HIP_ABI_VERSION
 
 
 def declared_symbols():

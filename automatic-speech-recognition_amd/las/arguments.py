@@ -99,6 +99,16 @@ _EXTRA = [
     (("--ngram_lm",), str, "", "N-gram LM shallow fusion (las.ngram): a back-off model over the model's own tokens in the ARPA text format "
                                "(train_ngram.py writes one); needs --ngram_weight > 0."),
     (("--ngram_weight",), float, 0.0, "Weight of the n-gram LM's natural-log probabilities in the beam search (0: off)."),
+    # attention coverage in the beam search (las.coverage, csrc/coverage.hip): all off by default
+    (("--coverage_weight",), float, 0.0, "Added to a hypothesis' score for every encoder frame whose accumulated attention rises above "
+                                         "--coverage_threshold (against skipped audio; 0: off)."),
+    (("--coverage_threshold",), float, 0.5, "A frame is covered once its accumulated attention exceeds this (Chorowski & Jaitly's 0.5)."),
+    (("--overattend_weight",), float, 0.0, "Taken from a hypothesis' score for every encoder frame whose accumulated attention rises "
+                                           "above --overattend_threshold (against loops; 0: off)."),
+    (("--overattend_threshold",), float, 1.5, "A frame is over-attended once its accumulated attention exceeds this (a guess: no WER "
+                                              "has been measured for any of these values)."),
+    (("--coverage_report",), str2bool, False, "Count covered and over-attended frames whatever the weights; transcribe.py prints JSON lines "
+                                              "with \"coverage\" and \"overattended\", the shares of the utterance's encoder frames."),
     # CTC-only decoding (las.ctc_search, csrc/ctc_search.hip): the default is the Speller's search
     (("--decoder",), str, "attention", "Search of transcribe.py / decode.py: attention = the Speller's beam search; ctc = the CTC head alone "
                                        "(needs --ctc True): --beam_size 1 is the greedy collapse, > 1 the prefix beam search, with "

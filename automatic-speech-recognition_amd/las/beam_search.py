@@ -35,6 +35,8 @@ class BeamState(object):
         #                                        (las.bias) it includes the hypothesis' biasing bonus, with an n-gram LM
         #                                        (las.ngram) the weighted log-probability of every token
         self.att = att
+        self.coverage = None                   # (covered, over, frames) when the coverage scorer ran, and then log_prob
+        #                                        includes the hypothesis' coverage gains
         self.dec_state = dec_state
         self.lm_state = lm_state
 
@@ -137,6 +139,10 @@ class BeamSearch(object):
         if (getattr(args, "ngram_lm", "") or "") or float(getattr(args, "ngram_weight", 0.0) or 0.0) != 0.0:
             from las import ngram
             self.set_ngram(ngram.from_args(args), float(args.ngram_weight))
+        # attention coverage: --coverage_weight / --overattend_weight / --coverage_threshold / --overattend_threshold /
+        # --coverage_report; weights 0 and no report = off, and then none of its code runs.  Bad values are refused here
+        from las import coverage
+        self.coverage = coverage.from_args(args)
         # decode_batch / decode_batches keep what align() needs of every batch in its results' `align_inputs` (off: nothing is retained --
         # the CTC log-probabilities are 410 MB at 64 utterances and V = 5000)
         self.retain_align = False
@@ -177,6 +183,11 @@ class BeamSearch(object):
         if lm is not None and w > 0:
             lm.tables(w)                    # (a weight that takes a table value out of float32 is refused here)
         self.ngram, self.ngram_weight = lm, (w if lm is not None else 0.0)
+
+    def set_coverage(self, w_c=0.0, w_o=0.0, tau=0.5, kappa=1.5, report=False):
+        """the coverage setting of the searches that follow: swapped between batches.  Weights 0 without a report: off"""
+        from las import coverage
+        self.coverage = coverage.make(w_c, w_o, tau, kappa, report)
 
     # -- model calls (the reference's sess.run wrappers, las/beam_search.py:203-246) -------------------
     def _get_encode(self, sess, audio, audiolen):
@@ -508,7 +519,9 @@ class BeamSearch(object):
         speller = S.SpellerStep(self, g, loop, rows, enc_u, keys_u, enc_lens, lm, ng, ctx, lam)
         if lm is not None:
             lm.attach(rows, speller)
-        scorers, ranked = S.make_scorers(g, loop, rows, speller.logits, self.end_id, ctc_lp, enc_lens, lam, ctx, ng, self.ngram_weight)
+        scorers, ranked = S.make_scorers(g, loop, rows, speller.logits, self.end_id, ctc_lp, enc_lens, lam, ctx, ng, self.ngram_weight,
+                                         self.coverage, speller.enc_len)
+        cover = scorers[0] if self.coverage is not None else None
         loop.ba.logits = ranked.data_ptr()
         rows.write(loop.ba)
         mark("encoded")
@@ -535,9 +548,9 @@ class BeamSearch(object):
             def finish():
                 self._tail_stream.wait_event(ev)
                 with torch.cuda.stream(self._tail_stream):
-                    return self._decode_tail(loop, Tps, mark, kept)
+                    return self._decode_tail(loop, Tps, mark, kept, cover)
             return finish
-        results = self._decode_tail(loop, Tps, mark, kept)
+        results = self._decode_tail(loop, Tps, mark, kept, cover)
         mark("done")
         if tm:
             live_steps, parts_us = self._time_parts(parts, loop)
@@ -634,7 +647,7 @@ class BeamSearch(object):
                 done.copy_(saved[0]); nlive.copy_(saved[1]); step.zero_()
         return live_steps, parts_us
 
-    def _decode_tail(self, loop, Tps, mark, kept=None):
+    def _decode_tail(self, loop, Tps, mark, kept=None, cover=None):
         """What follows a search (decode_batch; on the current stream): the back pointers are walked on the device (las_beam_backtrack), one
         read-back, then the reference's host-side objects (las/beam_search.py:136-158, :297-312)."""
         ba, selcap, alphas_hist, lib, dev, n, Umax = loop.ba, loop.selcap, loop.alphas_hist, _hip.lib(), loop.g.dev, loop.g.n, loop.g.Umax
@@ -653,6 +666,12 @@ class BeamSearch(object):
         t_idx = torch.cat([torch.full((1,), Umax, device=dev, dtype=torch.int64), pos[:-1]]).expand(W, -1)[item]
         r_idx = torch.cat([torch.zeros(W, 1, **i32), w_rows], 1)[item].long()
         g_att = alphas_hist[t_idx, r_idx]
+        cov_h = frames = None
+        if cover is not None:
+            # a hypothesis' counts: the coverage scorer's record of its LAST step, at the row it occupied there
+            last = (w_len - 1).clamp(min=0).long()
+            cov_h = cover.hist[last, w_rows.gather(1, last.unsqueeze(1))[:, 0].long()].cpu().numpy().astype(np.int64)
+            frames = cover.enc_len_rows[::loop.g.beam].clamp(0, loop.g.Tp).cpu().tolist()
         lens, ids_h, sc_h = w_len.cpu().numpy(), w_ids.cpu().numpy(), w_score.cpu().numpy()
         _hip.check_status(dev)
         mark("read back")
@@ -674,6 +693,8 @@ class BeamSearch(object):
                 w, ln_ = int(ws[i]), int(lens[ws[i]])
                 results[u].append(BeamState((self.start_id, ids_h[w, :ln_]), np.float32(sc_h[w]),
                                             _AttRows(g_att, int(of[i]), ln_ + 1, Tps[u]), None, None))
+                if cov_h is not None:
+                    results[u][-1].coverage = (int(cov_h[w, 0]), int(cov_h[w, 1]), int(frames[u]))
         return results
 
     def restore_las(self, sess, save_path, restore_epoch):

@@ -15,7 +15,7 @@ Geometry = collections.namedtuple("Geometry", "dev n beam N Tp Hd Umax V A NL D 
 
 class StateRows(object):
     """The tensors whose rows follow their hypotheses through the gather of las_beam_loop_step.  Slot order of a search: per decoder layer h
-    (then c for an LSTM), the alignment, the LM's state, CTC, hotwords, n-gram."""
+    (then c for an LSTM), the alignment, the LM's state, CTC, hotwords, n-gram, coverage."""
 
     def __init__(self):
         self.pairs = []
@@ -100,7 +100,8 @@ class SpellerStep(object):
         fa.row_group = beam if search.xcd_local_rows else 0
         self.logits = bufs["logits"][0]                                                 # [N, V]
         self.register(rows, bufs, NL, g.lstm, loop)
-        # (no short form with a scorer: they are placed between the materialised logits and the pruning launch)
+        # (no short form with a scorer that adds to the logits: they are placed between the materialised logits and the pruning launch; the
+    #  coverage scorer adds to the rows' running sums instead and is not considered here)
         self.fused = (ng is None and ctx is None and lam == 0 and g.prec == _hip.PREC_BF16 and g.lstm and NL == 1 and search.fuse_projection and
                       D % 32 == 0 and (E_ + Hd + D) % 32 == 0 and ((beam + 15) // 16) * ((V_ + 15) // 16) <= 8 and
                       (lm is None or (lm.lm.hidden_size % 32 == 0 and "packs" in lm.plan)))
@@ -220,8 +221,8 @@ class LmFusion(object):
 class Scorer(object):
     """A per-step scorer: ONE launch that reads the device step counter, advances every live row's state from its gathered parent `par`
     into `cur` and adds its term to the scores the pruning ranks; `cur` follows its hypotheses through the gather like the recurrent
-    state.  Launch order n-gram -> CTC -> hotwords: the n-gram adds to the logits in front of the CTC bank cut, the hotwords to what the
-    pruning ranks.  A subclass names the C entry point and gives the arguments in front of (par, cur, width, the loop words)."""
+    state.  Launch order coverage -> n-gram -> CTC -> hotwords: the n-gram adds to the logits in front of the CTC bank cut, the hotwords to
+    what the pruning ranks, the coverage scorer to the rows' running sums.  A subclass names the C entry point and gives the arguments in front of (par, cur, width, the loop words)."""
     name = entry = None
 
     def __init__(self, g, loop, rows, width, *head):
@@ -270,11 +271,28 @@ class NgramScorer(Scorer):
                         _hip.p(logits), g.n, g.beam, g.V)
 
 
-def make_scorers(g, loop, rows, logits, end_id, ctc_lp=None, enc_lens=None, lam=0.0, ctx=None, ng=None, ng_weight=0.0):
-    """The active scorers of a search, registered in slot order (CTC, hotwords, n-gram) -> (the scorers in LAUNCH order, the scores the
-    pruning ranks: the CTC scorer's `joint` when it is on, else the logits)."""
+class CoverageScorer(Scorer):
+    """Attention coverage: las_coverage_step adds the step's alignments (LoopState.alphas_cur) to every live row's
+    accumulated attention, counts the frames above the two thresholds and adds the gain to the row's running sum (LoopState.score) --
+    a per-row constant, so no [rows, V] tensor is needed and SpellerStep's short form stays on.  `hist` [Umax, N, 2] keeps every
+    step's counts: a finished hypothesis reads its own at its last step and row (BeamSearch._decode_tail)."""
+    name, entry = "coverage", "las_coverage_step"
+
+    def __init__(self, g, loop, rows, enc_len_rows, setting):
+        self.setting, self.enc_len_rows = setting, enc_len_rows
+        self.hist = torch.zeros(g.Umax, g.N, 2, device=g.dev)
+        Scorer.__init__(self, g, loop, rows, 4 * ((g.Tp + 2 + 3) // 4), _hip.p(loop.alphas_cur), _hip.p(enc_len_rows), g.n, g.beam, g.Tp,
+                        _hip.p(loop.score), setting.w_c, setting.w_o, setting.tau, setting.kappa, _hip.p(self.hist))
+
+
+def make_scorers(g, loop, rows, logits, end_id, ctc_lp=None, enc_lens=None, lam=0.0, ctx=None, ng=None, ng_weight=0.0, coverage=None,
+                 enc_len_rows=None):
+    """The active scorers of a search, registered in slot order (CTC, hotwords, n-gram, coverage) -> (the scorers in LAUNCH order, the
+    scores the pruning ranks: the CTC scorer's `joint` when it is on, else the logits).  The coverage scorer (a las.coverage.Setting;
+    enc_len_rows: T'_u per row, int32 on the device) launches first: it needs the Speller's alignments only."""
     ctc = CtcScorer(g, loop, rows, ctc_lp, enc_lens, logits, lam, end_id) if lam > 0 else None
     ranked = ctc.joint if ctc is not None else logits
     bias = BiasScorer(g, loop, rows, ctx, ranked) if ctx is not None else None
     ngram = NgramScorer(g, loop, rows, ng, ng_weight, logits) if ng is not None else None
-    return [s for s in (ngram, ctc, bias) if s is not None], ranked
+    cover = CoverageScorer(g, loop, rows, enc_len_rows, coverage) if coverage is not None else None
+    return [s for s in (cover, ngram, ctc, bias) if s is not None], ranked

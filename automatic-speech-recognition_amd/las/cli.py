@@ -57,7 +57,10 @@ def check_flags(args, parser):
         if np.isnan(args.keyword_threshold):
             raise ValueError("--keyword_threshold is not a number")
     refuse(align[:1], "%s %s: use one of them")
+    from las import coverage
+    cover = coverage.from_args(args)                                   # (bad weights and thresholds are refused here)
     if kind != "search":
+        coverage.refuse_without_attention(args, "--keywords" if kind == "keywords" else "--align_text")
         args.timestamps = args.timestamps or kind == "align"
         args.hotwords, args.hotword_weight = "", 0.0                  # (no search: nothing to bias)
         args.ngram_lm, args.ngram_weight = "", 0.0                    # (... and nothing to fuse an LM into)
@@ -72,7 +75,8 @@ def check_flags(args, parser):
         parser.error("no audio files (or --synthetic True)")
     if not args.cmvn:
         raise ValueError("the Listener takes the CMVN'd cube [T, feat_dim, 3]: transcribe with --cmvn True")
-    return Mode(kind, ctc_only, consensus, kind != "search" or bool(args.timestamps) or consensus)
+    report = cover is not None and cover.report                        # (--coverage_report prints the counts: JSON lines)
+    return Mode(kind, ctc_only, consensus, kind != "search" or bool(args.timestamps) or consensus or report)
 
 
 def load_lm(init_dir, store=None):

@@ -34,6 +34,9 @@ def check_args(args, force=False):
         raise ValueError("--decoder ctc: --hotwords biases the Speller's search; the CTC search has no hotword boosting")
     if float(getattr(args, "ctc_decode_weight", 0.0) or 0.0) > 0:
         raise ValueError("--decoder ctc: --ctc_decode_weight re-ranks the Speller's search with the head; here the head is the search")
+    if res == "none":                                                  # (coverage counts the attention decoder's alignments)
+        from las import coverage
+        coverage.refuse_without_attention(args, "--decoder ctc without --rescore attention")
     K = int(args.beam_size)
     if not 1 <= K <= MAX_BEAM:
         raise ValueError("--decoder ctc: --beam_size between 1 and %d (got %d)" % (MAX_BEAM, K))

@@ -94,12 +94,14 @@ def _check_rows(rows):
     return rows
 
 
-def teacher_forced_logits(bs, encs, enc_lens, strings, rows=64):
+def teacher_forced_logits(bs, encs, enc_lens, strings, rows=64, with_alphas=False):
     """The second pass' Speller calls: the rows -- strings[u][k], utterance by utterance -- in chunks of at most `rows`; a chunk may hold
     several utterances and may split one.  Yields per chunk (first row, logits [B, U, V] (a view of the time-major buffer), y int32
     [B, U], lens int32 [B]): U = the chunk's longest string, the encoder block of a row its utterance's output zero-padded to the
     chunk's longest (enc_len masks the rest), tokens_in[0] = <SOS>, tokens_in[t] = s[t - 1].  No dropout mask and no variational noise
-    (BeamSearch's decode step passes none either), no in-loop logits, no gradient.  The logits buffer is rows * U * V * 4 bytes."""
+    (BeamSearch's decode step passes none either), no in-loop logits, no gradient.  The logits buffer is rows * U * V * 4 bytes.
+    with_alphas: every chunk is followed by the Speller's time-major alignments [U, B, T'] and the rows' enc_len int32 [B] (what
+    las_coverage_rows reads)."""
     rows = _check_rows(rows)
     if len(encs) != len(strings) or len(enc_lens) != len(strings):
         raise ValueError("rescore: %d encoder outputs, %d lengths, %d hypothesis lists" % (len(encs), len(enc_lens), len(strings)))
@@ -136,21 +138,32 @@ def teacher_forced_logits(bs, encs, enc_lens, strings, rows=64):
                     "emb_mask": None, "emb_noise": None}
         with torch.no_grad():
             try:
-                logits, _, _ = bs.speller(enc, None, U, is_training=False, prepared=prepared)
+                logits, _, alphas = bs.speller(enc, None, U, is_training=False, prepared=prepared)
             except RuntimeError as e:
                 raise ValueError("rescore: the Speller refuses the chunk's geometry (%d rows, %d encoder frames, %d steps): %s" % (B, Tp, U, e))
-        yield c0, logits, d[U * B:2 * U * B].view(B, U), d[2 * U * B:2 * U * B + B]
+        out = (c0, logits, d[U * B:2 * U * B].view(B, U), d[2 * U * B:2 * U * B + B])
+        yield out + (alphas.permute(1, 0, 2), prepared["enc_len_i32"]) if with_alphas else out
 
 
-def _score_device(bs, encs, enc_lens, strings, rows, return_steps):
-    """-> (att float64 [N] on the device, the N rows in utterance order; per row its step terms (a device tensor) or None)"""
+def _score_device(bs, encs, enc_lens, strings, rows, return_steps, cover=None):
+    """-> (att float64 [N] on the device, the N rows in utterance order; per row its step terms (a device tensor) or None); with a
+    coverage setting `cover` a third item: the rows' (covered, over, frames) int32 [N, 3] on the device -- las_coverage_rows on the
+    teacher-forced alignments of the scored string's steps"""
     N = sum(len(s) for s in strings)
     att = torch.empty(N, dtype=torch.float64, device=encs[0].device)
-    steps = []
-    for c0, logits, y, lens in teacher_forced_logits(bs, encs, enc_lens, strings, rows):
+    steps, counts = [], []
+    for chunk in teacher_forced_logits(bs, encs, enc_lens, strings, rows, with_alphas=cover is not None):
+        c0, logits, y, lens = chunk[:4]
         _, st = score_rows(logits, y, lens, return_steps, out=att[c0:c0 + logits.shape[0]])
         if return_steps:
             steps.append(st)
+        if cover is not None:
+            from las import coverage
+            alphas, el = chunk[4], chunk[5]
+            counts.append(torch.cat([coverage.rows_counts(alphas, lens, el, cover.tau, cover.kappa),
+                                     el.clamp(0, alphas.shape[2]).unsqueeze(1)], 1))
+    if cover is not None:
+        return att, (steps if return_steps else None), torch.cat(counts, 0)
     return att, (steps if return_steps else None)
 
 
@@ -202,7 +215,16 @@ def rescored_results(bs, encs, enc_lens, hyps, kept):
     if N == 0:
         return results
     dev = encs[0].device
-    att_flat, _ = _score_device(bs, encs, enc_lens, strings, rows, False)
+    cover = getattr(bs, "coverage", None)                              # (the counts of the teacher-forced alignments)
+    if cover is None:
+        att_flat, _ = _score_device(bs, encs, enc_lens, strings, rows, False)
+        att_raw = cnt = None
+    else:
+        att_raw, _, cnt = _score_device(bs, encs, enc_lens, strings, rows, False, cover)
+        # att + fl32(w_c covered) - fl32(w_o over): the two products are float32 roundings, the sums are float64
+        cf = cnt[:, :2].to(torch.float32)
+        att_flat = att_raw + ((cf[:, 0] * float(np.float32(cover.w_c))).double() - (cf[:, 1] * float(np.float32(cover.w_o))).double())
+        att_raw, cnt = att_raw.cpu().numpy(), cnt.cpu().numpy()
     host = np.zeros(n * K + n + N, np.int32)                           # [first (fp32 bits) | nhyp | the rows' slots u K + k]
     h_first, h_nh, h_pos = host[:n * K].view(np.float32).reshape(n, K), host[n * K:n * K + n], host[n * K + n:]
     i = 0
@@ -219,8 +241,13 @@ def rescored_results(bs, encs, enc_lens, hyps, kept):
     h = out.cpu().numpy()
     _hip.check_status(dev)
     h_att, h_tot, h_ord = h[:2 * n * K].view(np.float64).reshape(n, K), h[2 * n * K:3 * n * K].view(np.float32).reshape(n, K), h[3 * n * K:].reshape(n, K)
+    base = np.concatenate(([0], np.cumsum([len(hs) for hs in hyps])))
     for u, hs in enumerate(hyps):
         for k in reversed(h_ord[u, :len(hs)].tolist()):                # ascending: the best last
             results[u].append(BeamState([bs.start_id] + list(hs[k][0]), np.float32(h_tot[u, k]), [], None, None))
             results.rescored[u].append(dict(first=float(hs[k][1]), att=float(h_att[u, k]), total=float(h_tot[u, k]), first_rank=int(k)))
+            if cnt is not None:                                        # att: with the coverage term; att_score: the decoder's own
+                row = int(base[u]) + k
+                results[u][-1].coverage = tuple(int(x) for x in cnt[row])
+                results.rescored[u][-1].update(att_score=float(att_raw[row]), coverage=results[u][-1].coverage)
     return results

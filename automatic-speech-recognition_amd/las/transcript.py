@@ -16,9 +16,12 @@ def choose(args, bs, ann, results, id_to_token):
     With one: one consensus call for the batch and, with --timestamps, one alignment of the chosen; score = the alignment's, else the search's."""
     if ann is None:
         token_lists = [list(r[-1].token_ids[1:]) if r else [] for r in results]
+        cov = [_coverage_fields(r[-1] if r else None) for r in results]          # (DESIGN 7t: {} unless the coverage scorer ran)
         if not args.timestamps:
+            if getattr(args, "coverage_report", False):                # JSON lines: the search's score and the two shares
+                return [(tokens, float(r[-1].log_prob) if r else None, None, c) for tokens, r, c in zip(token_lists, results, cov)]
             return [(tokens, None, None, None) for tokens in token_lists]
-        return [(tokens, score, span, {}) for tokens, score, span in zip(token_lists, *bs.align_results(results, token_lists))]
+        return [(tokens, score, span, c) for tokens, score, span, c in zip(token_lists, *bs.align_results(results, token_lists), cov)]
     from las import nbest as NB
     notes = ann.annotate(results)
     token_lists = [list(a["state"].token_ids[1:]) if a["state"] is not None else [] for a in notes]
@@ -29,7 +32,7 @@ def choose(args, bs, ann, results, id_to_token):
     out = []
     rescored = getattr(results, "rescored", None)                      # --rescore attention: both passes' scores of every listed hypothesis
     for u, (a, tokens, score, span) in enumerate(zip(notes, token_lists, scores, spans)):
-        extra = {}
+        extra = {} if ann.cn_decode else _coverage_fields(a["state"])  # (the consensus is a text no search produced: no coverage)
         if ann.cn:
             extra["network"] = a.get("network", [])
         if ann.cn_decode:                                              # the consensus: a text no search produced, so it has no score
@@ -44,6 +47,8 @@ def choose(args, bs, ann, results, id_to_token):
         if ann.nbest:
             extra["nbest"] = [{"text": convert_idx_to_string(t, id_to_token, args.unit), "score": sc if np.isfinite(sc) else None,
                                "posterior": p} for t, sc, p in a["nbest"]]
+            for j, e in enumerate(extra["nbest"]):                     # (the list is best first, the results ascend)
+                e.update(_coverage_fields(results[u][len(results[u]) - 1 - j] if j < len(results[u]) else None))
             if rescored is not None:
                 for j, e in enumerate(extra["nbest"]):                 # (the list is best first, the results ascend)
                     d = rescored[u][len(rescored[u]) - 1 - j]
@@ -52,14 +57,26 @@ def choose(args, bs, ann, results, id_to_token):
     return out
 
 
+def _coverage_fields(state):
+    """{"coverage", "overattended"} of a hypothesis the coverage scorer counted, else {}"""
+    cov = getattr(state, "coverage", None)
+    if cov is None:
+        return {}
+    from las import coverage
+    return coverage.fields(cov)
+
+
 def record(args, id_to_token, frame_s, tokens, score, span, extra, duration, segment=None):
-    """the object of one utterance, or of the segment (start s, end s) of a file: [start, end], text, score, [confidence], [words],
-    [nbest], [network].  A segment's word times are shifted into file time and clipped to its end.  extra None: the text alone"""
+    """the object of one utterance, or of the segment (start s, end s) of a file: [start, end], text, score, [coverage, overattended],
+    [confidence], [words], [nbest], [network].  A segment's word times are shifted into file time and clipped to its end.  extra None: the text alone"""
     text = convert_idx_to_string(tokens, id_to_token, args.unit)
     if extra is None:
         return {"text": text}
     d = {} if segment is None else {"start": segment[0], "end": segment[1]}
     d["text"], d["score"] = text, score if score is not None and np.isfinite(score) else None
+    for k in ("coverage", "overattended"):
+        if k in extra:
+            d[k] = extra[k]
     words = A.words(tokens, span, id_to_token, args.unit, frame_s, duration) if span is not None else None
     for w in words if words is not None and segment is not None else []:
         if w["start"] is not None:

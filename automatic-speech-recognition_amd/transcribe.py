@@ -13,6 +13,8 @@
     python transcribe.py --ctc True --decoder ctc --beam_size 16 a.wav ...     (the CTC head alone: prefix beam search, greedy with --beam_size 1)
     python transcribe.py --noise_file cafe.wav --snr_db 10 --rir_file room.wav a.wav ...   (the files as they would sound in that condition)
     python transcribe.py --ctc True --keywords names.txt a.wav ...     (keyword search: where the CTC head hears a listed phrase, no search)
+    python transcribe.py --coverage_report True a.wav ...              (JSON lines with the shares of attended / over-attended encoder frames)
+    python transcribe.py --coverage_weight 0.3 --overattend_weight 0.7 a.wav ...   (attention coverage scored in the beam search)
 
 With --timestamps the best hypothesis is aligned to the encoder frames by the CTC head (las.align, csrc/ctc_align.hip: a Viterbi pass
 over the head's log-probabilities) and every line is {"text", "score", "words": [{"word", "start", "end"}]}: times in seconds, None when
@@ -54,6 +56,14 @@ against the head's frame-wise best path over the same frames (<= 0), confidence 
 score >= --keyword_threshold x tokens (default -1.0 nat per token, not measured on a trained model); --keyword_max_hits (1 to 8) hits
 are kept per file and phrase.  It cannot be combined with --align_text, --segment, --timestamps, --nbest, --confidence, --mbr,
 --confusion_network or --cn_decode.
+
+With --coverage_weight / --overattend_weight (las.coverage, csrc/coverage.hip) the beam search adds --coverage_weight for
+every encoder frame whose accumulated attention rises above --coverage_threshold and takes --overattend_weight for every frame that
+rises above --overattend_threshold; plain text stays plain text, and every JSON record (and listed N-best hypothesis) carries
+"coverage" and "overattended", the two shares of the utterance's -- under --segment the segment's -- encoder frames.
+--coverage_report True counts with whatever weights and switches to JSON lines.  With --rescore attention the term joins the second
+pass' attention score.  --keywords, --align_text and --decoder ctc without --rescore attention run no attention decoder and refuse
+the flags; --cn_decode prints a text no search produced and carries no coverage fields.
 
 The files are read with preprocess.read_audio (.flac needs `soundfile`), `--decode_batch` of them at a time go through the device front
 end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip; a file at another rate than --sample_rate is resampled

@@ -37,7 +37,7 @@ enum { LAS_ACT_NONE = 0, LAS_ACT_TANH = 1 };
 enum { LAS_ATT_ADD = 0, LAS_ATT_LOC = 1 };      /* las/las.py:44-49 */
 enum { LAS_DT_F32 = 0, LAS_DT_BF16 = 1 };       /* element type of a tensor in HBM (see las_gemm_kk) */
 
-#define LAS_HIP_ABI_VERSION 607      /* bumped whenever an argument struct or a signature changes: las_version() of a library
+#define LAS_HIP_ABI_VERSION 608      /* bumped whenever an argument struct or a signature changes: las_version() of a library
                                         built from another header differs, and the Python loader refuses it */
 int         las_version(void);
 const char* las_last_error(void);
@@ -677,6 +677,41 @@ int las_ngram_step(const int* child_off, const int* child_tok, const float* chil
                    const int* bo, const float* uni_lp, const int* uni_next, int nnodes, int nchild, int order, float* scores,
                    int nutt, int beam, int V, const float* state_in, float* state_out, int state_width, const int* token,
                    const int* step, const int* nlive, const int* done, const int* dec_step, int Umax, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K10k  attention coverage of the search's hypotheses (Chorowski & Jaitly 2017): how many of its utterance's encoder frames
+ * a hypothesis has attended to, and how many it has over-attended -- a score term against skipping and looping, and a report.  For
+ * alignments alpha_1 .. alpha_t over T'_u frames:  cum_t[j] = fl32(cum_{t-1}[j] + alpha_t[j]), cum_0 = 0 (one fp32 add per step and
+ * frame, in step order);  covered_t = #{j < T'_u : cum_t[j] > tau};  over_t = #{j < T'_u : cum_t[j] > kappa};  a NaN never counts.
+ *
+ * las_coverage_step: one search step, launched behind the Speller step (las_speller_fwd, which writes alphas) and in front of the
+ * other scorers and las_beam_loop_step; all arguments are fixed across the search (the step is read from *step: hipGraph friendly).
+ * Live rows exactly as for las_bias_step; rows that are not live are not written.  Per live row:
+ *   - state_in[row] is the gathered parent's state (all zeros at step 0 whatever the buffer holds); state_out[row] receives
+ *     cum_t[0, Tp), then covered_t and over_t as fp32 values (exact below 2^24), then zeros up to state_width >= Tp + 2.  The search
+ *     passes 4 ceil((Tp + 2) / 4): rows of whole 16-byte groups, read and written 16 bytes at a time when the buffers are aligned.
+ *   - with dc = covered_t - covered_{t-1} and do = over_t - over_{t-1} (the parent's counts: the fp32 words of its row),
+ *     score[row] = fl32(score[row] + fl32(fl32(w_c dc) - fl32(w_o do))): the gain goes to the PARENT's running sum that
+ *     las_beam_loop_step adds every candidate's logit to -- a per-row constant, so the ranking inside a row, the top-64 cut and the
+ *     CTC bank are unchanged and no [rows, V] tensor is touched.  Nothing is contracted into an fma.  w_c = w_o = 0: the counts are
+ *     kept, score is neither read nor written.
+ *   - hist (may be NULL) fp32 [Umax, nutt * beam, 2]: hist[*step][row] = (covered_t, over_t), the record the host reads a finished
+ *     hypothesis' counts from.
+ * alphas fp32 [nutt * beam, Tp]; enc_len int32 [nutt * beam] = T'_u of the row's utterance, clamped to [0, Tp]; `token` is unused.
+ * Weights finite and >= 0, 0 < tau < kappa finite, state_width >= Tp + 2, state_in != state_out: refused (< 0, las_last_error)
+ * before anything is launched.  Counts by ballot and popcount, the waves' sums added in wave order; no atomics: two runs give the
+ * same bits, and numpy float32 gives them too (tests/coverage_ref.py).
+ *
+ * las_coverage_rows: the same counts for finished alignments alphas fp32 [U, R, Tp] (the layout the teacher-forced las_speller_fwd
+ * writes): row r accumulates its first steps[r] (int32 [R], clamped to [0, U]) alignments in step order with the step kernel's own
+ * accumulate-and-count functions -> counts int32 [R, 2] = (covered, over) against enc_len int32 [R] (clamped to [0, Tp]).
+ */
+int las_coverage_step(const float* alphas, const int* enc_len, int nutt, int beam, int Tp, float* score, float w_c, float w_o,
+                      float tau, float kappa, float* hist, const float* state_in, float* state_out, int state_width,
+                      const int* token, const int* step, const int* nlive, const int* done, const int* dec_step, int Umax,
+                      void* stream);
+int las_coverage_rows(const float* alphas, int U, int R, int Tp, const int* steps, const int* enc_len, float tau, float kappa,
+                      int* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K10h CTC-only decoding: greedy and prefix beam search over the CTC head's logits, without the Speller.  Classes as in
