@@ -51,10 +51,6 @@ struct BeamLds {
     int cnt[4];
     int count;
 };
-__device__ __forceinline__ unsigned f_order(float f) {                         // unsigned order == float order (-0 canonicalised by the caller)
-    const unsigned b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-}
 __device__ __forceinline__ BKey bkey_shfl_xor(const BKey& k, int off) {
     BKey y;
     y.norm = __shfl_xor(k.norm, off, 64); y.i = __shfl_xor(k.i, off, 64); y.l = __shfl_xor(k.l, off, 64); y.v = __shfl_xor(k.v, off, 64);
@@ -141,8 +137,8 @@ __device__ __forceinline__ int beam_rank(const float* lg, const float* sc, const
                 BKey k;
                 if (idx < ncand && beam_make_key(k, lg, sc, ln, idx, V, t, start_id)) {
                     on |= 1u << s;
-                    KA[s] = f_order(k.norm + 0.f);
-                    KB[s] = ((unsigned long long)(unsigned)k.i << 52) | ((unsigned long long)f_order(k.l + 0.f) << 20) | (unsigned)(k.v - k.i * V);
+                    KA[s] = order_key(k.norm + 0.f);
+                    KB[s] = ((unsigned long long)(unsigned)k.i << 52) | ((unsigned long long)order_key(k.l + 0.f) << 20) | (unsigned)(k.v - k.i * V);
                     ci[s] = k.i; cl[s] = k.l; cv[s] = k.v;
                 }
             }

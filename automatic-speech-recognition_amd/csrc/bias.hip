@@ -11,8 +11,7 @@
 //   4. a t that ends a phrase and has no children is the root (already folded into child_next); the bonus is kept.
 //
 // las_bias_step, once per search step, behind the step's logits (and behind las_ctc_prefix_step when that runs) and in front of
-// las_beam_loop_step.  One workgroup of 256 lanes per hypothesis row, the liveness rules of las_ctc_prefix_step (rows that are not live
-// are not written):
+// las_beam_loop_step.  One workgroup of 256 lanes per hypothesis row, live rows only (search_rows.h):
 //   advance   the gathered parent's node (state_in[row][0], a float that holds an integer < 2^24; the root at step 0 or when the value
 //             is not a node) is advanced by the entering token into state_out[row][0]; every lane walks the same two binary searches.
 //   score     scores[row][v] receives exactly ONE fp32 add of its gain for the advanced node s, and none where the gain is 0:
@@ -32,61 +31,35 @@
 // [0, M) is the root (the host refuses to build such tables) -- no input makes the kernel index outside its buffers.
 // No atomics and no reductions: two runs give the same bits, and numpy float32 gives them too (tests/bias_ref.py).
 #include "las_common.h"
+#include "ngram_trie.h"
+#include "search_rows.h"
 #include <math.h>
 
 namespace {
 
-constexpr int BIAS_MAX_V = 16384;
-constexpr int BIAS_MAX_NODES = 1 << 22;
-
-struct BiasDev {
-    const int *child_off, *child_tok, *child_next; const float *gdef, *groot; float beta; int M, E;
-    float* scores; const float* st_in; float* st_out; const int *token, *step, *nlive, *done, *dec_step;
-    int nutt, beam, V, width, Umax;
+struct BiasDev : SearchRows {                                          // (the rows and search_row_live / search_parent_node: search_rows.h;
+    const int *child_off, *child_tok, *child_next; const float *gdef, *groot; float beta; int M, E;        // the walk over
+    float* scores; int V;                                              //  the child lists, trie_range / trie_find: ngram_trie.h)
 };
 
-// the child list of node s as [lo, hi), inside [0, E) whatever the table holds
-__device__ __forceinline__ void bias_range(const BiasDev& a, int s, int& lo, int& hi) {
-    lo = a.child_off[s]; hi = a.child_off[s + 1];
-    lo = lo < 0 ? 0 : (lo > a.E ? a.E : lo);
-    hi = hi < lo ? lo : (hi > a.E ? a.E : hi);
-}
-// position of token v in the sorted list [lo, hi), or -1
-__device__ __forceinline__ int bias_find(const BiasDev& a, int lo, int hi, int v) {
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        const int tk = a.child_tok[mid];
-        if (tk == v) return mid;
-        if (tk < v) lo = mid + 1; else hi = mid;
-    }
-    return -1;
-}
-
 __global__ __launch_bounds__(256) void bias_step_kernel(BiasDev a) {
-    __shared__ unsigned char cls[BIAS_MAX_V];
+    __shared__ unsigned char cls[TRIE_MAX_V];
     const int row = blockIdx.x, tid = threadIdx.x;
-    const int t_step = __hip_atomic_load(a.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t_step >= a.Umax) return;
-    const int u = row / a.beam, j = row - u * a.beam;
-    if (a.done[u] || t_step >= a.dec_step[u]) return;                  // las_beam_loop_step ignores the utterance's rows
-    if (j >= (t_step == 0 ? 1 : a.nlive[u])) return;                   // no live hypothesis in this slot
+    int t_step, u;
+    if (!search_row_live(a, row, t_step, u)) return;
     const int V = a.V, M = a.M;
     int r_lo, r_hi;
-    bias_range(a, 0, r_lo, r_hi);
+    trie_range(a.child_off, a.E, 0, r_lo, r_hi);
 
     // ---- advance (uniform over the workgroup)
-    int p = 0;
-    if (t_step > 0) {
-        const float f = a.st_in[(size_t)row * a.width];
-        if (f >= 0.f && f < (float)M) p = (int)f;                      // (NaN fails both compares)
-    }
+    const int p = search_parent_node(a, row, t_step, M);
     const int c = a.token[row];
     int s = 0;
     if (c >= 0 && c < V) {
         int lo, hi;
-        bias_range(a, p, lo, hi);
-        int k = bias_find(a, lo, hi, c);
-        if (k < 0 && p != 0) k = bias_find(a, r_lo, r_hi, c);
+        trie_range(a.child_off, a.E, p, lo, hi);
+        int k = trie_find(a.child_tok, lo, hi, c);
+        if (k < 0 && p != 0) k = trie_find(a.child_tok, r_lo, r_hi, c);
         if (k >= 0) s = a.child_next[k];
         if (s < 0 || s >= M) s = 0;
     }
@@ -103,7 +76,7 @@ __global__ __launch_bounds__(256) void bias_step_kernel(BiasDev a) {
         return;
     }
     int s_lo, s_hi;
-    bias_range(a, s, s_lo, s_hi);
+    trie_range(a.child_off, a.E, s, s_lo, s_hi);
     const float gd = a.gdef[s], gr = a.groot[s];
     if (gd == 0.f) {                                                    // a phrase end with children: nothing to pay back, no pass over V
         for (int k = s_lo + tid; k < s_hi; k += 256) {
@@ -113,7 +86,7 @@ __global__ __launch_bounds__(256) void bias_step_kernel(BiasDev a) {
         if (gr != 0.f)
             for (int k = r_lo + tid; k < r_hi; k += 256) {
                 const int v = a.child_tok[k];
-                if (v >= 0 && v < V && bias_find(a, s_lo, s_hi, v) < 0) sc[v] = __fadd_rn(sc[v], gr);
+                if (v >= 0 && v < V && trie_find(a.child_tok, s_lo, s_hi, v) < 0) sc[v] = __fadd_rn(sc[v], gr);
             }
         return;
     }
@@ -142,20 +115,16 @@ extern "C" int las_bias_step(const int* child_off, const int* child_tok, const i
                              float beta, int nnodes, int nchild, float* scores, int nutt, int beam, int V, const float* state_in,
                              float* state_out, int state_width, const int* token, const int* step, const int* nlive, const int* done,
                              const int* dec_step, int Umax, void* stream) {
-    LAS_ARG(child_off && gdef && groot && scores && state_in && state_out && token && step && nlive && done && dec_step,
-            "las_bias_step: null pointer");
-    LAS_ARG(nchild >= 0 && (nchild == 0 || (child_tok && child_next)), "las_bias_step: %d children but no child tables", nchild);
-    LAS_ARG(nutt > 0 && beam > 0 && Umax > 0 && (long long)nutt * beam <= 0x7fffffffLL, "las_bias_step: bad dims");
-    LAS_ARG(V > 1 && V <= BIAS_MAX_V, "las_bias_step: 1 < V <= %d (got %d)", BIAS_MAX_V, V);
-    LAS_ARG(nnodes >= 1 && nnodes <= BIAS_MAX_NODES, "las_bias_step: 1 <= nodes <= %d (got %d)", BIAS_MAX_NODES, nnodes);
-    LAS_ARG(beta > 0.f && beta <= 3.0e38f, "las_bias_step: the weight must be positive and finite (got %g)", (double)beta);
-    LAS_ARG(state_width >= 1, "las_bias_step: state_width %d < 1", state_width);
-    LAS_ARG(state_in != state_out, "las_bias_step: state_in and state_out must differ");
     BiasDev a;
-    a.child_off = child_off; a.child_tok = child_tok; a.child_next = child_next; a.gdef = gdef; a.groot = groot; a.beta = beta;
-    a.M = nnodes; a.E = nchild; a.scores = scores; a.st_in = state_in; a.st_out = state_out; a.token = token; a.step = step;
-    a.nlive = nlive; a.done = done; a.dec_step = dec_step;
-    a.nutt = nutt; a.beam = beam; a.V = V; a.width = state_width; a.Umax = Umax;
+    if (search_rows_args(a, "las_bias_step", 1, nutt, beam, state_in, state_out, state_width,
+                         token, step, nlive, done, dec_step, Umax)) return -1;
+    LAS_ARG(child_off && gdef && groot && scores && token, "las_bias_step: null pointer");
+    LAS_ARG(nchild >= 0 && (nchild == 0 || (child_tok && child_next)), "las_bias_step: %d children but no child tables", nchild);
+    LAS_ARG(V > 1 && V <= TRIE_MAX_V, "las_bias_step: 1 < V <= %d (got %d)", TRIE_MAX_V, V);
+    LAS_ARG(nnodes >= 1 && nnodes <= TRIE_MAX_NODES, "las_bias_step: 1 <= nodes <= %d (got %d)", TRIE_MAX_NODES, nnodes);
+    LAS_ARG(beta > 0.f && beta <= 3.0e38f, "las_bias_step: the weight must be positive and finite (got %g)", (double)beta);
+    a.child_off = child_off; a.child_tok = child_tok; a.child_next = child_next; a.M = nnodes; a.E = nchild;
+    a.gdef = gdef; a.groot = groot; a.beta = beta; a.scores = scores; a.V = V;
     hipLaunchKernelGGL(bias_step_kernel, dim3(nutt * beam), dim3(256), 0, (hipStream_t)stream, a);
     LAS_LAUNCHED();
     return 0;

@@ -11,7 +11,7 @@
 // las_coverage_step, once per search step, behind the Speller step (which writes the step's alignments) and in front of
 // las_beam_loop_step: the gain does not depend on the candidate token, so it goes to the PARENT's running sum `score`, which the
 // pruning adds every candidate's logit to -- nothing [rows, V] is touched and the short form of the step stays on.  One workgroup of
-// 256 lanes per hypothesis row, the liveness rules of las_bias_step (rows that are not live are not written).  State row of `width`
+// 256 lanes per hypothesis row, live rows only (search_rows.h).  State row of `width`
 // >= Tp + 2 floats: cum[0, Tp), covered, over (fp32 values, exact below 2^24), zeros up to width.  16-byte loads and stores of the
 // state rows where width % 4 == 0 and the buffers are 16-byte aligned, of the alignments where Tp % 4 == 0 too.  Counts: one ballot
 // and popcount per wave and pass, the four waves' sums added in wave order by one lane through LDS -- integers, no atomics: two runs
@@ -23,6 +23,7 @@
 // Bounds: enc_len is clamped to [0, Tp] and steps to [0, U]; every index is < Tp, < width or < the row count by construction -- no
 // input makes a kernel index outside its buffers.
 #include "las_common.h"
+#include "search_rows.h"
 #include <math.h>
 
 namespace {
@@ -47,28 +48,23 @@ __device__ __forceinline__ void cov_block_sum(int (*red)[2], int& nc, int& no) {
     }
 }
 
-struct CovDev {
-    const float* alphas; const int* enc_len; const float* par; float* cur; float* score; float* hist;
-    const int *step, *nlive, *done, *dec_step;
+struct CovDev : SearchRows {                                           // (the rows and search_row_live: search_rows.h; token is not read)
+    const float* alphas; const int* enc_len; float* score; float* hist;
     float w_c, w_o, tau, kappa;
-    int nutt, beam, Tp, width, Umax, vec_state, vec_alpha;
+    int Tp, vec_state, vec_alpha;
 };
 
 __global__ __launch_bounds__(256) void coverage_step_kernel(CovDev a) {
     __shared__ int red[4][2];
     const int row = blockIdx.x, tid = threadIdx.x;
-    const int t_step = __hip_atomic_load(a.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t_step >= a.Umax) return;
-    const int u = row / a.beam, j = row - u * a.beam;
-    if (a.done[u] || t_step >= a.dec_step[u]) return;                  // las_beam_loop_step ignores the utterance's rows
-    if (j >= (t_step == 0 ? 1 : a.nlive[u])) return;                   // no live hypothesis in this slot
+    int t_step, u;
+    if (!search_row_live(a, row, t_step, u)) return;
     const int Tp = a.Tp, W = a.width;
-    int L = a.enc_len[row];
-    L = L < 0 ? 0 : (L > Tp ? Tp : L);
-    const bool first = t_step == 0;                                    // the parent is all zeros, whatever `par` holds
+    const int L = clampi(a.enc_len[row], 0, Tp);
+    const bool first = t_step == 0;                                    // the parent is all zeros, whatever state_in holds
     const float* al = a.alphas + (size_t)row * Tp;
-    const float* pr = a.par + (size_t)row * W;
-    float* cu = a.cur + (size_t)row * W;
+    const float* pr = a.st_in + (size_t)row * W;
+    float* cu = a.st_out + (size_t)row * W;
     const float tau = a.tau, kappa = a.kappa;
     int nc = 0, no = 0;
 
@@ -120,9 +116,7 @@ struct CovRowsDev { const float* alphas; const int *steps, *enc_len; int* counts
 __global__ __launch_bounds__(256) void coverage_rows_kernel(CovRowsDev a) {
     __shared__ int red[4][2];
     const int row = blockIdx.x, tid = threadIdx.x, Tp = a.Tp;
-    int n = a.steps[row], L = a.enc_len[row];
-    n = n < 0 ? 0 : (n > a.U ? a.U : n);
-    L = L < 0 ? 0 : (L > Tp ? Tp : L);
+    const int n = clampi(a.steps[row], 0, a.U), L = clampi(a.enc_len[row], 0, Tp);
     const size_t stride = (size_t)a.R * Tp;
     const float* al = a.alphas + (size_t)row * Tp;
     int nc = 0, no = 0;
@@ -146,19 +140,16 @@ extern "C" int las_coverage_step(const float* alphas, const int* enc_len, int nu
                                  float tau, float kappa, float* hist, const float* state_in, float* state_out, int state_width,
                                  const int* token, const int* step, const int* nlive, const int* done, const int* dec_step, int Umax,
                                  void* stream) {
-    (void)token;                                                        // (one of the loop words every scorer is handed; not read)
-    LAS_ARG(alphas && enc_len && score && state_in && state_out && step && nlive && done && dec_step, "las_coverage_step: null pointer");
-    LAS_ARG(nutt > 0 && beam > 0 && Tp > 0 && Umax > 0 && (long long)nutt * beam <= 0x7fffffffLL, "las_coverage_step: bad dims");
+    LAS_ARG(Tp > 0 && Tp <= (1 << 24) - 2, "las_coverage_step: bad dims (Tp = %d)", Tp);
+    CovDev a;                                           // (token: one of the loop words every scorer is handed; not read, may be NULL)
+    if (search_rows_args(a, "las_coverage_step", Tp + 2, nutt, beam, state_in, state_out, state_width,
+                         token, step, nlive, done, dec_step, Umax)) return -1;
+    LAS_ARG(alphas && enc_len && score, "las_coverage_step: null pointer");
     LAS_ARG(w_c >= 0.f && w_c <= 3.0e38f && w_o >= 0.f && w_o <= 3.0e38f,
             "las_coverage_step: the weights must be finite and >= 0 (got %g, %g)", (double)w_c, (double)w_o);
     LAS_ARG(cov_thresholds_ok(tau, kappa), "las_coverage_step: thresholds 0 < tau < kappa, finite (got %g, %g)", (double)tau, (double)kappa);
-    LAS_ARG(state_width >= Tp + 2 && Tp <= (1 << 24) - 2, "las_coverage_step: state_width %d < Tp + 2 = %d", state_width, Tp + 2);
-    LAS_ARG(state_in != state_out, "las_coverage_step: state_in and state_out must differ");
-    CovDev a;
-    a.alphas = alphas; a.enc_len = enc_len; a.par = state_in; a.cur = state_out; a.score = score; a.hist = hist;
-    a.step = step; a.nlive = nlive; a.done = done; a.dec_step = dec_step;
-    a.w_c = w_c; a.w_o = w_o; a.tau = tau; a.kappa = kappa;
-    a.nutt = nutt; a.beam = beam; a.Tp = Tp; a.width = state_width; a.Umax = Umax;
+    a.alphas = alphas; a.enc_len = enc_len; a.score = score; a.hist = hist;
+    a.w_c = w_c; a.w_o = w_o; a.tau = tau; a.kappa = kappa; a.Tp = Tp;
     a.vec_state = (state_width % 4 == 0 && (((size_t)state_in | (size_t)state_out) & 15) == 0) ? 1 : 0;
     a.vec_alpha = (Tp % 4 == 0 && ((size_t)alphas & 15) == 0) ? 1 : 0;
     hipLaunchKernelGGL(coverage_step_kernel, dim3(nutt * beam), dim3(256), 0, (hipStream_t)stream, a);

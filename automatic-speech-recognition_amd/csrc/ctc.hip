@@ -47,8 +47,6 @@ struct CtcWs {
     float* gam;      // [B, T', U+1]  posteriors: column 0 blank, column j+1 the class of label j (first occurrences only)
 };
 
-__host__ __device__ inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 __host__ __device__ inline size_t ctc_ws_layout(int B, int Tp, int U, char* base, CtcWs* w) {
     size_t o = 0;
     auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += align256(bytes); return p; };

@@ -41,26 +41,16 @@ struct AlignWs {
 
 __host__ __device__ inline int ca_sp(int U) { return (2 * U + 1 + 63) / 64 * 64; }
 __host__ __device__ inline int ca_rows(int Tp) { return (Tp + 15) / 16; }
-__host__ __device__ inline size_t ca_align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 __host__ __device__ inline size_t align_ws_layout(int n, int Tp, int U, char* base, AlignWs* w) {
     size_t o = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += ca_align256(bytes); return p; };
+    auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += align256(bytes); return p; };
     char* glp = take((size_t)n * Tp * (U + 1) * 4);
     char* bp = take((size_t)n * ca_rows(Tp) * ca_sp(U) * 4);
     char* fs = take((size_t)n * Tp * 4);
     char* fin = take((size_t)n * 4);
     if (w) { w->glp = (float*)glp; w->bp = (unsigned*)bp; w->fs = (int*)fs; w->fin = (int*)fin; }
     return o;
-}
-
-__device__ __forceinline__ int ca_frames(const int* enc_len, int u, int Tp) {
-    const int T = enc_len[u];
-    return T < 1 ? 1 : (T > Tp ? Tp : T);
-}
-__device__ __forceinline__ int ca_labels(const int* y_len, int u, int U) {       // labels whose outputs are written
-    const int L = y_len[u];
-    return L < 0 ? 0 : (L > U ? U : L);
 }
 
 // grid (ceil(T'/64), ceil((U+1)/64), n), 256 threads
@@ -70,7 +60,7 @@ __global__ __launch_bounds__(256) void ctc_align_gather_kernel(const float* __re
     __shared__ float tile[CA_TILE][CA_TILE + 1];
     const int u = blockIdx.z, t0 = blockIdx.x * CA_TILE, j0 = blockIdx.y * CA_TILE;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int T = ca_frames(enc_len, u, Tp), L = ca_labels(y_len, u, U);
+    const int T = clampi(enc_len[u], 1, Tp), L = clampi(y_len[u], 0, U);
     if (t0 >= T || j0 > L) return;
     const float* row = lp + (size_t)u * Vc * Tp;
     for (int k = wv * 16; k < wv * 16 + 16; ++k) {
@@ -94,9 +84,9 @@ __global__ __launch_bounds__(1024) void ctc_align_viterbi_kernel(int Vc, int Tp,
                                                                  AlignWs w) {
     __shared__ double buf[2][CA_MAX_STATES + 1];
     const int u = blockIdx.x, s = threadIdx.x, SP = blockDim.x;
-    const int T = ca_frames(enc_len, u, Tp);
+    const int T = clampi(enc_len[u], 1, Tp);
     const int Lraw = y_len[u];
-    const int L = ca_labels(y_len, u, U), S = 2 * L + 1;
+    const int L = clampi(y_len[u], 0, U), S = 2 * L + 1;
     const bool act = s < S, odd = s & 1;
     const int* lab = y + (size_t)u * ldy;
     const int c = (act && odd) ? lab[s >> 1] : 0;
@@ -161,7 +151,7 @@ __global__ __launch_bounds__(256) void ctc_align_trace_kernel(int Tp, const int*
     __shared__ __attribute__((aligned(16))) unsigned words[CA_STAGE_WORDS];
     __shared__ int st[CA_MAX_TP];
     const int u = blockIdx.x, tid = threadIdx.x;
-    const int T = ca_frames(enc_len, u, Tp), L = ca_labels(y_len, u, U);
+    const int T = clampi(enc_len[u], 1, Tp), L = clampi(y_len[u], 0, U);
     const int fin = w.fin[u];
     int* fst = frame_state ? frame_state + (size_t)u * Tp : w.fs + (size_t)u * Tp;
     if (fin < 0) {

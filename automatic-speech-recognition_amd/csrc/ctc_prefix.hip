@@ -15,12 +15,13 @@
 //                              over t; the EOS candidate is the full-sequence probability of h.EOS, a chain that runs in lock step with the
 //                              advance of step 1;
 //                           3. joint[row][v] = logit[v] + lam * (psi(h.v) - psi(h)) for the candidates, -inf for every other token.
-//                         The step counter, the utterance's done word and its live count are read on the device: the launch is the same
-//                         every step and is captured into the search's HIP graph.  No atomics; fixed reduction orders: same bits every run.
+//                         Live rows only, by the rule every scorer shares (search_rows.h): the launch is the same every step and is
+//                         captured into the search's HIP graph.  No atomics; fixed reduction orders: same bits every run.
 //
 // State row (state_width >= 2 T' + 2 floats): [0, T') r^n_t(h), [T', 2 T') r^b_t(h), [2 T'] psi(h), [2 T' + 1] last label of h (-1: empty).
 // All values are log-probabilities in fp32; LOGZERO = -1e10 (ESPnet's constant) instead of -inf keeps impossible prefixes finite.
 #include "las_common.h"
+#include "search_rows.h"
 #include <math.h>
 
 namespace {
@@ -33,20 +34,6 @@ constexpr int CP_MAX_TP = 2048;              // six [T'] fp32 arrays in LDS (48 
 __device__ __forceinline__ float lae(float a, float b) {                    // log(exp(a) + exp(b)), both finite
     const float m = fmaxf(a, b);
     return m + __logf(1.f + __expf(-fabsf(a - b)));
-}
-__device__ __forceinline__ unsigned cp_order(float f) {                    // unsigned order == float order
-    const unsigned b = __float_as_uint(f + 0.f);
-    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {                        // xor butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 // psi(h.v) by one wave: logsumexp of `start` and of phi[t-1] + y[t] for 1 <= t < T.  phi: LDS, y: the candidate's column (LDS or global),
 // read once: every lane keeps a running (max, sum of exp) pair, and the pairs meet in an xor butterfly (the combination is symmetric in
@@ -70,10 +57,9 @@ __device__ __forceinline__ float wave_psi(const float* phi, const float* y, int 
     return m + __logf(s);
 }
 
-struct CtcPrefixDev {
+struct CtcPrefixDev : SearchRows {                                     // (the rows and search_row_live: search_rows.h)
     const float* lp; const int* enc_len; const float* logits; float* joint;
-    const float* st_in; float* st_out; const int* token; const int* step; const int* nlive; const int* done; const int* dec_step;
-    int nutt, beam, V, Tp, width, Umax, end_id; float lam;
+    int V, Tp, end_id; float lam;
 };
 
 // BANK: V > 64, the top-64 cut binds and is selected here (a V <= 64 vocabulary takes every token and needs none of its registers)
@@ -84,14 +70,10 @@ __global__ __launch_bounds__(256) void ctc_prefix_step_kernel(CtcPrefixDev a) {
     __shared__ int wcnt[2][4];
     __shared__ float psi_s[2];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int t_step = __hip_atomic_load(a.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t_step >= a.Umax) return;
-    const int u = row / a.beam, j = row - u * a.beam;
-    if (a.done[u] || t_step >= a.dec_step[u]) return;                  // las_beam_loop_step ignores the utterance's rows
-    if (j >= (t_step == 0 ? 1 : a.nlive[u])) return;                   // no live hypothesis in this slot: its joint row is never ranked
+    int t_step, u;
+    if (!search_row_live(a, row, t_step, u)) return;                   // (a row that is not live: its joint row is never ranked)
     const int Tp = a.Tp, V = a.V, Vc = V + 1, W = a.width;
-    int T = a.enc_len[u];
-    T = T < 1 ? 1 : (T > Tp ? Tp : T);
+    const int T = clampi(a.enc_len[u], 1, Tp);
     float* RN = cp_lds;                 // r^n of the parent, then of h
     float* RB = RN + Tp;                // r^b ...
     float* P = RB + Tp;                 // phi of the parent for c (t-1 -> index t-1), then phi_o of h
@@ -99,8 +81,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_step_kernel(CtcPrefixDev a) {
     float* YB = YC + Tp;
     float* YE = YB + Tp;
     const float* col = a.lp + (size_t)u * Vc * Tp;
-    int c = a.token[row];
-    c = c < 0 ? 0 : (c >= V ? V - 1 : c);                              // (always a token id; clamped: no read outside lp)
+    const int c = clampi(a.token[row], 0, V - 1);                      // (always a token id; clamped: no read outside lp)
     const bool first = t_step == 0;     // h = [SOS]: the empty prefix (no advance)
     const float* sp = a.st_in + (size_t)row * W;
     for (int i = tid; i < T; i += 256) {
@@ -123,7 +104,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_step_kernel(CtcPrefixDev a) {
 #pragma unroll
         for (int s = 0; s < CP_MAX_SLOTS; ++s) {
             const int v = s * 256 + tid;
-            KA[s] = (s < NS && v < V) ? cp_order(lg[v]) : 0u;
+            KA[s] = (s < NS && v < V) ? order_key(lg[v] + 0.f) : 0u;
         }
         // largest TA with count(key >= TA) >= 64 (counts: per-slot ballots, the four waves' sums through LDS, one barrier per probe)
         auto count_ge = [&](auto pred, int parity) {
@@ -242,8 +223,8 @@ __global__ __launch_bounds__(256) void ctc_log_softmax_kernel(const float* __res
         if (t < Tp) {
             const float* r = xu + (size_t)t * Vc;
             for (int v = lane; v < Vc; v += 64) m = fmaxf(m, r[v]);
-            m = wave_max(m);
-            for (int v = lane; v < Vc; v += 64) s += expf(r[v] - m);
+            m = wave_max(m);                                            // (every lane is here: t < Tp is the wave's, t = t0 + f and
+            for (int v = lane; v < Vc; v += 64) s += expf(r[v] - m);   //  f runs over [16 w, 16 w + 16) in every lane of wave w)
             s = wave_sum(s);
         }
         if (lane == 0) lse[f] = t < Tp ? m + logf(s) : 0.f;
@@ -278,17 +259,14 @@ extern "C" int las_ctc_prefix_step(const float* lp, const int* enc_len, int nutt
                                    const float* logits, float* joint, float lam, const float* state_in, float* state_out,
                                    int state_width, const int* token, const int* step, const int* nlive, const int* done,
                                    const int* dec_step, int Umax, void* stream) {
-    LAS_ARG(lp && enc_len && logits && joint && state_in && state_out && token && step && nlive && done && dec_step,
-            "las_ctc_prefix_step: null pointer");
-    LAS_ARG(nutt > 0 && beam > 0 && Umax > 0 && V > 1 && end_id >= 0 && end_id < V, "las_ctc_prefix_step: bad dims");
     LAS_ARG(Tp > 0 && Tp <= CP_MAX_TP, "las_ctc_prefix_step: 1 <= T' <= %d (got %d)", CP_MAX_TP, Tp);
-    LAS_ARG(V <= CP_MAX_SLOTS * 256, "las_ctc_prefix_step: V <= %d (got %d)", CP_MAX_SLOTS * 256, V);
-    LAS_ARG(state_width >= 2 * Tp + 2, "las_ctc_prefix_step: state_width %d < 2 T' + 2 = %d", state_width, 2 * Tp + 2);
-    LAS_ARG(state_in != state_out, "las_ctc_prefix_step: state_in and state_out must differ");
     CtcPrefixDev a;
-    a.lp = lp; a.enc_len = enc_len; a.logits = logits; a.joint = joint; a.st_in = state_in; a.st_out = state_out; a.token = token;
-    a.step = step; a.nlive = nlive; a.done = done; a.dec_step = dec_step;
-    a.nutt = nutt; a.beam = beam; a.V = V; a.Tp = Tp; a.width = state_width; a.Umax = Umax; a.end_id = end_id; a.lam = lam;
+    if (search_rows_args(a, "las_ctc_prefix_step", 2 * Tp + 2, nutt, beam, state_in, state_out, state_width,
+                         token, step, nlive, done, dec_step, Umax)) return -1;
+    LAS_ARG(lp && enc_len && logits && joint && token, "las_ctc_prefix_step: null pointer");
+    LAS_ARG(V > 1 && end_id >= 0 && end_id < V, "las_ctc_prefix_step: bad dims");
+    LAS_ARG(V <= CP_MAX_SLOTS * 256, "las_ctc_prefix_step: V <= %d (got %d)", CP_MAX_SLOTS * 256, V);
+    a.lp = lp; a.enc_len = enc_len; a.logits = logits; a.joint = joint; a.V = V; a.Tp = Tp; a.end_id = end_id; a.lam = lam;
     const size_t lds = (size_t)6 * Tp * sizeof(float);
     if (V > CP_TOPN) hipLaunchKernelGGL(ctc_prefix_step_kernel<true>, dim3(nutt * beam), dim3(256), lds, (hipStream_t)stream, a);
     else             hipLaunchKernelGGL(ctc_prefix_step_kernel<false>, dim3(nutt * beam), dim3(256), lds, (hipStream_t)stream, a);

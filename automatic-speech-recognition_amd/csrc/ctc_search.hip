@@ -43,7 +43,9 @@ constexpr int BEAM_MAX_E = CTC_MAX_K * (CTC_MAX_C + 1);
 
 typedef unsigned long long u64;
 
-// float -> unsigned whose order is the floats' (-0 and +0 are one key)
+// float -> unsigned whose order is the floats' (-0 and +0 are one key).  The mapping is las_common.h's order_key bit for bit; it stays
+// written out as a select here because the compiler turns the two spellings into different code, and with order_key's the beam kernel
+// measured 1 % slower (3375 against 3345 us per 64 utterances x 150 frames, tools/bench_ctc_search.py, alternating runs)
 __device__ __forceinline__ unsigned okey(float f) {
     if (f == 0.f) f = 0.f;
     const unsigned u = __float_as_uint(f);
@@ -85,8 +87,7 @@ __global__ __launch_bounds__(TOPK_NT) void ctc_frame_topk_kernel(const float* __
     __shared__ u64 redu[TOPK_NT / 64];
     __shared__ int wg[TOPK_NT / 64], we[TOPK_NT / 64];
     const int u = blockIdx.x / Tp, t = blockIdx.x - u * Tp, tid = threadIdx.x;
-    int Tu = enc_len[u];
-    Tu = Tu < 0 ? 0 : (Tu > Tp ? Tp : Tu);
+    const int Tu = clampi(enc_len[u], 0, Tp);
     if (t >= Tu) return;
     const size_t f = (size_t)u * Tp + t;
     const float* z = logits + f * Vc;
@@ -107,8 +108,7 @@ __global__ __launch_bounds__(TOPK_NT) void ctc_frame_topk_kernel(const float* __
     const float lse = m + logf(s);
     bk = block_u64max<TOPK_NT>(bk, redu);
     if (tid == 0) {
-        int b = (int)(0xffffffffu - (unsigned)bk);
-        b = b < 0 ? 0 : (b > V ? V : b);
+        const int b = clampi((int)(0xffffffffu - (unsigned)bk), 0, V);
         best[f] = b;
         best_lp[f] = z[b] - lse;
         blank_lp[f] = z[V] - lse;
@@ -170,8 +170,7 @@ __global__ __launch_bounds__(256) void ctc_greedy_kernel(const int* __restrict__
                                                          int* __restrict__ lens, double* __restrict__ scores) {
     __shared__ int wc[4];
     const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int Tu = enc_len[u];
-    Tu = Tu < 0 ? 0 : (Tu > Tp ? Tp : Tu);
+    const int Tu = clampi(enc_len[u], 0, Tp);
     const int* b = best + (size_t)u * Tp;
     const u64 below = (1ull << lane) - 1ull;
     int run = 0;
@@ -228,8 +227,8 @@ __device__ __forceinline__ float lm_gain(const NgramTrie& L, int node, int c, in
     int q = node;
     for (int lvl = 0; lvl < L.order && q != 0; ++lvl) {
         int lo, hi;
-        ngram_range(L, q, lo, hi);
-        const int k = ngram_find(L, lo, hi, c);
+        trie_range(L.child_off, L.E, q, lo, hi);
+        const int k = trie_find(L.child_tok, lo, hi, c);
         if (k >= 0) {
             next = L.child_next[k];
             if (next < 0 || next >= L.M) next = 0;
@@ -281,8 +280,7 @@ __global__ __launch_bounds__(BEAM_NT) void ctc_beam_kernel(CtcBeamDev a) {
     int* nd_tok = a.nd_tok + (size_t)u * NN;
     int* nd_len = a.nd_len + (size_t)u * NN;
     int* nd_slot = a.nd_slot + (size_t)u * NN;
-    int Tu = a.enc_len[u];
-    Tu = Tu < 0 ? 0 : (Tu > Tp ? Tp : Tu);
+    const int Tu = clampi(a.enc_len[u], 0, Tp);
 
     for (int i = tid; i < H; i += BEAM_NT) hkey[i] = -1;
     if (tid == 0) {
@@ -432,8 +430,7 @@ __global__ __launch_bounds__(BEAM_NT) void ctc_beam_kernel(CtcBeamDev a) {
     if (tid < nlive) {
         const size_t row = (size_t)u * K + tid;
         a.totals[row] = lae(s_pb[tid], s_pnb[tid]);
-        int len = s_len[tid];
-        len = len < 0 ? 0 : (len > Tp ? Tp : len);
+        const int len = clampi(s_len[tid], 0, Tp);
         a.lens[row] = len;
         int node = s_node[tid];
         for (int pos = len - 1; pos >= 0 && node > 0 && node < NN; --pos) {
@@ -494,11 +491,11 @@ extern "C" int las_ctc_beam_search(const int* cand_tok, const float* cand_lp, co
     if (has_lm) {
         LAS_ARG(child_off && bow && bo && uni_lp && uni_next, "las_ctc_beam_search: n-gram tables: null pointer");
         LAS_ARG(nchild >= 0 && (nchild == 0 || (child_tok && child_lp && child_next)), "las_ctc_beam_search: %d children but no child tables", nchild);
-        LAS_ARG(V > 1 && V <= NGRAM_MAX_V, "las_ctc_beam_search: with an n-gram 1 < V <= %d (got %d)", NGRAM_MAX_V, V);
-        LAS_ARG(nnodes <= NGRAM_MAX_NODES, "las_ctc_beam_search: 1 <= nodes <= %d (got %d)", NGRAM_MAX_NODES, nnodes);
+        LAS_ARG(V > 1 && V <= TRIE_MAX_V, "las_ctc_beam_search: with an n-gram 1 < V <= %d (got %d)", TRIE_MAX_V, V);
+        LAS_ARG(nnodes <= TRIE_MAX_NODES, "las_ctc_beam_search: 1 <= nodes <= %d (got %d)", TRIE_MAX_NODES, nnodes);
         LAS_ARG(order >= 1 && order <= NGRAM_MAX_ORDER, "las_ctc_beam_search: 1 <= order <= %d (got %d)", NGRAM_MAX_ORDER, order);
     } else {
-        LAS_ARG(nnodes == 0, "las_ctc_beam_search: 1 <= nodes <= %d (got %d)", NGRAM_MAX_NODES, nnodes);
+        LAS_ARG(nnodes == 0, "las_ctc_beam_search: 1 <= nodes <= %d (got %d)", TRIE_MAX_NODES, nnodes);
     }
     const size_t need = las_ctc_beam_workspace_bytes(n, Tp, K, C);
     LAS_ARG(ws_bytes >= need, "las_ctc_beam_search: workspace of %zu bytes, %zu needed", ws_bytes, need);

@@ -39,30 +39,18 @@ constexpr int KW_WAVES = 4;              // phrases per workgroup of kws_search_
 
 typedef float kw_f4u __attribute__((ext_vector_type(4), aligned(4)));      // four floats at any float's address
 
-__host__ __device__ inline size_t kw_align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-__device__ __forceinline__ int kw_frames(const int* enc_len, int u, int Tp) {
-    const int T = enc_len[u];
-    return T < 1 ? 1 : (T > Tp ? Tp : T);
-}
-
 // a lane's double in every lane (wave-uniform lane index): two v_readlane_b32
 __device__ __forceinline__ double kw_readlane(double v, int lane) {
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane), lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
     return __hiloint2double(hi, lo);
 }
 
-// lane i reads lane i - 1 of the wave (DPP wave_shr:1, one VALU move per dword; lane 0 gets 0): the predecessor reads of the recursion
-// without the LDS queue round trip of __shfl_up
-__device__ __forceinline__ int kw_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ double kw_shr1(double v) { return __hiloint2double(kw_shr1(__double2hiint(v)), kw_shr1(__double2loint(v))); }
-
 // grid (ceil(T'/64), n), block (64, KW_FM_Y)
 __global__ __launch_bounds__(64 * KW_FM_Y) void kws_frame_max_kernel(const float* __restrict__ lp, int Vc, int Tp,
                                                                       const int* __restrict__ enc_len, float* __restrict__ m) {
     __shared__ float part[KW_FM_Y][64];
     const int u = blockIdx.y, t = blockIdx.x * 64 + threadIdx.x;
-    const int T = kw_frames(enc_len, u, Tp);
+    const int T = clampi(enc_len[u], 1, Tp);
     if ((int)blockIdx.x * 64 >= T) return;                                     // (uniform: frames t >= T_u are never read)
     float v = -INFINITY;
     if (t < T) {
@@ -90,7 +78,7 @@ __global__ __launch_bounds__(64 * KW_WAVES) void kws_search_kernel(const float* 
     const int lane = threadIdx.x & 63;
     const int u = blockIdx.y, p = blockIdx.x * KW_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (p >= P) return;                                                        // (wave-uniform; there is no barrier to miss)
-    const int T = kw_frames(enc_len, u, Tp);
+    const int T = clampi(enc_len[u], 1, Tp);
     const size_t up = (size_t)u * P + p;
     const int Lraw = y_len[p], Lmax = U < KW_MAX_L ? U : KW_MAX_L;
     bool ok = Lraw >= 1 && Lraw <= Lmax;
@@ -192,8 +180,8 @@ __global__ __launch_bounds__(64 * KW_WAVES) void kws_search_kernel(const float* 
                     if (t >= tend) continue;                                   // (uniform)
                     const float ev = j == 0 ? e4.x : j == 1 ? e4.y : j == 2 ? e4.z : e4.w;
                     const float mv = j == 0 ? m4.x : j == 1 ? m4.y : j == 2 ? m4.z : m4.w;
-                    const double b1 = kw_shr1(b), b2 = kw_shr1(b1);            // lanes 0 (and 1 for the second) read nothing they use
-                    const int s1 = kw_shr1(st), s2 = kw_shr1(s1);
+                    const double b1 = wave_shr1(b), b2 = wave_shr1(b1);        // lanes 0 (and 1 for the second) read nothing they use
+                    const int s1 = wave_shr1(st), s2 = wave_shr1(s1);
                     double cb = b;
                     int cs = st;
                     if (lane >= 1 && b1 > cb) { cb = b1; cs = s1; }            // equal values: the earlier candidate stays
@@ -253,7 +241,7 @@ __global__ __launch_bounds__(64 * KW_WAVES) void kws_search_kernel(const float* 
 
 extern "C" size_t las_kws_workspace_bytes(int n, int Tp) {
     if (n <= 0 || Tp <= 0) return 0;
-    return kw_align256((size_t)n * Tp * 4);
+    return align256((size_t)n * Tp * 4);
 }
 
 extern "C" int las_kws_search(const float* lp, int Vc, int Tp, const int* enc_len, int n, const int* y, int ldy, const int* y_len,

@@ -155,6 +155,25 @@ __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, dpp_f<0x128>(v)); v = fmaxf(v, dpp_f<0x124>(v)); v = fmaxf(v, dpp_f<0x122>(v)); v = fmaxf(v, dpp_f<0x121>(v));
     return v;
 }
+// lane i reads lane i - 1 of the wave (DPP wave_shr:1, one VALU move per dword instead of __shfl_up's round trip through the LDS
+// queue); lane 0 has no source: it reads 0, or keeps its own value in the _keep form.  EVERY lane must be active.
+__device__ __forceinline__ int wave_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }
+__device__ __forceinline__ double wave_shr1(double v) { return __hiloint2double(wave_shr1(__double2hiint(v)), wave_shr1(__double2loint(v))); }
+__device__ __forceinline__ int wave_shr1_keep(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
+// orders one wave's own LDS traffic (a wave's lanes exchange data through LDS without a workgroup barrier)
+__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// terms[0, L) added in index order in float64 by one FULL wave (L wave-uniform: uniform control flow around the shuffles): the lanes
+// load 64 terms at once, then every lane adds them in order (a broadcast per term) -- one lane walking the row alone waits a memory
+// round trip per term (17 us for 77 terms, measured: as long as las_rescore_score's whole score kernel).  The sum is in every lane.
+__device__ __forceinline__ double wave_terms_sum_f64(const float* terms, int L, int lane) {
+    double s = 0.0;
+    for (int base = 0; base < L; base += 64) {
+        const float x = base + lane < L ? terms[base + lane] : 0.f;
+        const int n = L - base < 64 ? L - base : 64;
+        for (int i = 0; i < n; ++i) s += (double)__shfl(x, i);
+    }
+    return s;
+}
 // block-wide sum for blockDim.x == NT (multiple of 64); red must hold NT/64 floats. All threads get the result.
 template <int NT> __device__ __forceinline__ float block_sum(float v, float* red) {
     v = wave_sum(v);
@@ -235,6 +254,15 @@ __device__ __forceinline__ u32x2_t granule8_load(__amdgpu_buffer_rsrc_t rs, unsi
 }
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+__host__ __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }      // (lo <= hi)
+__host__ __device__ inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }                   // workspace carving
+// float -> unsigned whose order is the floats'.  The bare mapping: -0 sorts below +0 and a NaN by its bits; a caller that wants one key
+// for both zeros canonicalises first (f + 0.f also quiets a signalling NaN, f == 0.f ? 0.f : f keeps every payload -- each caller
+// keeps the one it always had; ctc_search.hip's okey is the same mapping in another spelling, see there)
+__device__ __forceinline__ unsigned order_key(float f) {
+    const unsigned b = __float_as_uint(f);
+    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
 
 extern "C" int las_colsum_dt(const void* X, int dtype, int rows, int cols, int ldx, float beta, float* out, void* ws,
                              size_t ws_bytes, void* stream);

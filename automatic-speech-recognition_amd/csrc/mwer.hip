@@ -6,8 +6,8 @@
 //      label's term z[y] - lse, both kept in the workspace.  Up to 8192 classes a lane keeps its values in registers between the
 //      maximum and the sum (as ce_rows_reg_kernel): the row is read once; larger rows are read twice.  Steps t >= len[r] and the rows of
 //      absent slots are skipped.
-//   2  one workgroup per utterance: a row's terms added in step order in float64 (a wave per row, 64 terms per load, as
-//      rescore_sum_kernel), then posterior, expected errors and the rows' coefficients in float64, every sum in slot order.
+//   2  one workgroup per utterance: a row's terms added in step order in float64 (a wave per row: wave_terms_sum_f64), then
+//      posterior, expected errors and the rows' coefficients in float64, every sum in slot order.
 //   3  one wave per (row, step) again: dlogits = coef (onehot - expf(z - lse)), exact zeros wherever the contract asks for them -- those
 //      rows are stored without a look at the logits.  One more workgroup behind the grid adds the utterances' risks in a fixed order
 //      (with dlogits = NULL that workgroup is the whole launch).
@@ -21,8 +21,6 @@ namespace {
 constexpr int MWER_MAX_K = 64;
 constexpr int MWER_MAX_U = 1024;
 constexpr int UTT_NT = 256;
-
-__device__ __forceinline__ int clamp0(const int x, const int hi) { return x < 0 ? 0 : (x > hi ? hi : x); }
 
 // the workspace: [risk fp64 n | lse fp32 n K U | term fp32 n K U | coef fp32 n K]
 struct MwerWs {
@@ -51,8 +49,8 @@ __global__ __launch_bounds__(256) void mwer_lse_kernel(const float* __restrict__
     if (idx >= (long long)n * K * U) return;                           // (a wave's own index: the whole wave leaves)
     const int r = (int)(idx / U), t = (int)(idx - (long long)r * U);
     const int u = r / K, k = r - u * K;
-    if (k >= clamp0(nhyp[u], K)) return;                               // an absent slot: nothing of it is read
-    if (t >= clamp0(len[r], U)) return;
+    if (k >= clampi(nhyp[u], 0, K)) return;                               // an absent slot: nothing of it is read
+    if (t >= clampi(len[r], 0, U)) return;
     const float* z = logits + (long long)r * sb + (long long)t * st;
     float m = -INFINITY, s = 0.f;
     if (NV > 0) {
@@ -90,9 +88,8 @@ __global__ __launch_bounds__(256) void mwer_lse_kernel(const float* __restrict__
     }
 }
 
-// one workgroup per utterance.  Waves 0 .. 3 add the terms of slots w, w + 4, ... (the lanes load 64 terms at once, then every lane adds
-// them in step order: a broadcast per term); then thread k < nhyp is slot k, and every sum over the slots runs in slot order in every
-// thread (<= 64 LDS broadcasts).
+// one workgroup per utterance.  Waves 0 .. 3 add the terms of slots w, w + 4, ... in step order; then thread k < nhyp is slot k, and
+// every sum over the slots runs in slot order in every thread (<= 64 LDS broadcasts).
 __global__ __launch_bounds__(UTT_NT) void mwer_utt_kernel(const int* __restrict__ len, const int* __restrict__ nhyp,
                                                           const float* __restrict__ err, int n, int K, int U, int mode,
                                                           const float* __restrict__ scale_ptr, double* __restrict__ seq_lp,
@@ -100,17 +97,11 @@ __global__ __launch_bounds__(UTT_NT) void mwer_utt_kernel(const int* __restrict_
                                                           MwerWs w) {
     __shared__ double lp[MWER_MAX_K], ex[MWER_MAX_K], pp[MWER_MAX_K], ee[MWER_MAX_K];
     const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const int nh = clamp0(nhyp[u], K);
+    const int nh = clampi(nhyp[u], 0, K);
     const size_t base = (size_t)u * K;
     for (int k = tid >> 6; k < nh; k += UTT_NT / 64) {                 // (k is the wave's: uniform control flow around the shuffles)
         const size_t r = base + k;
-        const int L = clamp0(len[r], U);
-        double s = 0.0;
-        for (int b0 = 0; b0 < L; b0 += 64) {
-            const float x = b0 + lane < L ? w.term[r * U + b0 + lane] : 0.f;
-            const int cnt = L - b0 < 64 ? L - b0 : 64;
-            for (int i = 0; i < cnt; ++i) s += (double)__shfl(x, i);
-        }
+        const double s = wave_terms_sum_f64(w.term + r * U, clampi(len[r], 0, U), lane);
         if (lane == 0) {
             lp[k] = s;
             if (seq_lp) seq_lp[r] = s;
@@ -215,7 +206,7 @@ __global__ __launch_bounds__(256) void mwer_grad_kernel(const float* __restrict_
     float* d = dlogits + off;
     const float c = w.coef[r];                                         // 0: an absent slot, no posterior, or no share in the gradient
     float l = -INFINITY;
-    if (c != 0.f && t < clamp0(len[r], U)) l = w.lse[idx];
+    if (c != 0.f && t < clampi(len[r], 0, U)) l = w.lse[idx];
     if (!(l > -INFINITY)) {                                            // (also a step without mass: expf(-inf + inf) would be NaN)
         for (int v = lane; v < V; v += 64) d[v] = 0.f;
         return;

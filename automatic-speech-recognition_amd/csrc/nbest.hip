@@ -41,11 +41,6 @@ __host__ __device__ inline int nb_pitch(int U) { return (U + 63) / 64 * 64; }
 __host__ __device__ inline int nb_rows(int U) { return (U + 15) / 16; }
 __host__ __device__ inline size_t nb_dir_words(int U) { return (size_t)nb_rows(U) * nb_pitch(U); }
 
-__device__ __forceinline__ int nb_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// orders one wave's own LDS traffic (a wave's lanes exchange data through LDS without a workgroup barrier)
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 // lane l reads lane l - CTRL's source; a lane without a source (or in a row ROWS masks out) keeps its own value.  EVERY lane must be active.
 template <int CTRL, int ROWS> __device__ __forceinline__ int dpp_keep(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, ROWS, 0xf, false); }
 
@@ -84,7 +79,7 @@ __device__ __forceinline__ int nb_edit_dp(const int* __restrict__ a, int La, con
         up = j;                                                                // D[0][j]
         for (int i = 1; i <= La; ++i) {
             const int ai = sa[i - 1], cin = col[i];                            // (uniform addresses: broadcasts)
-            int diag = __builtin_amdgcn_update_dpp(up, up, 0x138, 0xf, 0xf, false);    // wave_shr:1
+            int diag = wave_shr1_keep(up);                                     // D[i-1][j-1] of the lane before
             if (lane == 0) diag = dprev;
             const bool eq = ai == bj;
             const int t = min(up + 1, diag + (eq ? 0 : 1));
@@ -118,9 +113,9 @@ __global__ __launch_bounds__(64 * NB_WAVES) void nbest_pairs_kernel(const int* _
     int i = 0;
     while (p >= K - 1 - i) { p -= K - 1 - i; ++i; }                            // pair p of the upper triangle, row by row
     const int j = i + 1 + p;
-    if (j >= nb_clamp(nhyp[u], K)) return;
+    if (j >= clampi(nhyp[u], 0, K)) return;
     const size_t r = (size_t)u * K;
-    const int d = nb_edit_dp<false>(tok + (r + i) * U, nb_clamp(len[r + i], U), tok + (r + j) * U, nb_clamp(len[r + j], U), sa[wv], col[wv],
+    const int d = nb_edit_dp<false>(tok + (r + i) * U, clampi(len[r + i], 0, U), tok + (r + j) * U, clampi(len[r + j], 0, U), sa[wv], col[wv],
                                     nullptr, 0);
     if ((threadIdx.x & 63) == 0) {
         dist[(r + i) * K + j] = d;
@@ -133,7 +128,7 @@ __global__ __launch_bounds__(64) void nbest_risk_kernel(const int* __restrict__ 
                                                         float* __restrict__ risk, int* __restrict__ pick) {
     __shared__ float sr[NB_MAX_K], sw[NB_MAX_K];
     const int u = blockIdx.x, i = threadIdx.x;
-    const int nh = nb_clamp(nhyp[u], K);
+    const int nh = clampi(nhyp[u], 0, K);
     const size_t r = (size_t)u * K;
     if (i < nh) {
         dist[(r + i) * K + i] = 0;
@@ -168,12 +163,12 @@ __global__ __launch_bounds__(64 * NB_WAVES) void nbest_align_kernel(const int* _
     __shared__ int sa[NB_WAVES][NB_MAX_U];
     __shared__ int col[NB_WAVES][NB_MAX_U + 1];
     const int u = blockIdx.y, wv = threadIdx.x >> 6, k = blockIdx.x * NB_WAVES + wv;
-    const int nh = nb_clamp(nhyp[u], K);
+    const int nh = clampi(nhyp[u], 0, K);
     if (k >= nh) return;
     const int pv = nb_pivot(pivot, u, nh);
     if (pv < 0) return;
     const size_t r = (size_t)u * K;
-    nb_edit_dp<true>(tok + (r + pv) * U, nb_clamp(len[r + pv], U), tok + (r + k) * U, nb_clamp(len[r + k], U), sa[wv], col[wv],
+    nb_edit_dp<true>(tok + (r + pv) * U, clampi(len[r + pv], 0, U), tok + (r + k) * U, clampi(len[r + k], 0, U), sa[wv], col[wv],
                      dirs + (r + k) * nb_dir_words(U), nb_pitch(U));
 }
 
@@ -185,17 +180,17 @@ __global__ __launch_bounds__(64 * NB_WAVES) void nbest_trace_kernel(const int* _
     __shared__ unsigned stage[NB_WAVES][NB_STAGE];
     __shared__ signed char hit[NB_WAVES][NB_MAX_U];
     const int u = blockIdx.x, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int nh = nb_clamp(nhyp[u], K);
+    const int nh = clampi(nhyp[u], 0, K);
     const int pv = nb_pivot(pivot, u, nh);
     if (pv < 0) return;                                                        // (the whole workgroup)
     const size_t r = (size_t)u * K;
-    const int La = nb_clamp(len[r + pv], U), pitch = nb_pitch(U);
+    const int La = clampi(len[r + pv], 0, U), pitch = nb_pitch(U);
     unsigned* st = stage[wv];
     signed char* m = hit[wv];
     for (int k = wv; k < nh; k += NB_WAVES) {
         const unsigned* dw = dirs + (r + k) * nb_dir_words(U);
         for (int i = lane; i < La; i += 64) m[i] = 0;
-        int i = La, j = nb_clamp(len[r + k], U);
+        int i = La, j = clampi(len[r + k], 0, U);
         while (i > 0 && j > 0) {                                               // (wave-uniform)
             // columns [0, j) of the row blocks lo .. hi: what the walk can still visit, as many blocks as fit
             const int hi = (i - 1) >> 4, jw = j;
@@ -316,7 +311,7 @@ __global__ __launch_bounds__(64) void nbest_network_kernel(const int* __restrict
     __shared__ unsigned char cnt[CN_MAX_BINS], scup[CN_MAX_BINS];              // per row: distinct symbols, bit 7 = EPS among them; per place: cup
     __shared__ float sw[NB_MAX_K];
     const int u = blockIdx.x, lane = threadIdx.x;
-    const int nh = __builtin_amdgcn_readfirstlane(nb_clamp(nhyp[u], K));
+    const int nh = __builtin_amdgcn_readfirstlane(clampi(nhyp[u], 0, K));
     const size_t r = (size_t)u * K;
     const int Kp = cn_kp(K);
     unsigned* dirs = ws + (size_t)u * cn_utt_words(K, U, max_bins);
@@ -326,7 +321,7 @@ __global__ __launch_bounds__(64) void nbest_network_kernel(const int* __restrict
     unsigned long long mmask = 0;                                              // bit k: slot k was merged
     if (lane < nh) sw[lane] = w[r + lane];
     for (int k = 0; k < nh; ++k) {
-        const int L = __builtin_amdgcn_readfirstlane(nb_clamp(len[r + k], U));
+        const int L = __builtin_amdgcn_readfirstlane(clampi(len[r + k], 0, U));
         const int* b = sym + (r + k) * U;
         __syncthreads();                                                       // the merge before is done with the LDS, and its stores are visible
         for (int j = lane; j < L; j += 64) sb[j] = max(b[j], 0);
@@ -383,7 +378,7 @@ __global__ __launch_bounds__(64) void nbest_network_kernel(const int* __restrict
                 for (int i = 1; i <= B; ++i) {
                     const unsigned long long m = smask[i - 1];                 // (uniform addresses: broadcasts)
                     const int cu = scup[i - 1], cin = col[i];
-                    int diag = __builtin_amdgcn_update_dpp(up, up, 0x138, 0xf, 0xf, false);    // wave_shr:1
+                    int diag = wave_shr1_keep(up);                                     // D[i-1][j-1] of the lane before
                     if (lane == 0) diag = dprev;
                     const bool eq = (m >> lane) & 1ull;
                     const int t = min(up + cu, diag + (eq ? 0 : 1));

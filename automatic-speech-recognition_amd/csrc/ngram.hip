@@ -12,8 +12,7 @@
 // cyclic bo table cannot spin.
 //
 // las_ngram_step, once per search step, behind the step's logits (and the RNN LM's) and in front of las_ctc_prefix_step, las_bias_step
-// and las_beam_loop_step.  One workgroup of 256 lanes per hypothesis row, the liveness rules of las_bias_step (rows that are not live are
-// not written):
+// and las_beam_loop_step.  One workgroup of 256 lanes per hypothesis row, live rows only (search_rows.h):
 //   advance   the gathered parent's node (state_in[row][0], a float that holds an integer < 2^24; the root at step 0 or when the value
 //             is not a node) is advanced by the entering token into state_out[row][0]; every lane walks the same binary searches.
 //   score     over the chain s0 = s, s1 = bo(s0), ..., root with acc0 = 0: every child v of s_i that no deeper level held gets
@@ -29,39 +28,32 @@
 // (tests/ngram_ref.py).
 #include "las_common.h"
 #include "ngram_trie.h"
+#include "search_rows.h"
 #include <math.h>
 
 namespace {
 
-struct NgramDev : NgramTrie {                                          // (the tables and ngram_range / ngram_find / ngram_backoff: ngram_trie.h)
-    float* scores; const float* st_in; float* st_out; const int *token, *step, *nlive, *done, *dec_step;
-    int nutt, beam, V, width, Umax;
+struct NgramDev : SearchRows, NgramTrie {                              // (the rows and search_row_live / search_parent_node: search_rows.h;
+    float* scores; int V;                                              //  the tables and trie_range / trie_find / ngram_backoff: ngram_trie.h)
 };
 
 __global__ __launch_bounds__(256) void ngram_step_kernel(NgramDev a) {
-    __shared__ unsigned char mark[NGRAM_MAX_V];
+    __shared__ unsigned char mark[TRIE_MAX_V];
     const int row = blockIdx.x, tid = threadIdx.x;
-    const int t_step = __hip_atomic_load(a.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t_step >= a.Umax) return;
-    const int u = row / a.beam, j = row - u * a.beam;
-    if (a.done[u] || t_step >= a.dec_step[u]) return;                  // las_beam_loop_step ignores the utterance's rows
-    if (j >= (t_step == 0 ? 1 : a.nlive[u])) return;                   // no live hypothesis in this slot
+    int t_step, u;
+    if (!search_row_live(a, row, t_step, u)) return;
     const int V = a.V, M = a.M;
 
     // ---- advance (uniform over the workgroup)
-    int p = 0;
-    if (t_step > 0) {
-        const float f = a.st_in[(size_t)row * a.width];
-        if (f >= 0.f && f < (float)M) p = (int)f;                      // (NaN fails both compares)
-    }
+    const int p = search_parent_node(a, row, t_step, M);
     const int c = a.token[row];
     int s = 0;
     if (c >= 0 && c < V) {
         int k = -1, q = p;
         for (int lvl = 0; lvl < a.order && q != 0 && k < 0; ++lvl) {
             int lo, hi;
-            ngram_range(a, q, lo, hi);
-            k = ngram_find(a, lo, hi, c);
+            trie_range(a.child_off, a.E, q, lo, hi);
+            k = trie_find(a.child_tok, lo, hi, c);
             q = ngram_backoff(a, q);
         }
         s = k >= 0 ? a.child_next[k] : a.uni_next[c];
@@ -81,7 +73,7 @@ __global__ __launch_bounds__(256) void ngram_step_kernel(NgramDev a) {
     int q = s;
     for (int lvl = 0; lvl < a.order && q != 0; ++lvl) {                // (q is the same in every lane: so is the number of barriers)
         int lo, hi;
-        ngram_range(a, q, lo, hi);
+        trie_range(a.child_off, a.E, q, lo, hi);
         for (int k = lo + tid; k < hi; k += 256) {
             const int v = a.child_tok[k];
             if (v >= 0 && v < V && !mark[v]) {                          // (a node's child tokens are distinct: one lane per byte)
@@ -104,21 +96,16 @@ extern "C" int las_ngram_step(const int* child_off, const int* child_tok, const 
                               int order, float* scores, int nutt, int beam, int V, const float* state_in, float* state_out,
                               int state_width, const int* token, const int* step, const int* nlive, const int* done,
                               const int* dec_step, int Umax, void* stream) {
-    LAS_ARG(child_off && bow && bo && uni_lp && uni_next && scores && state_in && state_out && token && step && nlive && done && dec_step,
-            "las_ngram_step: null pointer");
-    LAS_ARG(nchild >= 0 && (nchild == 0 || (child_tok && child_lp && child_next)), "las_ngram_step: %d children but no child tables", nchild);
-    LAS_ARG(nutt > 0 && beam > 0 && Umax > 0 && (long long)nutt * beam <= 0x7fffffffLL, "las_ngram_step: bad dims");
-    LAS_ARG(V > 1 && V <= NGRAM_MAX_V, "las_ngram_step: 1 < V <= %d (got %d)", NGRAM_MAX_V, V);
-    LAS_ARG(nnodes >= 1 && nnodes <= NGRAM_MAX_NODES, "las_ngram_step: 1 <= nodes <= %d (got %d)", NGRAM_MAX_NODES, nnodes);
-    LAS_ARG(order >= 1 && order <= NGRAM_MAX_ORDER, "las_ngram_step: 1 <= order <= %d (got %d)", NGRAM_MAX_ORDER, order);
-    LAS_ARG(state_width >= 1, "las_ngram_step: state_width %d < 1", state_width);
-    LAS_ARG(state_in != state_out, "las_ngram_step: state_in and state_out must differ");
     NgramDev a;
+    if (search_rows_args(a, "las_ngram_step", 1, nutt, beam, state_in, state_out, state_width,
+                         token, step, nlive, done, dec_step, Umax)) return -1;
+    LAS_ARG(child_off && bow && bo && uni_lp && uni_next && scores && token, "las_ngram_step: null pointer");
+    LAS_ARG(nchild >= 0 && (nchild == 0 || (child_tok && child_lp && child_next)), "las_ngram_step: %d children but no child tables", nchild);
+    LAS_ARG(V > 1 && V <= TRIE_MAX_V, "las_ngram_step: 1 < V <= %d (got %d)", TRIE_MAX_V, V);
+    LAS_ARG(nnodes >= 1 && nnodes <= TRIE_MAX_NODES, "las_ngram_step: 1 <= nodes <= %d (got %d)", TRIE_MAX_NODES, nnodes);
+    LAS_ARG(order >= 1 && order <= NGRAM_MAX_ORDER, "las_ngram_step: 1 <= order <= %d (got %d)", NGRAM_MAX_ORDER, order);
     a.child_off = child_off; a.child_tok = child_tok; a.child_lp = child_lp; a.child_next = child_next; a.bow = bow; a.bo = bo;
-    a.uni_lp = uni_lp; a.uni_next = uni_next; a.M = nnodes; a.E = nchild; a.order = order;
-    a.scores = scores; a.st_in = state_in; a.st_out = state_out; a.token = token; a.step = step;
-    a.nlive = nlive; a.done = done; a.dec_step = dec_step;
-    a.nutt = nutt; a.beam = beam; a.V = V; a.width = state_width; a.Umax = Umax;
+    a.uni_lp = uni_lp; a.uni_next = uni_next; a.M = nnodes; a.E = nchild; a.order = order; a.scores = scores; a.V = V;
     hipLaunchKernelGGL(ngram_step_kernel, dim3(nutt * beam), dim3(256), 0, (hipStream_t)stream, a);
     LAS_LAUNCHED();
     return 0;

@@ -28,8 +28,7 @@ __global__ __launch_bounds__(SCORE_NT) void rescore_score_kernel(const float* __
                                                                  int V, float* __restrict__ terms, int ldt) {
     __shared__ float red[SCORE_NT / 64];
     const int r = blockIdx.x / U, t = blockIdx.x - r * U, tid = threadIdx.x;
-    int L = len[r];
-    L = L < 0 ? 0 : (L > U ? U : L);
+    const int L = clampi(len[r], 0, U);
     if (t >= L) return;
     const float* z = logits + (long long)r * sb + (long long)t * st;
 
@@ -56,19 +55,11 @@ __global__ __launch_bounds__(SCORE_NT) void rescore_score_kernel(const float* __
     if (tid == 0) terms[(size_t)r * ldt + t] = term;                   // (a label outside [0, V): -inf, nothing read for it)
 }
 
-// one wave per row: the lanes load 64 terms at once, then every lane adds them in step order (a broadcast per term) -- one lane walking
-// the row alone waits a memory round trip per term (17 us for 77 steps, measured: as long as the whole score kernel)
+// one wave per row: its terms in step order in float64
 __global__ __launch_bounds__(SUM_NT) void rescore_sum_kernel(const float* __restrict__ terms, int ldt, const int* __restrict__ len, int U,
                                                              double* __restrict__ att) {
     const int r = blockIdx.x, lane = threadIdx.x;
-    int L = len[r];
-    L = L < 0 ? 0 : (L > U ? U : L);
-    double s = 0.0;
-    for (int base = 0; base < L; base += SUM_NT) {                     // (L is the wave's: uniform control flow around the shuffles)
-        const float x = base + lane < L ? terms[(size_t)r * ldt + base + lane] : 0.f;
-        const int n = L - base < SUM_NT ? L - base : SUM_NT;
-        for (int i = 0; i < n; ++i) s += (double)__shfl(x, i);
-    }
+    const double s = wave_terms_sum_f64(terms + (size_t)r * ldt, clampi(len[r], 0, U), lane);
     if (lane == 0) att[r] = s;
 }
 
@@ -77,8 +68,7 @@ __global__ __launch_bounds__(RANK_MAX_K) void rescore_rank_kernel(const float* _
                                                                   float* __restrict__ total, int* __restrict__ order) {
     __shared__ float tot[RANK_MAX_K];
     const int u = blockIdx.x, k = threadIdx.x;
-    int nh = nhyp[u];
-    nh = nh < 0 ? 0 : (nh > K ? K : nh);
+    const int nh = clampi(nhyp[u], 0, K);
     const size_t base = (size_t)u * K;
     float mine = 0.f;
     if (k < nh) {

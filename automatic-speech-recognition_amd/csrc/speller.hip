@@ -3020,7 +3020,6 @@ __global__ __launch_bounds__(256) void emb_grad_kernel(const int* tok, const flo
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 #include "speller_wide.h"
 
 struct BwdWs {

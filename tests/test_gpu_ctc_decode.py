@@ -27,7 +27,8 @@ def _width(Tp):
     return 4 * ((2 * Tp + 2 + 3) // 4)
 
 
-def _run_step(lp_cm, lens, logits, st_in, tokens, beam, t, lam, end_id=2):
+def _run_step(lp_cm, lens, logits, st_in, tokens, beam, t, lam, end_id=2, nlive=None, done=None, dec_step=None, Umax=1000, fill=0.0):
+    """one launch; by default every row is live (nlive = beam, nothing done, dec_step = Umax = 1000) and st_out starts as zeros (fill)"""
     from las import _hip
     n, Vc, Tp = lp_cm.shape
     V = Vc - 1
@@ -35,9 +36,10 @@ def _run_step(lp_cm, lens, logits, st_in, tokens, beam, t, lam, end_id=2):
     d = lambda x, dt=torch.float32: torch.as_tensor(np.ascontiguousarray(x), dtype=dt).cuda()
     i32 = torch.int32
     joint = torch.full((N, V), 7.0, device="cuda")
-    st_out = torch.zeros(N, _width(Tp), device="cuda")
+    st_out = torch.full((N, _width(Tp)), fill, device="cuda")
     args = [d(lp_cm), d(lens, i32), n, beam, Tp, V, end_id, d(logits), joint, lam, d(st_in), st_out, _width(Tp), d(tokens, i32),
-            d([t, 0], i32), d([beam] * n, i32), d([0] * n, i32), d([1000] * n, i32), 1000]
+            d([t, 0], i32), d([beam] * n if nlive is None else nlive, i32), d([0] * n if done is None else done, i32),
+            d([1000] * n if dec_step is None else dec_step, i32), Umax]
     ptr = [(_hip.p(a) if torch.is_tensor(a) else a) for a in args]
     _hip.check(_hip.lib().las_ctc_prefix_step(*ptr, _hip.stream()), "las_ctc_prefix_step")
     torch.cuda.synchronize()
@@ -129,6 +131,42 @@ def test_prefix_step_matches_cpu_reference(V, Tp):
                         continue
                     ref = np.float32(logits[r, v]) + np.float32(LAM) * np.float32(ps - h.psi)
                     assert abs(joint[r, v] - ref) <= LAM * 2 * _tol(max(abs(ps), abs(h.psi))) + 1e-5 * abs(ref), (u, j, v, joint[r, v], ref)
+
+
+@pytest.mark.parametrize("V", [30, 70])
+def test_prefix_step_writes_live_rows_only(V):
+    """The liveness rule of the per-step scorers, held directly: a row is written exactly when the pruning will rank it.  A row that is
+    not live (step 0: every slot but 0; t >= Umax; a done utterance; t >= dec_step[u]; slot >= nlive[u]) keeps the sentinel bits in joint
+    and state_out; a live row has the bits of the all-live launch of the same step.  V = 70 takes the top-64 bank kernel, which also
+    writes -inf to its rows"""
+    rng = np.random.RandomState(V)
+    n, beam, Tp = 3, 4, 7
+    N, SENT = n * beam, 7.0                                                # (joint's fill in _run_step; state_out gets the same)
+    lens = [7, 4, 1]
+    lp_cm = np.ascontiguousarray(torch.log_softmax(torch.tensor(rng.randn(n, Tp, V + 1) * 2.0, dtype=torch.float32), -1).numpy()
+                                 .transpose(0, 2, 1))
+    logits = (rng.randn(N, V) * 3.0).astype(np.float32)
+    tokens = rng.randint(3, V, size=N)
+    st_in = np.zeros((N, _width(Tp)), np.float32)
+    st_in[:, :2 * Tp] = -np.abs(rng.randn(N, 2 * Tp)) * 3.0                  # any finite parent state: only the bits are compared
+    st_in[:, 2 * Tp], st_in[:, 2 * Tp + 1] = -1.0, rng.randint(3, V, size=N)
+    run = lambda t, **kw: _run_step(lp_cm, lens, logits, st_in, tokens, beam, t, LAM, fill=SENT, **kw)
+    bits = lambda x: x.view(np.int32)
+    full = {t: run(t) for t in (0, 1)}
+    slot = np.tile(np.arange(beam), n)
+    utt = np.repeat(np.arange(n), beam)
+    assert not np.any(full[1][0] == SENT) and not np.any(full[1][1][:, 2 * Tp] == SENT)      # all-live: every row written
+    cases = [(0, {}, slot == 0),
+             (1, dict(nlive=[4, 2, 0]), slot < np.repeat([4, 2, 0], beam)),
+             (1, dict(done=[0, 1, 0]), utt != 1),
+             (1, dict(dec_step=[1000, 1, 2]), utt != 1),
+             (1, dict(Umax=1), np.zeros(N, bool))]
+    for t, kw, live in cases:
+        joint, st_out = run(t, **kw)
+        assert np.all(bits(joint[~live]) == bits(np.float32(SENT))) and np.all(bits(st_out[~live]) == bits(np.float32(SENT))), (t, kw)
+        assert np.array_equal(bits(joint[live]), bits(full[t][0][live])) and np.array_equal(bits(st_out[live]), bits(full[t][1][live])), (t, kw)
+        if live.any():
+            assert not np.any(joint[live] == SENT) and not np.any(st_out[live][:, 2 * Tp] == SENT), (t, kw)
 
 
 def test_log_softmax_is_class_major():
