@@ -266,10 +266,17 @@ _SIGS = {
     "las_noise_mix": (c_int, [c_void_p, c_longlong, c_void_p, POINTER(c_int), c_int, c_void_p, c_longlong, c_void_p, POINTER(c_int), c_int,
                               c_void_p, POINTER(c_int), c_void_p, POINTER(c_int), c_void_p, POINTER(c_float),
                               c_void_p, c_longlong, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "las_bic_candidates": (c_longlong, [c_longlong, c_int, c_int]),
+    "las_bic_change": (c_int, [c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int), c_int,
+                               c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    "las_bic_cluster_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "las_bic_cluster": (c_int, [c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int),
+                                POINTER(c_int), c_int, POINTER(c_int), c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 
-ABI_VERSION = 608      # include/las_hip.h LAS_HIP_ABI_VERSION
+ABI_VERSION = 609      # include/las_hip.h LAS_HIP_ABI_VERSION
 
 
 def declared_symbols():

@@ -26,6 +26,18 @@ def add_flags(parser):
     parser.add_argument("--keyword_max_hits", type=int, default=4, help="Hits kept per file and phrase, the strongest (1 to 8).")
 
 
+def add_diarize_flags(parser):
+    """the --diarize flags (las.diarize.add_flags; kept here so that a run without --diarize never imports las.diarize)"""
+    parser.add_argument("--diarize", type=str2bool, default=False, help="Label every segment with its speaker (needs --segment True; JSON "
+                        "lines): BIC change points inside the speech runs and BIC clustering of the pieces, no trained model.")
+    parser.add_argument("--num_speakers", type=int, default=0, help="Cluster down to this many speakers; 0 = stop when no merge lowers the BIC.")
+    parser.add_argument("--diar_window_ms", type=float, default=1000.0, help="Each of the two adjacent windows of the change-point curve.")
+    parser.add_argument("--diar_hop_ms", type=float, default=100.0, help="Distance between change-point candidates.")
+    parser.add_argument("--diar_change_lambda", type=float, default=1.0, help="BIC penalty weight of the change points (larger: fewer).")
+    parser.add_argument("--diar_cluster_lambda", type=float, default=1.0, help="BIC penalty weight of the clustering (larger: fewer speakers).")
+    parser.add_argument("--rttm", type=str, default="", metavar="FILE", help="Also write the labelled segments in RTTM, one line each.")
+
+
 def refuse(rows, message):
     for flag, on, why in rows:
         if on:
@@ -39,6 +51,17 @@ def check_flags(args, parser):
     network = check_confusion_flags(args)
     consensus = bool(args.nbest or args.confidence or args.mbr or network)
     kind = "keywords" if args.keywords is not None else "align" if args.align_text is not None else "search"
+    diarize = bool(getattr(args, "diarize", False))
+    if diarize:                                                        # (las.diarize is imported only when the flag is given)
+        refuse((("--keywords", kind == "keywords", "prints keyword hits and runs no search"),
+                ("--align_text", args.align_text is not None, "aligns one transcript per whole file")),
+               "--diarize labels the segments a search transcribes, %s %s: use one of them")
+        if not args.segment:
+            raise ValueError("--diarize labels the segments of --segment True: give both")
+        from las import diarize as DZ
+        DZ.check_values(args.num_speakers, args.diar_window_ms, args.diar_hop_ms, args.diar_change_lambda, args.diar_cluster_lambda)
+    elif getattr(args, "rttm", ""):
+        raise ValueError("--rttm writes the speakers of --diarize True: give both")
     keywords = (("--align_text", args.align_text is not None, "aligns a given transcript"),
                 ("--segment", args.segment, "cuts the recordings first; searching the segments is not built"),
                 ("--timestamps", args.timestamps, "times the search's hypothesis"),
@@ -76,7 +99,7 @@ def check_flags(args, parser):
     if not args.cmvn:
         raise ValueError("the Listener takes the CMVN'd cube [T, feat_dim, 3]: transcribe with --cmvn True")
     report = cover is not None and cover.report                        # (--coverage_report prints the counts: JSON lines)
-    return Mode(kind, ctc_only, consensus, kind != "search" or bool(args.timestamps) or consensus or report)
+    return Mode(kind, ctc_only, consensus, kind != "search" or bool(args.timestamps) or consensus or report or diarize)
 
 
 def load_lm(init_dir, store=None):

@@ -18,7 +18,7 @@ def choose(args, bs, ann, results, id_to_token):
         token_lists = [list(r[-1].token_ids[1:]) if r else [] for r in results]
         cov = [_coverage_fields(r[-1] if r else None) for r in results]          # ({} unless the coverage scorer ran)
         if not args.timestamps:
-            if getattr(args, "coverage_report", False):                # JSON lines: the search's score and the two shares
+            if getattr(args, "coverage_report", False) or getattr(args, "diarize", False):   # JSON lines: the search's score [and the two shares]
                 return [(tokens, float(r[-1].log_prob) if r else None, None, c) for tokens, r, c in zip(token_lists, results, cov)]
             return [(tokens, None, None, None) for tokens in token_lists]
         return [(tokens, score, span, c) for tokens, score, span, c in zip(token_lists, *bs.align_results(results, token_lists), cov)]
@@ -105,24 +105,31 @@ class FileAssembler(object):
 
     def __init__(self, make, as_json, words=False, confidence=False, network=False):
         self.make, self.as_json, self.words, self.confidence, self.network = make, as_json, words or confidence, confidence, network
-        self.files = collections.deque()                               # [segments (start s, end s) of a file, its records so far]
+        self.files = collections.deque()                               # [segments (start s, end s) of a file, its records so far, speakers]
 
-    def add_file(self, ranges, fs):                                    # (sample ranges at fs Hz; before their results arrive; -> ranges)
-        self.files.append(([(s0 / float(fs), s1 / float(fs)) for s0, s1 in ranges], []))
+    def add_file(self, ranges, fs, speakers=None):                     # (sample ranges at fs Hz; before their results arrive; -> ranges)
+        """speakers (--diarize): (the 1-based speaker of every range, the file's number of speakers) -- every segment record and
+        every word object then carry "speaker", the file's line "speakers" """
+        self.files.append(([(s0 / float(fs), s1 / float(fs)) for s0, s1 in ranges], [], speakers))
         return ranges
 
     def take(self, tokens, score, span, extra):
         self.emit_finished()                                           # (silent files in front of this segment's file)
-        spans, done = self.files[0]                                    # results arrive in stream order: the first unfinished file
+        spans, done, speakers = self.files[0]                          # results arrive in stream order: the first unfinished file
         t0, t1 = spans[len(done)]
-        done.append(self.make(tokens, score, span, extra, t1 - t0, (t0, t1)))
+        d = self.make(tokens, score, span, extra, t1 - t0, (t0, t1))
+        if speakers is not None:
+            d["speaker"] = speakers[0][len(done)]
+            for w in d.get("words", []):
+                w["speaker"] = d["speaker"]
+        done.append(d)
         self.emit_finished()
 
     def emit_finished(self):
         """a finished file's line: the texts joined by one space; as JSON the summed score (None if one is None), [the least
         confidence], [the words], [the network's bins] in order, and the segments' own records"""
         while self.files and len(self.files[0][1]) == len(self.files[0][0]):
-            spans, done = self.files.popleft()
+            spans, done, speakers = self.files.popleft()
             text = " ".join(d["text"] for d in done)
             if not self.as_json:
                 print(text)
@@ -136,6 +143,8 @@ class FileAssembler(object):
                 line["words"] = [w for d in done for w in d["words"]]
             if self.network:
                 line["network"] = [b for d in done for b in d["network"]]
+            if speakers is not None:
+                line["speakers"] = speakers[1]
             line["segments"] = done
             print(json.dumps(line))
 

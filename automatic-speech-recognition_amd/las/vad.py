@@ -67,6 +67,7 @@ class VoiceActivity:
         self.min_run = max(2, int(math.ceil(self.min_speech_ms / self.frame_step)))
         self.device = device
         self.energies = []                    # of the last runs() call: per recording None, or its frame energies when asked for
+        self.kept = []                        # of the last runs(keep=True) call: per recording (energies, peak) on the device
 
     def geometry(self, rate):
         fl, step = frame_geometry(int(rate), self.frame_length, self.frame_step)
@@ -83,12 +84,13 @@ class VoiceActivity:
         fl, step = self.geometry(rate)
         return max(4, int((self.max_segment_s * int(rate) - fl) // step) + 1)
 
-    def runs(self, waves, rate, energy_over=None):
+    def runs(self, waves, rate, energy_over=None, keep=False):
         """waves: list of 1-D float or int16 arrays; rate: a scalar or one sample rate per recording.  -> per recording an int array
         [k, 2] of runs [a, b) in frames of ITS rate's geometry (so a run means the same milliseconds at any rate).  One upload and
         one las_vad call per group of recordings at one sample rate; one wait for the counts and the runs.  energy_over: a frame
         count (or a function of the rate) -- the energies of a recording with a run longer than that are read back into
-        self.energies (the planner cuts such runs); nothing else leaves the device."""
+        self.energies (the planner cuts such runs); nothing else leaves the device.  keep: every recording's energies and peak stay
+        on the device in self.kept, for speech_mask."""
         dev = torch.device(self.device if self.device is not None else "cuda")
         if dev.type != "cuda":
             raise RuntimeError("las.vad needs a ROCm device (got %s); there is no CPU fallback" % dev)
@@ -102,6 +104,7 @@ class VoiceActivity:
         rates = [int(r) for r in np.broadcast_to(np.asarray(rate), (len(ws_np),))]
         out = [None] * len(ws_np)
         self.energies = [None] * len(ws_np)
+        self.kept = [None] * len(ws_np)
         lib = _hip.lib()
         with torch.cuda.device(dev):
             for fs in sorted(set(rates)):
@@ -124,20 +127,32 @@ class VoiceActivity:
                 d_runs = torch.empty((n, max_runs, 2), dtype=torch.int32, device=dev)
                 d_count = torch.empty(n, dtype=torch.int32, device=dev)
                 d_energy = torch.empty((n, Tmax), dtype=torch.float64, device=dev)
+                d_emax = torch.empty(n, dtype=torch.float64, device=dev) if keep else None
                 need = int(lib.las_vad_workspace_bytes(n, Tmax))
                 ws = _hip.workspace(dev, need, _hip._tag("vad"))
                 ns_host = (ctypes.c_int * n)(*ns)
                 _hip.check(lib.las_vad(_hip.p(d_rows), int(i16), ld, _hip.p(d_ns), ns_host, n, Tmax, fl, step, self.ratio, self.floor(fl),
-                                       self.hang, self.min_run, _hip.p(d_energy), None, _hip.p(d_runs), max_runs, _hip.p(d_count),
+                                       self.hang, self.min_run, _hip.p(d_energy), _hip.p(d_emax), _hip.p(d_runs), max_runs, _hip.p(d_count),
                                        _hip.p(ws), ws.numel(), _hip.stream()), "las_vad")
                 counts = d_count.cpu().numpy()
                 got = d_runs[:, :max(1, int(counts.max()))].cpu().numpy()
                 limit = energy_over(fs) if callable(energy_over) else energy_over
                 for k, u in enumerate(idx):
                     out[u] = got[k, :counts[k]].copy()
+                    if keep:
+                        self.kept[u] = (d_energy[k, :Ts[k]], d_emax[k], self.floor(fl))
                     if limit is not None and len(out[u]) and int((out[u][:, 1] - out[u][:, 0]).max()) > int(limit):
                         self.energies[u] = d_energy[k, :Ts[k]].cpu().numpy()
         return out
+
+    def speech_mask(self, u):
+        """recording u of the last runs(keep=True) call -> a bool device tensor over its frames: las_vad's raw frames, energy >= max(peak
+        x ratio, floor) and > 0 (the runs are these frames padded and joined); computed on the device, nothing is read back"""
+        if u >= len(self.kept) or self.kept[u] is None:
+            raise RuntimeError("speech_mask(%d): the last runs() call kept nothing on the device (keep=True)" % u)
+        e, emax, floor = self.kept[u]
+        thr = torch.clamp(emax * self.ratio, min=floor)                    # (one double multiply, as the kernel's)
+        return (e >= thr) & (e > 0)
 
     def segments_batch(self, waves, rate):
         """per recording [(s0, s1)] sample ranges: segment [a, b) in frames covers samples [a step, min((b - 1) step + fl, n))"""

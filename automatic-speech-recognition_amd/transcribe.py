@@ -15,6 +15,7 @@
     python transcribe.py --ctc True --keywords names.txt a.wav ...     (keyword search: where the CTC head hears a listed phrase, no search)
     python transcribe.py --coverage_report True a.wav ...              (JSON lines with the shares of attended / over-attended encoder frames)
     python transcribe.py --coverage_weight 0.3 --overattend_weight 0.7 a.wav ...   (attention coverage scored in the beam search)
+    python transcribe.py --segment True --diarize True meeting.wav ...  (who spoke when: every segment labelled with its speaker)
 
 With --timestamps the best hypothesis is aligned to the encoder frames by the CTC head (las.align, csrc/ctc_align.hip: a Viterbi pass
 over the head's log-probabilities) and every line is {"text", "score", "words": [{"word", "start", "end"}]}: times in seconds, None when
@@ -65,6 +66,16 @@ rises above --overattend_threshold; plain text stays plain text, and every JSON 
 pass' attention score.  --keywords, --align_text and --decoder ctc without --rescore attention run no attention decoder and refuse
 the flags; --cn_decode prints a text no search produced and carries no coverage fields.
 
+With --segment True --diarize True (las.diarize, csrc/diarize.hip; JSON lines) every speech run of the detector is split where
+the speaker changes -- the peaks of the delta-BIC curve between two adjacent windows of --diar_window_ms, every --diar_hop_ms, full-
+covariance Gaussians over the 13 static MFCCs of the detector's speech frames, penalty weight --diar_change_lambda -- and the pieces of
+a file are clustered agglomeratively under the same criterion (--diar_cluster_lambda) until no merge lowers the BIC, or down to
+--num_speakers.  The pieces then go through the --max_segment_s cut as runs do.  Every segment record gains "speaker" (1, 2, ... in the
+order of first appearance), the file's line "speakers" (the count), and with --timestamps / --confidence every word object "speaker";
+--rttm FILE also writes `SPEAKER <file stem> 1 <start> <duration> <NA> <NA> S<k> <NA> <NA>` per segment.  No trained model is involved
+and nobody has measured a diarization error rate for the defaults; overlapped speech is not handled.  --diarize needs --segment and
+cannot be combined with --keywords or --align_text.  Without it las.diarize is not imported and the output is what it was.
+
 The files are read with preprocess.read_audio (.flac needs `soundfile`), `--decode_batch` of them at a time go through the device front
 end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip; a file at another rate than --sample_rate is resampled
 on the device first, csrc/resample.hip) and stay on the device for BeamSearch.decode_batches:
@@ -83,7 +94,7 @@ from las import align as A                                         # noqa: E402
 from las import transcript as T                                    # noqa: E402
 from las import vad as VAD                                         # noqa: E402
 from las.arguments import build_parser, str2bool                   # noqa: E402
-from las.cli import add_flags, build_search, check_flags, encoded_batches, make_tokenizer   # noqa: E402
+from las.cli import add_diarize_flags, add_flags, build_search, check_flags, encoded_batches, make_tokenizer   # noqa: E402
 from las.frontend import FeatureExtractor                          # noqa: E402
 from preprocess import read_audio                                  # noqa: E402
 
@@ -99,6 +110,7 @@ def main(argv=None):
     parser = build_parser()
     add_flags(parser)
     VAD.add_flags(parser, str2bool)
+    add_diarize_flags(parser)
     args = parser.parse_args(argv)
     mode = check_flags(args, parser)
     logging.basicConfig(stream=sys.stderr, format='%(asctime)s %(levelname)s:%(message)s', level=logging.INFO, datefmt='%I:%M:%S')
@@ -160,6 +172,15 @@ def main(argv=None):
         va = VAD.VoiceActivity(args, device=dev)
         files = T.FileAssembler(record, mode.json, args.timestamps, ann is not None and ann.confidence, ann is not None and ann.cn)
         cut, sink = lambda audio, fs: files.add_file(va.segments(audio, fs), fs), files.take     # (one las_vad call and one wait per file)
+        if args.diarize:                                               # (las.diarize is imported only when the flag is given)
+            from las import diarize as DZ
+            dz, rttm = DZ.Diarizer(args, device=dev), []
+
+            def cut(audio, fs):                                        # las_vad, las_bic_change and las_bic_cluster: three waits per file
+                ranges, speakers, count = dz.segments(va, audio, fs)
+                stem = os.path.splitext(os.path.basename(args.audio[len(durations) - 1]))[0] if waves is None else "synthetic%d" % (len(durations) - 1)
+                rttm.extend(DZ.rttm_line(stem, s0 / float(fs), (s1 - s0) / float(fs), k) for (s0, s1), k in zip(ranges, speakers))
+                return files.add_file(ranges, fs, speakers=(speakers, count))
     else:
         def cut(audio, fs):
             return [(0, len(audio))]
@@ -187,6 +208,9 @@ def main(argv=None):
             done += len(encs)
             for tokens, score, span in zip(token_lists, *bs.align(encs, enc_lens, token_lists, h_one=h_one, ctc_lp=ctc_lp)):
                 sink(tokens, score, span, {})
+    if args.segment and args.diarize and args.rttm:
+        with open(args.rttm, "w") as f:
+            f.write("".join(line + "\n" for line in rttm))
     sys.stdout.flush()
 
 

@@ -37,7 +37,7 @@ enum { LAS_ACT_NONE = 0, LAS_ACT_TANH = 1 };
 enum { LAS_ATT_ADD = 0, LAS_ATT_LOC = 1 };      /* las/las.py:44-49 */
 enum { LAS_DT_F32 = 0, LAS_DT_BF16 = 1 };       /* element type of a tensor in HBM (see las_gemm_kk) */
 
-#define LAS_HIP_ABI_VERSION 608      /* bumped whenever an argument struct or a signature changes: las_version() of a library
+#define LAS_HIP_ABI_VERSION 609      /* bumped whenever an argument struct or a signature changes: las_version() of a library
                                         built from another header differs, and the Python loader refuses it */
 int         las_version(void);
 const char* las_last_error(void);
@@ -1216,6 +1216,64 @@ int    las_noise_mix(const float* in, long long ld_in, const int* n_in, const in
                      const int* noise_idx, const int* noise_idx_host, const int* noise_off, const int* noise_off_host,
                      const float* snr_db, const float* snr_db_host,
                      float* out, long long ld_out, float* gain_out, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K17  speaker diarization of long recordings without a trained model: the Bayesian information criterion between
+ * full-covariance Gaussians (Chen & Gopalakrishnan 1998) finds the speaker changes inside a run of speech (las_bic_change) and
+ * drives the agglomerative clustering of the pieces (las_bic_cluster).  Plain arguments, no struct (as las_vad).  All reals are
+ * doubles unless stated.  Every pointer but the *_host ones is a device pointer; a *_host array holds the same values on the host
+ * and is what the entry validates.
+ *   inputs     feat fp32 [N, ld], a row = a frame, the first D columns are used (1 <= D <= LAS_BIC_MAX_DIM = 20); mask uint8 [N] or
+ *              NULL (= all ones); S sequences, sequence s = the rows [seq_off[s], seq_off[s] + seq_len[s]).  Only rows inside a
+ *              listed sequence are read, and of those only the columns < D.
+ *   statistics of a set F of frames, over its frames with mask != 0 only: n = their number, S1 = sum x, S2 = sum x x^T, every fp32 x
+ *              widened to double first (a product is exact; every sum runs in frame order);
+ *              Sigma(F) = (S2 - S1 S1^T / n) / n + floor I;  L(F) = log det Sigma(F), by Cholesky.  floor > 0 keeps digital silence
+ *              and constant frames from giving a singular matrix.  The statistics of a union are the sums of its parts'.
+ *   dBIC(X, Y; lambda) = 1/2 [n L(X u Y) - n1 L(X) - n2 L(Y)] - lambda 1/2 (D + D (D + 1) / 2) log n,  n = n1 + n2
+ *
+ * las_bic_change   w >= 2, hop >= 1, nmin >= 1.  Sequence s has C_s = las_bic_candidates(seq_len[s], w, hop) candidates (0 when the
+ *   sequence is shorter than 2 w, else (len - 2 w) / hop + 1; < 0: bad arguments), candidate c at the local frame t = w + c hop:
+ *   v[c] = dBIC([t - w, t), [t, t + w); lambda), -inf when either window holds fewer than nmin masked frames.  With R = ceil(w / hop),
+ *   c is a change point iff v[c] > 0, v[c] > v[c'] for every existing c' in [c - R, c) and v[c] >= v[c'] for every existing c' in
+ *   (c, c + R]: the first of equal maxima wins, two change points are more than w frames apart.  cand_off int32 [S + 1] is the
+ *   exclusive prefix of the C_s (the caller computes it); v fp64 and peak uint8 hold cand_off[S] entries, sequence s's from
+ *   cand_off[s]; nothing behind the last candidate is written.  Two launches (none when there is no candidate), no workspace.
+ *   Refused on the host before anything is launched (< 0, las_last_error): a NULL feat / seq_off / cand_off / seq_off_host /
+ *   seq_len_host / v / peak; D outside 1..20; N < 1; ld < D; S < 1; a sequence outside [0, N); w < 2, hop < 1, nmin < 1; lambda or
+ *   floor not finite, floor < 0; more than INT32_MAX candidates.
+ *
+ * las_bic_cluster  one problem per recording: recording r owns the units (sequences, as above) [rec_off[r], rec_off[r + 1]), S_r of
+ *   them, 1 <= S_r <= LAS_BIC_MAX_UNITS; indices i, j below count inside the recording.  d(i, j) = dBIC of the two units' statistics
+ *   with lambda.  Loop over the live units: take the pair i < j of least d (ties: the smallest i, then the smallest j); stop when one
+ *   unit is left, when K > 0 and at most K are live (the sign of d is ignored), or when K = 0 and d >= 0; else add j's statistics
+ *   to i's, retire j and recompute d(i, .).  Outputs: label int32 [S], the clusters of a recording numbered from 0 in the order of
+ *   their earliest unit; n_clusters int32 [n_rec]; optionally dist fp64 [S, ldd], ldd = max_r S_r: dist[s, j] = the INITIAL d(i, j) of
+ *   unit s = rec_off[r] + i for i < j < S_r (nothing else is written); optionally merges int32 [S, 2] and merge_val fp64 [S] (both or
+ *   neither) and n_merges int32 [n_rec]: recording r's m-th merge (i, j) and its d at row rec_off[r] - r + m.
+ *   Every unit needs a masked frame: n_masked_host int32 [S] states the units' masked frame counts on the host (NULL allowed iff mask
+ *   is NULL); the kernels count for themselves.  Three launches (statistics, pairs, one workgroup per recording for the loop), no
+ *   atomics.  ws >= las_bic_cluster_workspace_bytes(S, max_r S_r, D) (0: bad arguments), 8-byte aligned.
+ *   Refused on the host before anything is launched: a NULL feat / seq_off / seq_len / rec_off / *_host / label / n_clusters / ws; a
+ *   mask without n_masked_host; merges without merge_val or the reverse; D, N, ld, S, lambda, floor as above; an empty sequence or
+ *   one outside [0, N); n_rec outside 1..S; K < 0; rec_off_host not running from 0 to S; S_r outside 1..LAS_BIC_MAX_UNITS; a unit
+ *   without a masked frame; a workspace that is too small.
+ * Both: a sequence gives the bits it gives alone, whatever else the call holds, and two calls give the same bits.
+ */
+#define LAS_BIC_MAX_DIM 20
+#define LAS_BIC_MAX_UNITS 1024
+long long las_bic_candidates(long long len, int w, int hop);
+int       las_bic_change(const float* feat, long long N, long long ld, int D, const unsigned char* mask,
+                         const int* seq_off, const int* cand_off, const int* seq_off_host, const int* seq_len_host, int S,
+                         int w, int hop, int nmin, double lambda, double floor,
+                         double* v, unsigned char* peak, void* stream);
+size_t    las_bic_cluster_workspace_bytes(int S, int Smax, int D);
+int       las_bic_cluster(const float* feat, long long N, long long ld, int D, const unsigned char* mask,
+                          const int* seq_off, const int* seq_len, const int* rec_off,
+                          const int* seq_off_host, const int* seq_len_host, const int* n_masked_host, int S,
+                          const int* rec_off_host, int n_rec, int K, double lambda, double floor,
+                          int* label, int* n_clusters, double* dist, int* merges, double* merge_val, int* n_merges,
+                          void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
