@@ -273,10 +273,16 @@ _SIGS = {
     "las_bic_cluster": (c_int, [c_void_p, c_longlong, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int),
                                 POINTER(c_int), c_int, POINTER(c_int), c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "las_bf_windows": (c_longlong, [c_longlong, c_int]),
+    "las_bf_workspace_bytes": (c_size_t, [c_int, c_longlong, c_int, c_int]),
+    "las_gcc_phat": (c_int, [c_void_p, c_int, c_longlong, c_int, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_size_t, c_void_p]),
+    "las_tdoa_track": (c_int, [c_void_p, c_int, c_longlong, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "las_delay_sum": (c_int, [c_void_p, c_int, c_longlong, c_int, c_longlong, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 
-ABI_VERSION = 609      # include/las_hip.h LAS_HIP_ABI_VERSION
+ABI_VERSION = 610      # include/las_hip.h LAS_HIP_ABI_VERSION
 
 
 def declared_symbols():

@@ -38,6 +38,36 @@ def add_diarize_flags(parser):
     parser.add_argument("--rttm", type=str, default="", metavar="FILE", help="Also write the labelled segments in RTTM, one line each.")
 
 
+BEAMFORM_DEFAULTS = dict(bf_window_ms=500.0, bf_max_delay_ms=10.0, bf_jump_penalty=0.01, bf_ref=0)
+
+
+def add_beamform_flags(parser):
+    """the --beamform flags (kept here so that a run without --beamform never imports las.beamform).  The --bf_*
+    values default to None here -- check_flags refuses one given without --beamform True and fills in BEAMFORM_DEFAULTS with it."""
+    parser.add_argument("--beamform", type=str2bool, default=False, help="Accept multi-channel recordings (microphone arrays): GCC-PHAT delays "
+                        "against --bf_ref per window, tracked over the windows, then delay-and-sum to one channel; no trained model.")
+    parser.add_argument("--bf_window_ms", type=float, default=None, help="The analysis window, every half window (default 500).")
+    parser.add_argument("--bf_max_delay_ms", type=float, default=None, help="The largest delay searched, either way (default 10).")
+    parser.add_argument("--bf_jump_penalty", type=float, default=None, help="Viterbi penalty per sample of lag change per window (default 0.01).")
+    parser.add_argument("--bf_ref", type=int, default=None, help="The reference channel (default 0).")
+    parser.add_argument("--beamform_wav", type=str, default="", metavar="DIR", help="Also write every beamformed file as DIR/<stem>.wav (16-bit).")
+
+
+def check_beamform_flags(args):
+    """--beamform and its values: refusals before any audio is read; the defaults filled in (--bf_ref against a file's channels: at load time)"""
+    given = [k for k in BEAMFORM_DEFAULTS if getattr(args, k, None) is not None]
+    if not getattr(args, "beamform", False):
+        if given or getattr(args, "beamform_wav", ""):
+            raise ValueError("--%s sets the beamformer of --beamform True: give both" % (given[0] if given else "beamform_wav"))
+        return False
+    for k, v in BEAMFORM_DEFAULTS.items():
+        if getattr(args, k, None) is None:
+            setattr(args, k, v)
+    from las import beamform as BF                                     # (las.beamform is imported only when the flag is given)
+    BF.check_values(args.bf_window_ms, args.bf_max_delay_ms, args.bf_jump_penalty, args.bf_ref)
+    return True
+
+
 def refuse(rows, message):
     for flag, on, why in rows:
         if on:
@@ -51,6 +81,7 @@ def check_flags(args, parser):
     network = check_confusion_flags(args)
     consensus = bool(args.nbest or args.confidence or args.mbr or network)
     kind = "keywords" if args.keywords is not None else "align" if args.align_text is not None else "search"
+    check_beamform_flags(args)
     diarize = bool(getattr(args, "diarize", False))
     if diarize:                                                        # (las.diarize is imported only when the flag is given)
         refuse((("--keywords", kind == "keywords", "prints keyword hits and runs no search"),

@@ -16,6 +16,7 @@
     python transcribe.py --coverage_report True a.wav ...              (JSON lines with the shares of attended / over-attended encoder frames)
     python transcribe.py --coverage_weight 0.3 --overattend_weight 0.7 a.wav ...   (attention coverage scored in the beam search)
     python transcribe.py --segment True --diarize True meeting.wav ...  (who spoke when: every segment labelled with its speaker)
+    python transcribe.py --beamform True array.wav ...                 (microphone arrays: delay-and-sum to one channel first)
 
 With --timestamps the best hypothesis is aligned to the encoder frames by the CTC head (las.align, csrc/ctc_align.hip: a Viterbi pass
 over the head's log-probabilities) and every line is {"text", "score", "words": [{"word", "start", "end"}]}: times in seconds, None when
@@ -76,6 +77,17 @@ order of first appearance), the file's line "speakers" (the count), and with --t
 and nobody has measured a diarization error rate for the defaults; overlapped speech is not handled.  --diarize needs --segment and
 cannot be combined with --keywords or --align_text.  Without it las.diarize is not imported and the output is what it was.
 
+With --beamform True (las.beamform, csrc/beamform.hip) a file with two to sixteen channels -- a .wav, or a .npy of shape [n, C] --
+is accepted: at its own sample rate, before anything else sees it, the delay of every channel against the reference channel --bf_ref
+is taken per window of --bf_window_ms (every half window) from the peak of the PHAT-weighted cross-correlation within
+--bf_max_delay_ms, the delays are smoothed over the windows by a Viterbi pass (--bf_jump_penalty per sample of lag per window), and the
+channels are shifted by whole samples, weighted by their coherence with the reference, and summed.  The mono result takes the path of
+any mono file (resampling, --segment, --diarize, --noise_file, --rir_file, the front end, the search); a mono file passes through
+untouched; the output records are what they are without the flag.  --beamform_wav DIR also writes every beamformed file as
+DIR/<stem>.wav, 16-bit at the file's rate.  No trained model is involved, nobody has measured a word error rate with it, and no
+default has been tuned on a real room.  A --bf_* value or --beamform_wav without --beamform True is refused before audio is read;
+without the flag las.beamform is not imported and a multi-channel file is refused as before.
+
 The files are read with preprocess.read_audio (.flac needs `soundfile`), `--decode_batch` of them at a time go through the device front
 end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip; a file at another rate than --sample_rate is resampled
 on the device first, csrc/resample.hip) and stay on the device for BeamSearch.decode_batches:
@@ -94,7 +106,7 @@ from las import align as A                                         # noqa: E402
 from las import transcript as T                                    # noqa: E402
 from las import vad as VAD                                         # noqa: E402
 from las.arguments import build_parser, str2bool                   # noqa: E402
-from las.cli import add_diarize_flags, add_flags, build_search, check_flags, encoded_batches, make_tokenizer   # noqa: E402
+from las.cli import add_beamform_flags, add_diarize_flags, add_flags, build_search, check_flags, encoded_batches, make_tokenizer   # noqa: E402
 from las.frontend import FeatureExtractor                          # noqa: E402
 from preprocess import read_audio                                  # noqa: E402
 
@@ -111,6 +123,7 @@ def main(argv=None):
     add_flags(parser)
     VAD.add_flags(parser, str2bool)
     add_diarize_flags(parser)
+    add_beamform_flags(parser)
     args = parser.parse_args(argv)
     mode = check_flags(args, parser)
     logging.basicConfig(stream=sys.stderr, format='%(asctime)s %(levelname)s:%(message)s', level=logging.INFO, datefmt='%I:%M:%S')
@@ -159,8 +172,19 @@ def main(argv=None):
 
     durations = collections.deque()                                    # seconds per file, in the order of the results
 
+    beamformer = None
+    if args.beamform:                                                  # (las.beamform is imported only when the flag is given)
+        from las import beamform as BF
+        beamformer = BF.Beamformer(args, device=dev)
+        if args.beamform_wav:
+            os.makedirs(args.beamform_wav, exist_ok=True)
+
     def load(i):
         audio, fs = (waves[i], args.sample_rate) if waves is not None else read_audio(args.audio[i])
+        if beamformer is not None and audio.ndim == 2 and audio.shape[1] >= 2:      # one upload, three calls, one read-back per file
+            audio, _ = beamformer.enhance(audio, int(fs))
+            if args.beamform_wav:
+                BF.write_wav(os.path.join(args.beamform_wav, os.path.splitext(os.path.basename(args.audio[i]))[0] + ".wav"), audio, fs)
         if audio.ndim != 1:
             raise ValueError("%s has %d channels: mono recordings only" % (args.audio[i], audio.shape[1]))
         durations.append(len(audio) / float(fs))

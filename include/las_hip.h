@@ -37,7 +37,7 @@ enum { LAS_ACT_NONE = 0, LAS_ACT_TANH = 1 };
 enum { LAS_ATT_ADD = 0, LAS_ATT_LOC = 1 };      /* las/las.py:44-49 */
 enum { LAS_DT_F32 = 0, LAS_DT_BF16 = 1 };       /* element type of a tensor in HBM (see las_gemm_kk) */
 
-#define LAS_HIP_ABI_VERSION 609      /* bumped whenever an argument struct or a signature changes: las_version() of a library
+#define LAS_HIP_ABI_VERSION 610      /* bumped whenever an argument struct or a signature changes: las_version() of a library
                                         built from another header differs, and the Python loader refuses it */
 int         las_version(void);
 const char* las_last_error(void);
@@ -1274,6 +1274,55 @@ int       las_bic_cluster(const float* feat, long long N, long long ld, int D, c
                           const int* rec_off_host, int n_rec, int K, double lambda, double floor,
                           int* label, int* n_clusters, double* dist, int* merges, double* merge_val, int* n_merges,
                           void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K18  microphone arrays: the delays of every channel against a reference channel from the peak of the PHAT-weighted
+ * cross-correlation per window (las_gcc_phat), smoothed over the windows by a Viterbi pass (las_tdoa_track), then the channels
+ * shifted, weighted and summed (las_delay_sum) -- BeamformIt's scheme (Anguera et al. 2007) without its N-best lists.  No trained
+ * model.  Plain arguments, no struct (as las_vad).  One recording per call; every pointer is a device pointer.  All work goes on the
+ * caller's stream, no atomics, no cross-workgroup synchronisation: two calls give the same bits.
+ *   geometry   x [C, ld], int16 (x_i16 != 0; widened as v / 32767, as in las_vad) or fp32; 2 <= C <= LAS_BF_MAX_CHANNELS; n <= ld
+ *              samples per row are read; ref = the reference channel.  Windows of L samples (even) every H = L / 2; the largest lag
+ *              1 <= D <= LAS_BF_MAX_LAG; the FFT length NF a power of two, L + D <= NF <= LAS_BF_MAX_FFT.  Wn = las_bf_windows(n, L) =
+ *              1 if n <= L, else ceil((n - L) / H) + 1 (< 0: bad arguments); window w covers the samples [w H, w H + L), samples at
+ *              or behind n read as 0.  ws >= las_bf_workspace_bytes(C, Wn, NF, D) (0: bad arguments), 8-byte aligned: the tracker's
+ *              back-pointers (int16 [C, Wn, 2 D + 1]) and las_gcc_phat's fp32 copies of its two tables.
+ *
+ * las_gcc_phat   r fp32 [C, Wn, 2 D + 1], column D + tau = lag tau:  X_c = FFT_NF(hann . x_c[window]);
+ *   G_c[k] = X_c[k] conj(X_ref[k]) / max(|X_c[k] conj(X_ref[k])|, 1e-12);  r_c[tau] = Re IFFT_NF(G_c)[tau mod NF], -D <= tau <= D.
+ *   A channel that lags the reference by tau samples (x_c[t] = s[t - tau]) peaks at +tau.  The row of ref is computed like any
+ *   other: 1 at lag 0 where the window has signal.  hann: double [L], hann[i] = 0.5 - 0.5 cos(2 pi (i + 0.5) / L); twiddle: double
+ *   [NF / 2 + 1, 2], (cos, -sin)(2 pi k / NF) -- the caller computes both in double, the call rounds them to fp32 once; the
+ *   transforms run in fp32.  Two launches (the tables; one workgroup per window, which computes the reference spectrum once).
+ *
+ * las_tdoa_track   reads r, writes tau int32 [C, Wn] and a fp32 [C, Wn].  Per channel c != ref, all arithmetic in double on the widened r:
+ *   score[0][s] = r[0][s];  score[w][s] = r[w][s] + max_s' (score[w-1][s'] - gamma |s - s'|), the product and the difference each
+ *   rounded once (never contracted); ties at a back-pointer go to the smaller |s - s'|, then the smaller s'.  The last window takes
+ *   the arg-max of score, ties to the smaller |tau|, then the smaller tau; the path is traced back from there.  tau[ref][w] = 0.
+ *   Weights: q_c[w] = max(0, r_c[w][tau_c[w]]) for c != ref, q_ref[w] = max_{c != ref} q_c[w]; a_c[w] = q_c[w] / sum_c q_c[w], the sum
+ *   in channel order; where the sum is 0 the reference gets 1 and the others 0.  gamma finite, >= 0.  Two launches (one wave per
+ *   channel steps through the windows; the weights).  The kernel picks the two candidate predecessors of a state, one on either
+ *   side, by a prefix and a suffix maximum of score[s'] +- gamma s' and evaluates and compares those two as written above: equal to the
+ *   maximum over all predecessors wherever gamma s' and the sums are exact, within two roundings of it elsewhere.
+ *
+ * las_delay_sum   reads x, tau, a, writes y fp32 [n]:  z_w[t] = sum_c a_c[w] x_c[t + tau_c[w]] in channel order, reads outside [0, n)
+ *   are 0;  p = clamp((t - H) / H, 0, Wn - 1), w0 = floor(p), f = p - w0;  y[t] = (1 - f) z_w0[t] + f z_min(w0 + 1, Wn - 1)[t]: a linear
+ *   cross-fade between window centres, one window alone at both ends.  Integer delays only.  One launch, no workspace.
+ *
+ * Refused on the host before anything is launched (< 0, las_last_error): a NULL pointer; C, L, D, NF, n, ld, ref, Wn, gamma outside the
+ * above; a workspace that is too small or misaligned; las_delay_sum's Wn != las_bf_windows(n, L).
+ */
+#define LAS_BF_MAX_CHANNELS 16
+#define LAS_BF_MAX_FFT 16384
+#define LAS_BF_MAX_LAG 512
+long long las_bf_windows(long long n, int L);
+size_t    las_bf_workspace_bytes(int C, long long Wn, int NF, int D);
+int       las_gcc_phat(const void* x, int x_i16, long long ld, int C, long long n, int ref, int L, int D, int NF,
+                       const double* hann, const double* twiddle, float* r, void* ws, size_t ws_bytes, void* stream);
+int       las_tdoa_track(const float* r, int C, long long Wn, int D, int ref, double gamma, int* tau, float* a,
+                         void* ws, size_t ws_bytes, void* stream);
+int       las_delay_sum(const void* x, int x_i16, long long ld, int C, long long n, int L, long long Wn,
+                        const int* tau, const float* a, float* y, void* stream);
 
 #ifdef __cplusplus
 }
