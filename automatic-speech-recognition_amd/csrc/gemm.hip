@@ -756,31 +756,20 @@ static bool g_tn_tr_on = true;
 extern "C" void las_dev_gemm_tn_tr(int on) { g_tn_tr_on = on != 0; }       // development switch (A/B measurements)
 #endif
 
-// Grid of a kernel that finds its tile with gemm_tile, and g.zgroup: nx x ny tiles, zdim k-chunks / batch entries.
-static dim3 gemm_grid(GemmArgs& g, int nx, int ny, int zdim, bool row_order) {
-    g.zgroup = 0;
-    if (zdim > 1 && nx * ny <= 64) {                      // few tiles per k-chunk / batch entry: group them per XCD, entries padded to 8
-        g.zgroup = zdim;
-        return dim3(nx * ny * ((zdim + 7) / 8 * 8), 1, 1);
-    }
-    if (row_order && ny >= 64 && zdim == 1) return dim3(nx * ((ny + 7) / 8 * 8), 1, 1);   // tall output: row blocks padded to 8, XCD-aware order
-    return dim3(nx, ny, zdim);
-}
-
+// Launch of the branch-free bf16 kernel the plan chose (gemm_plan below: tile, loader bits, operand type and grid are its decisions).
 template <int WM, int WN, int TM, int TN, typename TI>
-static void launch_fast_t(GemmArgs& g, int zdim, hipStream_t st) {
-    constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-    const dim3 grid = gemm_grid(g, cdiv(g.N, BN), cdiv(g.M, BM), zdim, true), blk(WM * WN * 64);
-    const bool akc = g.ksA == 1, bkc = g.ksB == 1;
+static void launch_fast_t(const GemmArgs& g, int loader, dim3 grid, hipStream_t st) {
+    const dim3 blk(WM * WN * 64);
+    const bool akc = loader & 1, bkc = loader & 2;
     if (akc && bkc)       hipLaunchKernelGGL((gemm_bf16_fast_kernel<WM, WN, TM, TN, true, true, TI>), grid, blk, 0, st, g);
     else if (akc && !bkc) hipLaunchKernelGGL((gemm_bf16_fast_kernel<WM, WN, TM, TN, true, false, TI>), grid, blk, 0, st, g);
     else if (!akc && bkc) hipLaunchKernelGGL((gemm_bf16_fast_kernel<WM, WN, TM, TN, false, true, TI>), grid, blk, 0, st, g);
     else                  hipLaunchKernelGGL((gemm_bf16_fast_kernel<WM, WN, TM, TN, false, false, TI>), grid, blk, 0, st, g);
 }
 template <int WM, int WN, int TM, int TN>
-static void launch_fast(GemmArgs& g, int zdim, hipStream_t st) {
-    if (g.in_bf16) launch_fast_t<WM, WN, TM, TN, unsigned short>(g, zdim, st);
-    else           launch_fast_t<WM, WN, TM, TN, float>(g, zdim, st);
+static void launch_fast(const GemmArgs& g, int loader, dim3 grid, hipStream_t st) {
+    if (g.in_bf16) launch_fast_t<WM, WN, TM, TN, unsigned short>(g, loader, grid, st);
+    else           launch_fast_t<WM, WN, TM, TN, float>(g, loader, grid, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1042,9 +1031,7 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmArgs g) {
 }
 
 template <int WM, int WN, int TM, int TN>
-static void launch_bf16(const GemmArgs& g, int zdim, hipStream_t st) {
-    constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-    dim3 grid(cdiv(g.N, BN), cdiv(g.M, BM), zdim);
+static void launch_bf16(const GemmArgs& g, dim3 grid, hipStream_t st) {
     hipLaunchKernelGGL((gemm_bf16_kernel<WM, WN, TM, TN>), grid, dim3(WM * WN * 64), 0, st, g);
 }
 
@@ -1122,6 +1109,106 @@ extern "C" size_t las_gemm_workspace_bytes(int prec, int M, int N, int K, int ba
     return need < LAS_GEMM_WS_CAP ? need : LAS_GEMM_WS_CAP;
 }
 
+// Every decision of a las_gemm_dt call, made ONCE for the launch and for the query las_gemm_plan (include/las_hip.h: the public part is
+// las_gemm_plan_info): the kernel family, its tile, loader and operand type, the split (gemm_split) and the grid with its order.
+// las_gemm_dt launches from this struct and decides nothing itself.  Pure host arithmetic: the operands enter as their addresses mod 16.
+struct GemmPlan {
+    las_gemm_plan_info info;
+    int vecA, vecB;                                // 4-element vector loads legal (GemmArgs)
+    int zgroup;                                    // GemmArgs::zgroup of a z-grouped grid, else 0
+};
+
+// Grid of a kernel that finds its tile with gemm_tile: nx x ny tiles, zdim k-chunks / batch entries.
+static void gemm_plan_grid(GemmPlan* p, int nx, int ny, int zdim, bool row_order) {
+    las_gemm_plan_info& pi = p->info;
+    p->zgroup = 0;
+    if (zdim > 1 && nx * ny <= 64) {                      // few tiles per k-chunk / batch entry: group them per XCD, entries padded to 8
+        p->zgroup = zdim;
+        pi.grid_order = 1; pi.grid_x = nx * ny * ((zdim + 7) / 8 * 8); pi.grid_y = 1; pi.grid_z = 1;
+    } else if (row_order && ny >= 64 && zdim == 1) {      // tall output: row blocks padded to 8, XCD-aware order
+        pi.grid_order = 2; pi.grid_x = nx * ((ny + 7) / 8 * 8); pi.grid_y = 1; pi.grid_z = 1;
+    } else {
+        pi.grid_order = 0; pi.grid_x = nx; pi.grid_y = ny; pi.grid_z = zdim;
+    }
+}
+
+static int gemm_plan(int prec, int transA, int transB, int M, int N, int K, int lda, long long strideA, int ldb, long long strideB,
+                     int in_dtype, int batch, int a_mask_period, unsigned a_align, unsigned b_align, size_t ws_bytes, GemmPlan* p) {
+    LAS_ARG(in_dtype == LAS_DT_F32 || (in_dtype == LAS_DT_BF16 && prec == LAS_PREC_BF16), "las_gemm: bf16 operands need LAS_PREC_BF16");
+    LAS_ARG(prec == LAS_PREC_F32 || prec == LAS_PREC_BF16, "las_gemm: bad prec %d", prec);
+    LAS_ARG(M >= 0 && N >= 0 && K >= 0 && batch >= 1, "las_gemm: bad dims M=%d N=%d K=%d batch=%d", M, N, K, batch);
+    LAS_ARG(lda >= (transA ? M : K) && ldb >= (transB ? K : N), "las_gemm: leading dimension too small");
+    LAS_ARG(a_mask_period == 0 || transA == 1, "las_gemm: a_mask_period needs transA=1");
+    *p = GemmPlan();
+    las_gemm_plan_info& pi = p->info;
+    pi.kernel = LAS_GEMM_K_NONE; pi.splitk = 1; pi.kchunk = K;
+    if (M == 0 || N == 0) return 0;
+    // (M = 1 with pitch 1: the transposed A is k-contiguous as well, and the loaders mask only a k-strided operand -- the mask was dropped silently)
+    LAS_ARG(a_mask_period == 0 || lda > 1, "las_gemm: a_mask_period needs a k-strided A (lda > 1)");
+    const long long ksA = transA ? lda : 1, ksB = transB ? 1 : ldb;
+    pi.in_bf16 = in_dtype == LAS_DT_BF16;
+    const unsigned amask = pi.in_bf16 ? 7 : 15;                     // 4-element chunks: 8 bytes of bf16 / 16 bytes of fp32
+    p->vecA = ((lda % 4) == 0) && ((a_align & amask) == 0) && ((strideA % 4) == 0);
+    p->vecB = ((ldb % 4) == 0) && ((b_align & amask) == 0) && ((strideB % 4) == 0);
+
+    // tile configuration
+    int cfg;
+    // branch-free fast path: 16-byte loads legal, k (or row) counts multiples of 4, no contraction mask
+    const bool fastA = p->vecA && (ksA == 1 ? (K % 4 == 0) : (M % 4 == 0 && M >= 4));
+    const bool fastB = p->vecB && (ksB == 1 ? (K % 4 == 0) : (N % 4 == 0 && N >= 4));
+    const bool fast_ok = prec == LAS_PREC_BF16 && fastA && fastB && a_mask_period == 0 && K > 0;
+    // exact-fp32 kernels: the same conditions select their branch-free loader (1 + A k-contiguous + 2 B k-contiguous; 0 = generic).
+    // (tried: the generic loader for these products too -> 44-57 % of the fp32 matrix peak, see tile_gload_f32fast; its A/B switch is retired)
+    const int f32_ld = (fastA && fastB && a_mask_period == 0 && K > 0) ? 1 + (ksA == 1 ? 1 : 0) + (ksB == 1 ? 2 : 0) : 0;
+    if (prec == LAS_PREC_F32) cfg = 0;                                             // exact-fp32 MFMA tiles
+    else if (M <= 48 && !(fast_ok && K >= 4096)) cfg = 3;                          // 48 x 64; tall contractions: 64-row fast tiles win
+    else if (M < 128 || N < 128) cfg = 2;                                          // 64 x 64
+    else cfg = 1;                                                                  // 128 x 128
+
+    const GemmSplit sp = gemm_split(prec, M, N, K, batch, ws_bytes);
+    if (sp.splitk > 1) { pi.splitk = sp.splitk; pi.kchunk = sp.kchunk; }
+    const int zdim = pi.splitk > 1 ? pi.splitk : batch;
+
+    LAS_ARG(!pi.in_bf16 || fast_ok,
+            "las_gemm: bf16 operands are served by the branch-free path only (aligned pitches, K / row counts multiples of 4, no mask)");
+    if (pi.in_bf16 && cfg == 3) cfg = 2;                                           // (no 48-row branch-free tile: M <= 48 takes the 64-row one)
+    // weight-gradient form (both operands k-strided bf16, whole 128 x 128 tiles, 16-byte aligned rows): LDS-transposing kernel
+    const bool tn_al = g_tn_tr_on && fast_ok && pi.in_bf16 && ksA != 1 && ksB != 1 && N % 128 == 0 &&
+                       lda % 8 == 0 && ldb % 8 == 0 && strideA % 8 == 0 && strideB % 8 == 0 && ((a_align | b_align) & 15) == 0;
+    const bool tn_tr = tn_al && cfg == 1 && M % 128 == 0;
+    const bool tn_tr64 = tn_al && cfg == 2 && M <= 64 && M % 8 == 0 && batch == 1;     // (a first layer's dW_ih; one row block)
+    if (tn_tr64 || tn_tr) {
+        pi.kernel = LAS_GEMM_K_TN_TR; pi.tile_m = tn_tr64 ? 64 : 128; pi.tile_n = 128;
+        gemm_plan_grid(p, N / 128, tn_tr64 ? 1 : M / 128, zdim, false);
+    } else if (fast_ok && (cfg == 1 || cfg == 2)) {
+        pi.kernel = LAS_GEMM_K_BF16_FAST; pi.tile_m = pi.tile_n = cfg == 1 ? 128 : 64;
+        pi.loader = (ksA == 1 ? 1 : 0) | (ksB == 1 ? 2 : 0);
+        gemm_plan_grid(p, cdiv(N, pi.tile_n), cdiv(M, pi.tile_m), zdim, true);
+    } else if (cfg != 0) {
+        pi.kernel = LAS_GEMM_K_BF16_GENERIC; pi.tile_m = cfg == 1 ? 128 : cfg == 2 ? 64 : 48; pi.tile_n = cfg == 1 ? 128 : 64;
+        pi.grid_x = cdiv(N, pi.tile_n); pi.grid_y = cdiv(M, pi.tile_m); pi.grid_z = zdim;
+    } else if (M <= 64) {
+        pi.kernel = LAS_GEMM_K_MF32_SKINNY; pi.tile_m = 16 * cdiv(M, 16); pi.tile_n = 32; pi.loader = f32_ld;
+        pi.grid_x = cdiv(N, 32); pi.grid_y = 1; pi.grid_z = zdim;
+    } else {
+        pi.kernel = LAS_GEMM_K_MF32; pi.tile_m = pi.tile_n = (M < 128 || N < 128) ? 64 : 128; pi.loader = f32_ld;
+        pi.grid_x = cdiv(N, pi.tile_n); pi.grid_y = cdiv(M, pi.tile_m); pi.grid_z = zdim;
+    }
+    return 0;
+}
+
+extern "C" int las_gemm_plan(int prec, int transA, int transB, int M, int N, int K, int lda, long long strideA, int ldb, long long strideB,
+                             int in_dtype, int batch, int a_mask_period, unsigned a_align, unsigned b_align, size_t ws_bytes,
+                             las_gemm_plan_info* out) {
+    LAS_ARG(out, "las_gemm_plan: null out");
+    GemmPlan pl;
+    const int rc = gemm_plan(prec, transA, transB, M, N, K, lda, strideA, ldb, strideB, in_dtype, batch, a_mask_period, a_align & 15,
+                             b_align & 15, ws_bytes, &pl);
+    if (rc) return rc;
+    *out = pl.info;
+    return 0;
+}
+
 extern "C" int las_gemm(int prec, int transA, int transB, int M, int N, int K, float alpha, const float* A,
                         int lda, long long strideA, const float* B, int ldb, long long strideB, float beta,
                         float* C, int ldc, long long strideC, const float* bias, int act, int batch,
@@ -1134,72 +1221,49 @@ extern "C" int las_gemm_dt(int prec, int transA, int transB, int M, int N, int K
                            int lda, long long strideA, const void* Bv, int ldb, long long strideB, int in_dtype, float beta,
                            float* C, int ldc, long long strideC, const float* bias, int act, int batch,
                            int a_mask_period, int a_mask_skip, void* ws, size_t ws_bytes, void* stream) {
-    const float* A = (const float*)Av;
-    const float* B = (const float*)Bv;
-    LAS_ARG(in_dtype == LAS_DT_F32 || (in_dtype == LAS_DT_BF16 && prec == LAS_PREC_BF16), "las_gemm: bf16 operands need LAS_PREC_BF16");
-    LAS_ARG(prec == LAS_PREC_F32 || prec == LAS_PREC_BF16, "las_gemm: bad prec %d", prec);
-    LAS_ARG(M >= 0 && N >= 0 && K >= 0 && batch >= 1, "las_gemm: bad dims M=%d N=%d K=%d batch=%d", M, N, K, batch);
-    LAS_ARG(A && B && C, "las_gemm: null operand");
-    LAS_ARG(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, "las_gemm: leading dimension too small");
-    LAS_ARG(a_mask_period == 0 || transA == 1, "las_gemm: a_mask_period needs transA=1");
+    GemmPlan pl;
+    const int rc = gemm_plan(prec, transA, transB, M, N, K, lda, strideA, ldb, strideB, in_dtype, batch, a_mask_period,
+                             (unsigned)((uintptr_t)Av & 15), (unsigned)((uintptr_t)Bv & 15), ws ? ws_bytes : 0, &pl);
+    if (rc) return rc;
+    LAS_ARG(Av && Bv && C, "las_gemm: null operand");              // what the plan cannot see: the pointers, C's pitch, the activation
+    LAS_ARG(ldc >= N, "las_gemm: leading dimension too small");
     LAS_ARG(act == LAS_ACT_NONE || act == LAS_ACT_TANH, "las_gemm: bad act %d", act);
-    if (M == 0 || N == 0) return 0;
+    const las_gemm_plan_info& pi = pl.info;
+    if (pi.kernel == LAS_GEMM_K_NONE) return 0;            // M == 0 or N == 0: nothing to write
     hipStream_t st = (hipStream_t)stream;
     GemmArgs g;
     g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta;
-    g.A = A; g.B = B; g.C = C; g.ldc = ldc;
+    g.A = (const float*)Av; g.B = (const float*)Bv; g.C = C; g.ldc = ldc;
     g.strideA = strideA; g.strideB = strideB; g.strideC = strideC;
     g.rsA = transA ? 1 : lda;  g.ksA = transA ? lda : 1;
     g.rsB = transB ? ldb : 1;  g.ksB = transB ? 1 : ldb;
     g.bias = bias; g.act = act;
     g.mask_period = a_mask_period; g.mask_skip = a_mask_skip;
-    const uintptr_t amask = in_dtype == LAS_DT_BF16 ? 7 : 15;       // 4-element chunks: 8 bytes of bf16 / 16 bytes of fp32
-    g.vecA = ((lda % 4) == 0) && (((uintptr_t)A & amask) == 0) && ((strideA % 4) == 0);
-    g.vecB = ((ldb % 4) == 0) && (((uintptr_t)B & amask) == 0) && ((strideB % 4) == 0);
-    g.splitk = 1; g.kchunk = K; g.partial = nullptr;
-    g.in_bf16 = in_dtype == LAS_DT_BF16; g.zgroup = 0;
+    g.vecA = pl.vecA; g.vecB = pl.vecB;
+    g.splitk = pi.splitk; g.kchunk = pi.kchunk; g.partial = pi.splitk > 1 ? (float*)ws : nullptr;
+    g.in_bf16 = pi.in_bf16; g.zgroup = pl.zgroup;
 
-    // tile configuration
-    int cfg;
-    // branch-free fast path: 16-byte loads legal, k (or row) counts multiples of 4, no contraction mask
-    const bool fastA = g.vecA && (g.ksA == 1 ? (K % 4 == 0) : (M % 4 == 0 && M >= 4));
-    const bool fastB = g.vecB && (g.ksB == 1 ? (K % 4 == 0) : (N % 4 == 0 && N >= 4));
-    const bool fast_ok = prec == LAS_PREC_BF16 && fastA && fastB && a_mask_period == 0 && K > 0;
-    // exact-fp32 kernels: the same conditions select their branch-free loader (1 + A k-contiguous + 2 B k-contiguous; 0 = generic).
-    // (tried: the generic loader for these products too -> 44-57 % of the fp32 matrix peak, see tile_gload_f32fast; its A/B switch is retired)
-    const int f32_ld = (fastA && fastB && a_mask_period == 0 && K > 0) ? 1 + (g.ksA == 1 ? 1 : 0) + (g.ksB == 1 ? 2 : 0) : 0;
-    if (prec == LAS_PREC_F32) cfg = 0;                                             // exact-fp32 MFMA tiles
-    else if (M <= 48 && !(fast_ok && K >= 4096)) cfg = 3;                          // 48 x 64; tall contractions: 64-row fast tiles win
-    else if (M < 128 || N < 128) cfg = 2;                                          // 64 x 64
-    else cfg = 1;                                                                  // 128 x 128
-
-    const GemmSplit sp = gemm_split(prec, M, N, K, batch, ws ? ws_bytes : 0);
-    if (sp.splitk > 1) { g.splitk = sp.splitk; g.kchunk = sp.kchunk; g.partial = (float*)ws; }
-    const int zdim = g.splitk > 1 ? g.splitk : batch;
-
-    LAS_ARG(!g.in_bf16 || (fast_ok && cfg != 3) || (fast_ok && M <= 48),
-            "las_gemm: bf16 operands are served by the branch-free path only (aligned pitches, K / row counts multiples of 4, no mask)");
-    if (g.in_bf16 && cfg == 3) cfg = 2;
-    // weight-gradient form (both operands k-strided bf16, whole 128 x 128 tiles, 16-byte aligned rows): LDS-transposing kernel
-    const bool tn_al = g_tn_tr_on && fast_ok && g.in_bf16 && g.ksA != 1 && g.ksB != 1 && N % 128 == 0 &&
-                       lda % 8 == 0 && ldb % 8 == 0 && strideA % 8 == 0 && strideB % 8 == 0 && (((uintptr_t)A | (uintptr_t)B) & 15) == 0;
-    const bool tn_tr = tn_al && cfg == 1 && M % 128 == 0;
-    const bool tn_tr64 = tn_al && cfg == 2 && M <= 64 && M % 8 == 0 && batch == 1;     // (a first layer's dW_ih; one row block)
-    if (fast_ok && tn_tr64) {
-        const dim3 grid = gemm_grid(g, N / 128, 1, zdim, false);
-        hipLaunchKernelGGL(gemm_tn_tr_kernel<64>, grid, dim3(256), 0, st, g);
-    } else if (fast_ok && tn_tr) {
-        const dim3 grid = gemm_grid(g, N / 128, M / 128, zdim, false);
-        hipLaunchKernelGGL(gemm_tn_tr_kernel<128>, grid, dim3(256), 0, st, g);
+    const dim3 grid(pi.grid_x, pi.grid_y, pi.grid_z);
+    switch (pi.kernel) {
+        case LAS_GEMM_K_TN_TR:
+            if (pi.tile_m == 64) hipLaunchKernelGGL(gemm_tn_tr_kernel<64>, grid, dim3(256), 0, st, g);
+            else                 hipLaunchKernelGGL(gemm_tn_tr_kernel<128>, grid, dim3(256), 0, st, g);
+            break;
+        case LAS_GEMM_K_BF16_FAST:
+            if (pi.tile_m == 128) launch_fast<2, 2, 4, 4>(g, pi.loader, grid, st);
+            else                  launch_fast<2, 2, 2, 2>(g, pi.loader, grid, st);
+            break;
+        case LAS_GEMM_K_BF16_GENERIC:
+            if (pi.tile_m == 128)     launch_bf16<2, 2, 4, 4>(g, grid, st);
+            else if (pi.tile_m == 64) launch_bf16<2, 2, 2, 2>(g, grid, st);
+            else                      launch_bf16<1, 4, 3, 1>(g, grid, st);
+            break;
+        case LAS_GEMM_K_MF32_SKINNY: launch_mf32_skinny(g, pi.loader, pi.tile_m / 16, grid, st); break;
+        default:
+            if (pi.tile_m == 64) launch_mf32<2, 2>(g, pi.loader, grid, st);
+            else                 launch_mf32<4, 4>(g, pi.loader, grid, st);
+            break;
     }
-    else if (fast_ok && cfg == 1) launch_fast<2, 2, 4, 4>(g, zdim, st);
-    else if (fast_ok && cfg == 2) launch_fast<2, 2, 2, 2>(g, zdim, st);
-    else if (cfg == 1) launch_bf16<2, 2, 4, 4>(g, zdim, st);
-    else if (cfg == 2) launch_bf16<2, 2, 2, 2>(g, zdim, st);
-    else if (cfg == 3) launch_bf16<1, 4, 3, 1>(g, zdim, st);
-    else if (M <= 64) launch_mf32_skinny(g, f32_ld, cdiv(M, 16), dim3(cdiv(N, 32), 1, zdim), st);
-    else if (M < 128 || N < 128) launch_mf32<2, 2>(g, f32_ld, dim3(cdiv(N, 64), cdiv(M, 64), zdim), st);
-    else launch_mf32<4, 4>(g, f32_ld, dim3(cdiv(N, 128), cdiv(M, 128), zdim), st);
     LAS_LAUNCHED();
     if (g.splitk > 1) {
         int nb = cdiv((long long)M * N, 256);

@@ -107,6 +107,12 @@ class RnnSeqPlanInfo(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("kernel", "P", "rows_per_tile", "launches", "x_chunks", "rows", "dout_chunks", "progress_words")]
 
 
+class GemmPlanInfo(ctypes.Structure):
+    """include/las_hip.h las_gemm_plan_info"""
+    _fields_ = [(n, c_int) for n in ("kernel", "tile_m", "tile_n", "loader", "in_bf16", "grid_order", "splitk", "kchunk",
+                                     "grid_x", "grid_y", "grid_z")]
+
+
 class FrontendArgs(ctypes.Structure):
     """include/las_hip.h las_frontend_args"""
     _fields_ = [("samples", c_void_p), ("samples_i16", c_int), ("ld_samples", c_longlong), ("n_samples", c_void_p), ("n_samples_host", POINTER(c_int))] + \
@@ -138,6 +144,8 @@ _SIGS = {
                             c_void_p, c_int, c_longlong, c_int, c_float, c_void_p, c_int, c_longlong, c_void_p, c_int,
                             c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "las_gemm_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "las_gemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_longlong, c_int, c_longlong, c_int, c_int, c_int,
+                              ctypes.c_uint, ctypes.c_uint, c_size_t, POINTER(GemmPlanInfo)]),
     "las_wgrad_ih_hh_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "las_wgrad_ih_hh": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -282,7 +290,7 @@ _SIGS = {
 }
 
 
-ABI_VERSION = 610      # include/las_hip.h LAS_HIP_ABI_VERSION
+ABI_VERSION = 611      # include/las_hip.h LAS_HIP_ABI_VERSION
 
 
 def declared_symbols():
@@ -538,6 +546,31 @@ def gemm(prec, A, B, C, transA=False, transB=False, M=None, N=None, K=None, lda=
                            c_void_p(C.data_ptr() + 4 * c_off), ldc, strideC, p(bias), act, batch,
                            mask_period, mask_skip, p(ws), min(ws.numel(), GEMM_WS_BYTES) if need else 0, stream())
     check(rc, "las_gemm")
+
+
+# las_gemm_plan's kernels (include/las_hip.h LAS_GEMM_K_*)
+GEMM_KERNELS = ("none", "bf16_generic", "bf16_fast", "tn_tr", "mf32", "mf32_skinny")
+GemmPlan = collections.namedtuple("GemmPlan", [n for n, _ in GemmPlanInfo._fields_])
+
+
+def gemm_plan(prec, A, B, C=None, transA=False, transB=False, M=None, N=None, K=None, lda=None, ldb=None, ldc=None,
+              alpha=1.0, beta=0.0, bias=None, act=ACT_NONE, batch=1, strideA=0, strideB=0, strideC=0,
+              mask_period=0, mask_skip=0, a_off=0, b_off=0, c_off=0):
+    """las_gemm_plan: what `gemm` with the same arguments launches (kernel: its GEMM_KERNELS name).  Host arithmetic, no launch: the
+    operands count by their element type and their addresses (data_ptr plus the element offsets) modulo 16, the scratch by what `gemm`
+    would hand over."""
+    if A.dtype != B.dtype:
+        raise RuntimeError("las_gemm: operands must share one element type (got %s, %s)" % (A.dtype, B.dtype))
+    need = int(lib().las_gemm_workspace_bytes(prec, M, N, K, batch))
+    es = A.element_size()
+    info = GemmPlanInfo()
+    check(lib().las_gemm_plan(prec, int(transA), int(transB), M, N, K, lda, strideA, ldb, strideB,
+                              DT_BF16 if A.dtype == torch.bfloat16 else DT_F32, batch, mask_period,
+                              (A.data_ptr() + es * a_off) % 16, (B.data_ptr() + es * b_off) % 16, min(need, GEMM_WS_BYTES), ctypes.byref(info)),
+          "las_gemm_plan")
+    d = {n: getattr(info, n) for n, _ in GemmPlanInfo._fields_}
+    d["kernel"] = GEMM_KERNELS[d["kernel"]]
+    return GemmPlan(**d)
 
 
 def gemm_kk(A, B, C, M, N, K, lda, ldb, ldc, bias=None, act=ACT_NONE, a_off=0, b_off=0, c_off=0, tanh_y=None, ldy=0):

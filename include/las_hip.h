@@ -37,7 +37,7 @@ enum { LAS_ACT_NONE = 0, LAS_ACT_TANH = 1 };
 enum { LAS_ATT_ADD = 0, LAS_ATT_LOC = 1 };      /* las/las.py:44-49 */
 enum { LAS_DT_F32 = 0, LAS_DT_BF16 = 1 };       /* element type of a tensor in HBM (see las_gemm_kk) */
 
-#define LAS_HIP_ABI_VERSION 610      /* bumped whenever an argument struct or a signature changes: las_version() of a library
+#define LAS_HIP_ABI_VERSION 611      /* bumped whenever an argument struct or a signature changes: las_version() of a library
                                         built from another header differs, and the Python loader refuses it */
 int         las_version(void);
 const char* las_last_error(void);
@@ -51,7 +51,8 @@ const char* las_last_error(void);
  * transposed (A as K x M, B as N x K).  bias (length N) may be NULL.
  * a_mask_period > 0: logical rows r of the CONTRACTION index of a transA=1 product with
  * (r % a_mask_period) == a_mask_skip contribute zero -- used for dW_hh = sum_t h_{t-1}^T dG_t where
- * the t=0 (fw) / t=T-1 (bw) frame has no predecessor inside its utterance.
+ * the t=0 (fw) / t=T-1 (bw) frame has no predecessor inside its utterance (needs lda > 1: an A of one column
+ * at pitch 1 is refused).
  * ws (optional, may be NULL): scratch for a deterministic split-K of tall contractions
  * (partials [s][M][N] reduced in fixed order); without it the product runs unsplit.
  */
@@ -76,6 +77,29 @@ int las_gemm_dt(int prec, int transA, int transB, int M, int N, int K,
                 float beta, float* C, int ldc, long long strideC,
                 const float* bias, int act, int batch,
                 int a_mask_period, int a_mask_skip, void* ws, size_t ws_bytes, void* stream);
+
+/* What a las_gemm_dt call with these arguments launches: every decision of the dispatch (kernel family, tile, loader, operand type,
+ * grid order, split-K and the grid), made by the one host function the launch itself follows.  Pure host arithmetic, no GPU: the
+ * operands enter as a_align / b_align, their addresses modulo 16, and the scratch as ws_bytes (0 = none).  Returns 0, or a negative
+ * value with las_gemm_dt's las_last_error text wherever that would refuse the call (e.g. bf16 operands off the branch-free path).
+ * M == 0 or N == 0: kernel = LAS_GEMM_K_NONE, nothing is launched.  A test can so name the kernel a case ran, and a table of cases can
+ * be held to the set of plans that are reachable at all. */
+enum { LAS_GEMM_K_NONE = 0, LAS_GEMM_K_BF16_GENERIC = 1, LAS_GEMM_K_BF16_FAST = 2, LAS_GEMM_K_TN_TR = 3, LAS_GEMM_K_MF32 = 4,
+       LAS_GEMM_K_MF32_SKINNY = 5 };
+typedef struct las_gemm_plan_info {
+    int kernel;              /* LAS_GEMM_K_* */
+    int tile_m, tile_n;      /* output tile of a workgroup: 48 / 64 / 128 x 64 / 128; skinny: 16 * row tiles x 32 */
+    int loader;              /* BF16_FAST: bit 0 = A k-contiguous, bit 1 = B k-contiguous; MF32 / MF32_SKINNY: 0 = generic loader, 1 + (A k-
+                                contiguous) + 2 (B k-contiguous) = branch-free loader; else 0 */
+    int in_bf16;             /* operands are bf16 in HBM */
+    int grid_order;          /* 0 = plain 3-D grid, 1 = all tiles of a k-chunk / batch entry on one XCD, 2 = the column tiles of a row block on one XCD */
+    int splitk, kchunk;      /* k-chunks (1 = unsplit) of kchunk contraction rows each (whole 32-wide k-tiles when split) */
+    int grid_x, grid_y, grid_z;
+} las_gemm_plan_info;
+int las_gemm_plan(int prec, int transA, int transB, int M, int N, int K,
+                  int lda, long long strideA, int ldb, long long strideB, int in_dtype,
+                  int batch, int a_mask_period, unsigned a_align, unsigned b_align,
+                  size_t ws_bytes, las_gemm_plan_info* out);
 
 /* Both weight gradients of a recurrent layer's direction(s) (the matmul gradient of the cell's kernel, las/layers.py:31 under
  * bidirectional_dynamic_rnn, las/layers.py:49-53) in one pass over d(pre-activation):

@@ -16,6 +16,10 @@ int main() {
     FIELD(las_seq_prepare_desc, whh_fw); FIELD(las_seq_prepare_desc, whh_bw); FIELD(las_seq_prepare_desc, ldw); FIELD(las_seq_prepare_desc, cell);
     FIELD(las_seq_prepare_desc, H); FIELD(las_seq_prepare_desc, B); FIELD(las_seq_prepare_desc, bwd); FIELD(las_seq_prepare_desc, flags);
     FIELD(las_seq_prepare_desc, ws); FIELD(las_seq_prepare_desc, ws_bytes);
+    STRUCT(las_gemm_plan_info);
+    FIELD(las_gemm_plan_info, kernel); FIELD(las_gemm_plan_info, tile_m); FIELD(las_gemm_plan_info, tile_n); FIELD(las_gemm_plan_info, loader);
+    FIELD(las_gemm_plan_info, in_bf16); FIELD(las_gemm_plan_info, grid_order); FIELD(las_gemm_plan_info, splitk); FIELD(las_gemm_plan_info, kchunk);
+    FIELD(las_gemm_plan_info, grid_x); FIELD(las_gemm_plan_info, grid_y); FIELD(las_gemm_plan_info, grid_z);
     STRUCT(las_rnn_seq_plan_info);
     FIELD(las_rnn_seq_plan_info, kernel); FIELD(las_rnn_seq_plan_info, P); FIELD(las_rnn_seq_plan_info, rows_per_tile);
     FIELD(las_rnn_seq_plan_info, launches); FIELD(las_rnn_seq_plan_info, x_chunks); FIELD(las_rnn_seq_plan_info, rows);

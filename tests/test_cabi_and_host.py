@@ -82,7 +82,7 @@ def test_argument_validation_happens_before_any_launch(libpath):
 
 
 # include/las_hip.h's argument structs and the ctypes classes las/_hip.py lays out by hand for them
-ABI_STRUCTS = {"las_seq_prepare_desc": "SeqPrepareDesc", "las_rnn_seq_plan_info": "RnnSeqPlanInfo", "las_rnn_seq_args": "RnnSeqArgs",
+ABI_STRUCTS = {"las_gemm_plan_info": "GemmPlanInfo", "las_seq_prepare_desc": "SeqPrepareDesc", "las_rnn_seq_plan_info": "RnnSeqPlanInfo", "las_rnn_seq_args": "RnnSeqArgs",
                "las_speller_fwd_args": "SpellerFwdArgs", "las_speller_bwd_args": "SpellerBwdArgs", "las_shadow_desc": "ShadowDesc",
                "las_lstm_cell_args": "LstmCellArgs", "las_beam_loop_args": "BeamLoopArgs", "las_input_config": "InputConfig",
                "las_input_batch": "InputBatch", "las_frontend_args": "FrontendArgs", "las_resample_args": "ResampleArgs",

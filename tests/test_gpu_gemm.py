@@ -1,4 +1,5 @@
-"""K1/K3/K4 parity: las_gemm (C ABI) vs an fp64 torch-CPU contraction of the same operands."""
+"""K1/K3/K4 parity: las_gemm (C ABI) vs an fp64 torch-CPU contraction of the same operands.  For bf16-mode correctness of every
+kernel the dispatch can reach (bit-exact on integer operands, rounding and epilogue apart) see tests/test_gpu_gemm_exact.py."""
 import pytest
 import torch
 
