@@ -84,6 +84,10 @@ __device__ __forceinline__ f32x4_t mfma_bf16_16x16x32(u16x8_t a, u16x8_t b, f32x
                                                    __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
 }
 
+// Pins a loop-invariant MFMA operand fragment to the accumulation half (AGPRs) of the lane's register file.  A kernel of one wave per
+// SIMD owns 512 registers per lane, 256 of each class, and an MFMA reads its A / B operands from either: fragments parked there leave
+// the architectural VGPRs to the rest of the loop.  (The MFMA itself stays the builtin, so the compiler keeps its hazard handling.)
+__device__ __forceinline__ void pin_agpr(u16x8_t& v) { asm volatile("" : "+a"(v)); }
 // ---- activations --------------------------------------------------------------------------------
 // accurate forms (fp32 parity mode)
 __device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + expf(-x)); }

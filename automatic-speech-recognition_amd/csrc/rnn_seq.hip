@@ -1140,7 +1140,23 @@ struct KsCfg {
     static constexpr int LDZ = KP + 16;              // bf16 row pitch of the own-dG tile (8 dwords mod 64 banks, see RnnCfg::LDH)
     static constexpr int DZ_BYTES = 2 * RB * LDZ * 2;
     static constexpr int GPD = 4 * UTP * 4 * 64;     // granules one member sends to ONE other member per step
+    // operand ring of the step loop: 3 slots = a step's operands are requested two steps ahead.  One instantiation cannot pay for the
+    // third slot: 16-row tiles with two unit tiles per wave and 16 A fragments (LSTM, H = 256, P = 2) hold 20 words per slot beside
+    // 64 registers of A fragments -- two slots (one step ahead) there, and the A fragments in two batches (AFB), or the compiler spills
+    // VGPRs.  Four unit tiles per wave (the tanh cell, H = 512, P = 2) take two slots as well: the third copy of the loop body ran the
+    // 8-row kernel out of SGPRs (62 spilled to VGPR lanes)
+    static constexpr bool TIGHT = RB == 16 && UTP * KSP >= 32;
+    static constexpr int RING = (TIGHT || UTP >= 4) ? 2 : 3;
+    static constexpr int AFB = TIGHT ? KSP / 2 : KSP;
     static constexpr bool OK = C::OK && NFR <= 64 && (KP % 32 == 0);
+    // 1 - x * x of the gate backward (x = tanh(c_t), or h of the tanh cell) for unit tile j: one fma, or a rounded square and a
+    // subtraction.  Until the step loop was unrolled this was the compiler's choice (fp contraction), and it chose differently per
+    // instantiation and even per tile: the square stayed unfused in the LSTM kernels of one unit tile on 8-row tiles at P <= 4 and in
+    // the LAST tile of the tanh cell's 8-row kernels.  The choice is now written down as it was made then, so that dZ and the bias sums
+    // keep their bits (tests/golden/bptt_bits_parent.json) whatever the loop shape; one form everywhere is a change of results.
+    static constexpr bool sq_fused(int j) {
+        return CELL == LAS_CELL_LSTM ? !(RB == 8 && UTP == 1 && P <= 4) : !(RB == 8 && j == UTP - 1);
+    }
 };
 
 // RB = batch rows per tile.  RB = 8: the step is bound by per-lane work (gate backward, operand loads, granules), all of which
@@ -1148,7 +1164,8 @@ struct KsCfg {
 // repeat rows 0..7.  Lanes 32..63 then hold the same accumulators as lanes 0..31 and every lane keeps HALF of them (selected
 // by hsel = lane >> 5): one row x one unit pair per lane instead of two rows, half the loads / stores / transcendentals /
 // granule bytes per step, twice as many CUs per batch.
-// CH: dout arrives in chunks (a.dflag): a separate instantiation -- the kernel sits at the register limit and the plain one must not change
+// CH: dout arrives in chunks (a.dflag): a separate instantiation (made when the kernel sat at the VGPR limit with its W_hh fragments in
+// VGPRs and the plain one must not change; the fragments now live in the AGPRs and both variants run the same operand ring)
 // PG (round 5, with CH): the sweep PUBLISHES its progress -- every a.pstep steps each member waits for its own dZ stores, writes the XCD's
 // dirty L2 lines back (one agent-scope release) and stores the step count into a.prog -- so that the layer's weight gradients can follow the sweep window
 // by window on another stream (las_rnn_seq_args' progress) instead of starting when it ends.  A separate instantiation, like CH.
@@ -1175,6 +1192,10 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
     u16x8_t wreg[NFR];
 #pragma unroll
     for (int r = 0; r < NFR; ++r) wreg[r] = Wp[r * 64 + lane];
+    // ... in the ACCUMULATION registers: the fragments are MFMA B operands, written here and never again, and this kernel runs one
+    // wave per SIMD, which owns 256 AGPRs besides its 256 VGPRs (NFR <= 64 fragments = 256 AGPRs: KsCfg::OK)
+#pragma unroll
+    for (int r = 0; r < NFR; ++r) pin_agpr(wreg[r]);
     // inbox of member d: [2 slots][P dst][P src][GPD]
     unsigned long long* xb = a.xbuf + (size_t)cl * 2 * P * P * GPD;
     const __amdgpu_buffer_rsrc_t xrs = granule_rsrc(xb);
@@ -1248,28 +1269,66 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
             __builtin_amdgcn_s_sleep(16);
         }
     };
-    wait_dout(0);
-    // operands of one step as packed pairs, ONE register set refilled for step s+1 right after step s consumed it
-    unsigned n_do[UTP][2], n_g[NG][UTP][2], n_c[UTP][2], n_cn[UTP][2];
+    // ---- operands of a step as packed pairs, requested TWO steps ahead: a ring of U = 3 register sets, named statically by the
+    // step loop's unroll (x U; no register rotation).  Slot s % U holds dout and the saved gates (the tanh cell: h) of step s; cell
+    // frame f sits in n_c[f % U], is loaded ONCE and serves as c_t of step f and as c_{t-1} of step f - 1.  Step s, once its gate
+    // backward has consumed slot s % U, requests step s + 2 into slot (s + 2) % U (free since step s - 1) and cell frame s + 3 into
+    // the slot of frame s.  The loads are unconditional: past the last frame the load pointers stop advancing (the address is clamped
+    // and the value unused) -- a conditional load makes the compiler drain vmcnt at the join, which puts the HBM latency of the whole
+    // request on the dependent chain.  The W_hh fragments in the AGPRs are what leaves the VGPRs for this.
+    constexpr int U = K::RING;
+    unsigned n_do[U][UTP][2], n_g[U][NG][UTP][2], n_c[U][UTP][2];
+    const gu32* lgp[2];                      // load pointers: the gate block of the next step to request (gptr stays with the dZ stores)
 #pragma unroll
-    for (int j = 0; j < UTP; ++j)
+    for (int rr = 0; rr < NR; ++rr) lgp[rr] = gptr[rr];
+    int lfr = 0, lcf = 0;                    // frame (in sweep order) optr / dptr / lgp and cptr point at
+    // dout, gates (h) of the frame at the load pointers -> slot k; the pointers move on unless that was the last frame
+    auto request_step = [&](unsigned (&vdo)[UTP][2], unsigned (&vg)[NG][UTP][2]) __attribute__((always_inline)) {
+        const bool more = lfr + 1 < T;
 #pragma unroll
         for (int rr = 0; rr < NR; ++rr) {
-            n_do[j][rr] = dptr[rr][j * 8];
-            if (CELL == LAS_CELL_LSTM) {
 #pragma unroll
-                for (int q = 0; q < NG; ++q) n_g[q][j][rr] = gptr[rr][(q * H + j * 16) / 2];
-                n_c[j][rr] = cptr[rr][j * 8];
-                n_cn[j][rr] = T > 1 ? cptr[rr][cst_[rr] + j * 8] : 0u;
-            } else {
-                n_g[0][j][rr] = optr[rr][j * 8];
-                n_c[j][rr] = 0u; n_cn[j][rr] = 0u;
+            for (int j = 0; j < UTP; ++j) {
+                vdo[j][rr] = dptr[rr][j * 8];
+                if (CELL == LAS_CELL_LSTM) {
+#pragma unroll
+                    for (int q = 0; q < NG; ++q) vg[q][j][rr] = lgp[rr][(q * H + j * 16) / 2];
+                } else {
+                    vg[0][j][rr] = optr[rr][j * 8];
+                }
             }
+            dptr[rr] += more ? dst[rr] : 0; lgp[rr] += more ? gst[rr] : 0; optr[rr] += more ? ost[rr] : 0;
         }
+        lfr += more ? 1 : 0;
+    };
+    auto request_cell = [&](unsigned (&vc)[UTP][2]) __attribute__((always_inline)) {
+        const bool more = lcf + 1 < T;
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) {
+#pragma unroll
+            for (int j = 0; j < UTP; ++j) vc[j][rr] = CELL == LAS_CELL_LSTM ? cptr[rr][j * 8] : 0u;
+            if (CELL == LAS_CELL_LSTM) cptr[rr] += more ? cst_[rr] : 0;
+        }
+        lcf += more ? 1 : 0;
+    };
+#pragma unroll
+    for (int k = 0; k < U - 1; ++k) {
+        if (k < T) wait_dout(k);
+        request_step(n_do[k], n_g[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < U; ++k) request_cell(n_c[k]);
     int cur = 0;
     int pleft = PG ? a.pstep : 0;                   // steps until the next publication of dZ progress (PG)
     const bool prof = sweep_prof_begin(a.dbg);
-    for (int s = 0; s < T; ++s) {
+    for (int sb = 0; sb < T; sb += U) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int s = sb + u;
+        if (s >= T) break;
+        unsigned (&c_do)[UTP][2] = n_do[u];                      // this step's operands
+        unsigned (&c_g)[NG][UTP][2] = n_g[u];
+        unsigned (&c_c)[UTP][2] = n_c[u], (&c_cn)[UTP][2] = n_c[(u + 1) % U];
         SWEEP_STAMP(0);
         unsigned short* dzc = dzs + cur * RB * LDZ;
         unsigned sv_z[G][UTP][2];            // d(pre-activation) of this step as packed pairs (written to HBM after the exchange)
@@ -1294,23 +1353,28 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
                 float dz[G][2];
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
-                    const float dh = (k ? hi(n_do[j][rr]) : lo(n_do[j][rr])) + dhp[rr][k];
+                    const float dh = (k ? hi(c_do[j][rr]) : lo(c_do[j][rr])) + dhp[rr][k];
                     if (CELL == LAS_CELL_LSTM) {
-                        const float gi = k ? hi(n_g[0][j][rr]) : lo(n_g[0][j][rr]);
-                        const float gj = k ? hi(n_g[NG > 1 ? 1 : 0][j][rr]) : lo(n_g[NG > 1 ? 1 : 0][j][rr]);
-                        const float gf = k ? hi(n_g[NG > 2 ? 2 : 0][j][rr]) : lo(n_g[NG > 2 ? 2 : 0][j][rr]);
-                        const float go = k ? hi(n_g[NG > 3 ? 3 : 0][j][rr]) : lo(n_g[NG > 3 ? 3 : 0][j][rr]);
-                        const float cprev = (s + 1 < T) ? (k ? hi(n_cn[j][rr]) : lo(n_cn[j][rr])) : 0.f;
-                        const float tc = tanhx<true>(k ? hi(n_c[j][rr]) : lo(n_c[j][rr]));
-                        const float dc = dcc[j][rr][k] + dh * go * (1.f - tc * tc);
+                        // which multiply-add pairs are fused is WRITTEN here, not left to the compiler (KsCfg::sq_fused): with contraction
+                        // allowed the copies of the unrolled loop body fused tc * tc into 1 - tc * tc where the single body did not,
+                        // and the bias sums (fp32 sums of the unrounded dz) moved in their last bits
+#pragma clang fp contract(off)
+                        const float gi = k ? hi(c_g[0][j][rr]) : lo(c_g[0][j][rr]);
+                        const float gj = k ? hi(c_g[NG > 1 ? 1 : 0][j][rr]) : lo(c_g[NG > 1 ? 1 : 0][j][rr]);
+                        const float gf = k ? hi(c_g[NG > 2 ? 2 : 0][j][rr]) : lo(c_g[NG > 2 ? 2 : 0][j][rr]);
+                        const float go = k ? hi(c_g[NG > 3 ? 3 : 0][j][rr]) : lo(c_g[NG > 3 ? 3 : 0][j][rr]);
+                        const float cprev = (s + 1 < T) ? (k ? hi(c_cn[j][rr]) : lo(c_cn[j][rr])) : 0.f;
+                        const float tc = tanhx<true>(k ? hi(c_c[j][rr]) : lo(c_c[j][rr]));
+                        const float dc = fmaf(dh * go, K::sq_fused(j) ? fmaf(-tc, tc, 1.f) : 1.f - tc * tc, dcc[j][rr][k]);
                         dcc[j][rr][k] = dc * gf;
                         dz[0][k] = dc * gj * gi * (1.f - gi);
-                        dz[G > 1 ? 1 : 0][k] = dc * gi * (1.f - gj * gj);
+                        dz[G > 1 ? 1 : 0][k] = dc * gi * fmaf(-gj, gj, 1.f);
                         dz[G > 2 ? 2 : 0][k] = dc * cprev * gf * (1.f - gf);
                         dz[G > 3 ? 3 : 0][k] = dh * tc * go * (1.f - go);
                     } else {
-                        const float h = k ? hi(n_g[0][j][rr]) : lo(n_g[0][j][rr]);
-                        dz[0][k] = dh * (1.f - h * h);
+#pragma clang fp contract(off)
+                        const float h = k ? hi(c_g[0][j][rr]) : lo(c_g[0][j][rr]);
+                        dz[0][k] = dh * (K::sq_fused(j) ? fmaf(-h, h, 1.f) : 1.f - h * h);
                     }
                 }
 #pragma unroll
@@ -1326,31 +1390,17 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
         SWEEP_STAMP(1);
         gu32* gprev[2];
 #pragma unroll
-        for (int rr = 0; rr < NR; ++rr) { gprev[rr] = gptr[rr]; gptr[rr] += gst[rr]; optr[rr] += ost[rr]; dptr[rr] += dst[rr]; if (CELL == LAS_CELL_LSTM) cptr[rr] += cst_[rr]; }
-        if (s + 1 < T) {     // operands of the next step fly under this step's MFMAs and exchange
-            wait_dout(s + 1);
-#pragma unroll
-            for (int j = 0; j < UTP; ++j)
-#pragma unroll
-                for (int rr = 0; rr < NR; ++rr) {
-                    n_do[j][rr] = dptr[rr][j * 8];
-                    if (CELL == LAS_CELL_LSTM) {
-#pragma unroll
-                        for (int q = 0; q < NG; ++q) n_g[q][j][rr] = gptr[rr][(q * H + j * 16) / 2];
-                        if constexpr (CH) n_c[j][rr] = cptr[rr][j * 8];      // (this variant re-loads c_t -- an L1 / L2 hit -- instead of rotating
-                                                                            //  registers: the pinned rotation below survives only in the plain loop shape)
-                        else {
-                        n_c[j][rr] = n_cn[j][rr];
-                        asm volatile("" : "+v"(n_c[j][rr]));        // the copy happens HERE: the old register of n_cn is free for the load below
-                        }
-                        // unconditional (a conditional load makes the compiler drain vmcnt at the join, which puts the HBM latency of
-                        // this whole prefetch on the dependent chain); past the last frame the address is clamped and the value unused
-                        n_cn[j][rr] = cptr[rr][((s + 2 < T) ? cst_[rr] : 0) + j * 8];
-                    } else {
-                        n_g[0][j][rr] = optr[rr][j * 8];
-                    }
-                }
-        }
+        for (int rr = 0; rr < NR; ++rr) { gprev[rr] = gptr[rr]; gptr[rr] += gst[rr]; }
+        // operands of step s + 2 (and cell frame s + 3): they fly under the MFMAs and exchanges of TWO steps.  CH: the chunk of the frame
+        // that is being requested must be complete (the flag is monotone, the wait bounded)
+        auto request_ahead = [&]() __attribute__((always_inline)) {
+            if (s + U - 1 < T) wait_dout(s + U - 1);
+            request_step(n_do[(u + U - 1) % U], n_g[(u + U - 1) % U]);
+            request_cell(n_c[u]);
+        };
+#ifndef LAS_KS_REQUEST_LATE
+        request_ahead();
+#endif
         SWEEP_STAMP(2);
         lds_barrier();
         SWEEP_STAMP(3);
@@ -1360,18 +1410,22 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
         for (int m = 0; m < P; ++m)
 #pragma unroll
             for (int j = 0; j < UTP; ++j) acc[m][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-        u16x8_t av[KSP];                         // all A fragments requested up front: the MFMAs then wait on LDS once, not per pair
+        constexpr int AFB = K::AFB;              // all A fragments requested up front (AFB = KSP but for one instantiation): the MFMAs then wait on LDS once, not per pair
 #pragma unroll
-        for (int ks = 0; ks < KSP; ++ks) av[ks] = *reinterpret_cast<const u16x8_t*>(&dzc[(c & (RB - 1)) * LDZ + ks * 32 + g * 8]);
+        for (int k0 = 0; k0 < KSP; k0 += AFB) {
+        u16x8_t av[AFB];
+#pragma unroll
+        for (int ks = 0; ks < AFB; ++ks) av[ks] = *reinterpret_cast<const u16x8_t*>(&dzc[(c & (RB - 1)) * LDZ + (k0 + ks) * 32 + g * 8]);
         __builtin_amdgcn_sched_barrier(0);
         // (measured: contracting the partners' tiles first and the own tile under the sends / the poll is slower, 1.31-1.36 vs 1.29 us)
 #pragma unroll
-        for (int ks = 0; ks < KSP; ++ks) {
+        for (int ks = 0; ks < AFB; ++ks) {
 #pragma unroll
             for (int m = 0; m < P; ++m)
 #pragma unroll
-                for (int j = 0; j < UTP; ++j) acc[m][j] = mfma_bf16_16x16x32(av[ks], wreg[(m * UTP + j) * KSP + ks], acc[m][j]);
+                for (int j = 0; j < UTP; ++j) acc[m][j] = mfma_bf16_16x16x32(av[ks], wreg[(m * UTP + j) * KSP + k0 + ks], acc[m][j]);
             __builtin_amdgcn_sched_barrier(0);
+        }
         }
 #ifdef LAS_PROF
         asm volatile("s_nop 0" :: "v"(acc[0][0][0]), "v"(acc[P - 1][UTP - 1][3]));
@@ -1468,6 +1522,9 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
             }
         }
         SWEEP_STAMP(6);
+#ifdef LAS_KS_REQUEST_LATE
+        request_ahead();
+#endif
         // ---- d(pre-activation) of this step to HBM as packed bf16 pairs (never waited on)
 #pragma unroll
         for (int j = 0; j < UTP; ++j)
@@ -1493,6 +1550,7 @@ __global__ __launch_bounds__(256, 1) void rnn_seq_bwd_ks_kernel(RnnArgs a) {
                 }
             }
         }
+    }
     }
     sweep_prof_end(a.dbg, prof);
     // bias gradient partials of this (tile, direction): sum the rows held by the lane pair and by the four row groups
