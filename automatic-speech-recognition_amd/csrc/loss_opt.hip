@@ -361,13 +361,13 @@ static int lb_launch(const LstmCellLaunch& a, hipStream_t st) {
     return 0;
 }
 template <int ROWS>
-static int lb_launch2(const LstmCellLaunch& a, const LstmCellLaunch& b, hipStream_t st) {
+static int lb_launch2(const LstmCellLaunch& a, const LstmCellLaunch& b, const bool bbf, hipStream_t st) {
     static int attr = lb_attr(lstm_cell_rows_big_pair_kernel<false, ROWS>, ROWS) | lb_attr(lstm_cell_rows_big_pair_kernel<true, ROWS>, ROWS);
     if (attr != 0) { las_set_error("hipFuncSetAttribute(lstm_cell_rows_big_pair) failed: %d", attr); return attr; }
     const int bx = (a.H > b.H ? a.H : b.H) / 16, by = cdiv(a.M > b.M ? a.M : b.M, ROWS);
     constexpr int LDS = lb_lds_bytes(ROWS);
-    if (lb_rows_type(b) == 1) hipLaunchKernelGGL((lstm_cell_rows_big_pair_kernel<true, ROWS>), dim3(bx, by, 2), dim3(512), LDS, st, a, b);
-    else                      hipLaunchKernelGGL((lstm_cell_rows_big_pair_kernel<false, ROWS>), dim3(bx, by, 2), dim3(512), LDS, st, a, b);
+    if (bbf) hipLaunchKernelGGL((lstm_cell_rows_big_pair_kernel<true, ROWS>), dim3(bx, by, 2), dim3(512), LDS, st, a, b);
+    else     hipLaunchKernelGGL((lstm_cell_rows_big_pair_kernel<false, ROWS>), dim3(bx, by, 2), dim3(512), LDS, st, a, b);
     LAS_LAUNCHED();
     return 0;
 }
@@ -386,14 +386,38 @@ int las_lstm_cell_check(const LstmCellLaunch& a) {
     return 0;
 }
 
-int las_lstm_cell_rows_launch(const LstmCellLaunch& a, hipStream_t st) {
+// THE dispatch decision of both launchers and of las_lstm_cell_rows_plan (host arithmetic only): which body serves one problem (b = NULL)
+// or a pair.  Negative: refused (las_lstm_cell_check).  Otherwise the LAS_LSTM_CELL_PLAN_* code of include/las_hip.h: rows per workgroup of
+// the pipelined body (0: the unpipelined 32-row body), PAIR = both problems in one grid, B_BF16 = the pair's second problem reads bf16 rows,
+// TWO = no pair kernel is compiled for these two problems: two single launches, each planned by this function on its own.
+static int lstm_cell_rows_decide(const LstmCellLaunch& a, const LstmCellLaunch* b) {
     if (int rc = las_lstm_cell_check(a)) return rc;
-    // (fp32 rows at <= 256 rows of x AND h -- the LM's second layer in a 16-utterance search: the unpipelined body's two 512-column chunks beat
-    //  eight pipelined 128-column chunks of 32 rows, 8.1 against 9.4 us)
-    if (lb_serves(a) && !(a.M <= 256 && lb_rows_type(a) == 0 && a.x && a.h && !a.h_out_bf16)) {
-        const int rows = g_lb_rows ? g_lb_rows : lb_rows_for(a.M);
-        return rows == 128 ? lb_launch<128>(a, st) : (rows == 64 ? lb_launch<64>(a, st) : lb_launch<32>(a, st));
+    if (!b) {
+        // (fp32 rows at <= 256 rows of x AND h -- the LM's second layer in a 16-utterance search: the unpipelined body's two 512-column chunks beat
+        //  eight pipelined 128-column chunks of 32 rows, 8.1 against 9.4 us)
+        if (lb_serves(a) && !(a.M <= 256 && lb_rows_type(a) == 0 && a.x && a.h && !a.h_out_bf16)) return g_lb_rows ? g_lb_rows : lb_rows_for(a.M);
+        return 0;
     }
+    if (int rc = las_lstm_cell_check(*b)) return rc;
+    if (!a.fast || b->fast) return LAS_LSTM_CELL_PLAN_TWO;                // the pair kernels: a with the Speller's transcendentals, b exact
+    if (lb_serves(a) && lb_rows_type(a) == 1 && lb_serves(*b)) {
+        // (two problems: 64-row tiles also at 1024 rows -- at 100-120 VGPRs both problems' workgroups share a CU and cover each other's
+        //  round trips, 18.1-18.4 against 18.6-18.7 ms per 211-step search; at 128 rows and 140-180 VGPRs they run one behind the other)
+        const int mm = a.M > b->M ? a.M : b->M;
+        const int rows = g_lb_pair_rows ? g_lb_pair_rows : (mm > 256 ? 64 : 32);
+        return rows | LAS_LSTM_CELL_PLAN_PAIR | (lb_rows_type(*b) == 1 ? LAS_LSTM_CELL_PLAN_B_BF16 : 0);
+    }
+    // the unpipelined pair kernel: a = bf16 x (+ fp32 h), b = fp32 rows.  Its body knows neither bf16 h rows nor h_out_bf16: a problem with
+    // either goes to a single launch of its own (the pipelined body, or las_lstm_cell_check's refusal)
+    if (a.x_bf16 && !b->x_bf16 && !a.h_bf16 && !b->h_bf16 && !a.h_out_bf16 && !b->h_out_bf16) return LAS_LSTM_CELL_PLAN_PAIR;
+    return LAS_LSTM_CELL_PLAN_TWO;
+}
+
+int las_lstm_cell_rows_launch(const LstmCellLaunch& a, hipStream_t st) {
+    const int plan = lstm_cell_rows_decide(a, nullptr);
+    if (plan < 0) return plan;
+    const int rows = plan & LAS_LSTM_CELL_PLAN_ROWS;
+    if (rows) return rows == 128 ? lb_launch<128>(a, st) : (rows == 64 ? lb_launch<64>(a, st) : lb_launch<32>(a, st));
     const dim3 grid(a.H / 16, cdiv(a.M, 32));
     if (a.fast && a.x_bf16) hipLaunchKernelGGL((lstm_cell_rows_kernel<true, true>), grid, dim3(512), 0, st, a);
     else if (a.fast)        hipLaunchKernelGGL((lstm_cell_rows_kernel<true, false>), grid, dim3(512), 0, st, a);
@@ -404,23 +428,29 @@ int las_lstm_cell_rows_launch(const LstmCellLaunch& a, hipStream_t st) {
 }
 
 int las_lstm_cell_rows_launch2(const LstmCellLaunch& a, const LstmCellLaunch& b, hipStream_t st) {
-    if (int rc = las_lstm_cell_check(a)) return rc;
-    if (int rc = las_lstm_cell_check(b)) return rc;
-    if (!(a.fast && a.x_bf16 && !b.fast && !b.x_bf16 && !b.h_bf16) && !(lb_serves(a) && lb_rows_type(a) == 1 && a.fast && !b.fast && lb_serves(b))) {   // not a pair a kernel is compiled for: two launches
+    const int plan = lstm_cell_rows_decide(a, &b);
+    if (plan < 0) return plan;
+    if (plan & LAS_LSTM_CELL_PLAN_TWO) {
         if (int rc = las_lstm_cell_rows_launch(a, st)) return rc;
         return las_lstm_cell_rows_launch(b, st);
     }
-    if (lb_serves(a) && lb_rows_type(a) == 1 && lb_serves(b)) {
-        // (two problems: 64-row tiles also at 1024 rows -- at 100-120 VGPRs both problems' workgroups share a CU and cover each other's
-        //  round trips, 18.1-18.4 against 18.6-18.7 ms per 211-step search; at 128 rows and 140-180 VGPRs they run one behind the other)
-        const int mm = a.M > b.M ? a.M : b.M;
-        const int rows = g_lb_pair_rows ? g_lb_pair_rows : (mm > 256 ? 64 : 32);
-        return rows == 128 ? lb_launch2<128>(a, b, st) : (rows == 64 ? lb_launch2<64>(a, b, st) : lb_launch2<32>(a, b, st));
-    }
+    const int rows = plan & LAS_LSTM_CELL_PLAN_ROWS;
+    const bool bbf = (plan & LAS_LSTM_CELL_PLAN_B_BF16) != 0;
+    if (rows) return rows == 128 ? lb_launch2<128>(a, b, bbf, st) : (rows == 64 ? lb_launch2<64>(a, b, bbf, st) : lb_launch2<32>(a, b, bbf, st));
     const int gx = (a.H > b.H ? a.H : b.H) / 16, gy = cdiv(a.M > b.M ? a.M : b.M, 32);
     hipLaunchKernelGGL(lstm_cell_rows_pair_kernel, dim3(gx, gy, 2), dim3(512), 0, st, a, b);
     LAS_LAUNCHED();
     return 0;
+}
+
+extern "C" int las_lstm_cell_rows_plan(const las_lstm_cell_args* a, const las_lstm_cell_args* b) {
+    LAS_ARG(a, "las_lstm_cell_rows_plan: null args");
+    return lstm_cell_rows_decide(*a, b);
+}
+
+extern "C" int las_lstm_cell_rows_pair_args(const las_lstm_cell_args* a, const las_lstm_cell_args* b, void* stream) {
+    LAS_ARG(a && b, "las_lstm_cell_rows_pair_args: null args");
+    return las_lstm_cell_rows_launch2(*a, *b, (hipStream_t)stream);
 }
 
 extern "C" int las_lstm_cell_rows_args(const las_lstm_cell_args* a, void* stream) {

@@ -17,6 +17,8 @@ CELL_RNN, CELL_LSTM = 0, 1
 ACT_NONE, ACT_TANH = 0, 1
 ATT_ADD, ATT_LOC = 0, 1
 DT_F32, DT_BF16 = 0, 1
+# las_lstm_cell_rows_plan's code (include/las_hip.h LAS_LSTM_CELL_PLAN_*): rows per workgroup (0: the unpipelined body) and three bits
+LSTM_CELL_PLAN_ROWS, LSTM_CELL_PLAN_PAIR, LSTM_CELL_PLAN_B_BF16, LSTM_CELL_PLAN_TWO = 0xff, 0x100, 0x200, 0x400
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAS_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "liblas_hip.so")   # (override: development builds)
@@ -238,6 +240,8 @@ _SIGS = {
     "las_lstm_cell_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "las_lstm_cell_rows_args": (c_int, [POINTER(LstmCellArgs), c_void_p]),
+    "las_lstm_cell_rows_pair_args": (c_int, [POINTER(LstmCellArgs), POINTER(LstmCellArgs), c_void_p]),
+    "las_lstm_cell_rows_plan": (c_int, [POINTER(LstmCellArgs), POINTER(LstmCellArgs)]),
     "las_lstm_pointwise_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "las_beam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

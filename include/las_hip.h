@@ -580,12 +580,29 @@ typedef struct las_lstm_cell_args {
     float fb;
     float *c_out, *h_out, *gates_out;
     int M, H, fast;
-    int h_bf16;                      /* (round 5) h holds bf16 rows: the copy a previous launch left in h_out_bf16.  Served by the 128-row
-                                        workgroups only (M >= 384, x absent or bf16 too): the beam search's LM cells at decode.py's batch */
+    int h_bf16;                      /* (round 5) h holds bf16 rows: the copy a previous launch left in h_out_bf16.  Served by the pipelined
+                                        body only (M >= 128, x absent or bf16 too; as is h_out_bf16): the beam search's LM cells */
     void* h_out_bf16;                /* optional [M, H] bf16: h' rounded as the next launch's operand staging would round it (RNE) -- the
                                         next layer's x and, gathered, the next step's h, at half the bytes */
 } las_lstm_cell_args;
 int las_lstm_cell_rows_args(const las_lstm_cell_args* a, void* stream);
+/* Two independent cell steps as the two problems of ONE grid (what las_speller_fwd does with its companion): a = the Speller's (fast,
+ * bf16 x), b = the LM's (exact; fp32 or bf16 rows, or a one-hot input).  Two problems no pair kernel is compiled for are served as two
+ * single launches, a then b; the results are those of las_lstm_cell_rows_args(a) and las_lstm_cell_rows_args(b), bit for bit. */
+int las_lstm_cell_rows_pair_args(const las_lstm_cell_args* a, const las_lstm_cell_args* b, void* stream);
+/* What las_lstm_cell_rows_args(a) (b = NULL) or las_lstm_cell_rows_pair_args(a, b) launches: host arithmetic, no launch, callable
+ * without a device (the pointers count by being NULL or not, and by their alignment).  Negative: the launch refuses these arguments.
+ * Otherwise a code of the bits below.  One problem: 0 below 128 rows and for fp32 x AND h at <= 256 rows, else 32 rows per workgroup
+ * up to 256 rows, 64 up to 512, 128 above.  A pair: PAIR with 0 (either problem below 128 rows or not of one element type), 32 (both
+ * <= 256 rows) or 64 rows; TWO where a is not fast, b is fast, or the unpipelined pair kernel would meet fp32 x in a, bf16 x in b, or
+ * bf16 h / h_out_bf16 in either. */
+enum {
+    LAS_LSTM_CELL_PLAN_ROWS = 0xff,      /* rows per workgroup of the pipelined body (32, 64, 128); 0: the unpipelined 32-row body */
+    LAS_LSTM_CELL_PLAN_PAIR = 0x100,     /* both problems in one grid */
+    LAS_LSTM_CELL_PLAN_B_BF16 = 0x200,   /* with PAIR and rows > 0: the second problem's rows are bf16 */
+    LAS_LSTM_CELL_PLAN_TWO = 0x400       /* two single launches, each as the query with b = NULL says; no other bit is set */
+};
+int las_lstm_cell_rows_plan(const las_lstm_cell_args* a, const las_lstm_cell_args* b /* may be NULL */);
 /* ... and its gradient, for training the RNNLM (lang/char_rnn_model.py:177-190, truncated BPTT over num_unrollings steps):
  * dz [N,4H] and dc_prev [N,H] from z, c_prev, dh (gradient w.r.t. h') and dc_in (gradient w.r.t. c', may be NULL). */
 int las_lstm_pointwise_bwd(const float* z, const float* c_prev, const float* dh, const float* dc_in, int N, int H,

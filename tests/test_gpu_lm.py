@@ -30,7 +30,9 @@ def test_pointwise_rows_equals_lookup_add_then_pointwise(N, H, V, shift):
     assert (c1 - c_t).abs().max() < 1e-5 and (h1 - torch.tanh(c_t) * torch.sigmoid(o)).abs().max() < 1e-5
 
 
-# (M >= 384: the 128-row workgroups of round 5 -- lstm_cell_rows_big_body -- incl. a ragged last row block and K chunks that end inside a part)
+# (M >= 128: the pipelined body of round 5 -- lstm_cell_rows_big_body, 32 rows per workgroup up to 256 rows, 64 up to 512, 128 above; fp32 x
+#  AND h at M <= 256 stay with the unpipelined body -- incl. a ragged last row block and K chunks that end inside a part.  Every body, the
+#  dispatch boundaries and the paired launch: test_gpu_lstm_cell_rows.py)
 @pytest.mark.parametrize("M,I,H,onehot", [(256, 512, 512, False), (256, 0, 512, True), (5, 64, 32, False), (33, 0, 64, True), (70, 1024, 96, False),
                                           (1024, 512, 512, False), (1024, 0, 512, True), (390, 1024, 96, False), (700, 160, 64, False)])
 def test_lstm_cell_rows_matches_bf16_operand_reference(M, I, H, onehot):
@@ -101,10 +103,10 @@ def test_lstm_cell_rows_struct_entry_bf16_rows_fast_gates(M, I, H):
 
 @pytest.mark.parametrize("M,onehot", [(384, False), (1024, False), (1024, True), (500, False)])
 def test_lstm_cell_rows_bf16_state_copies_are_bit_identical(M, onehot):
-    """Round 5: from 384 rows on the beam search's LM cells read their operand rows from bf16 copies (x = the layer below's h_out_bf16,
-    h = the gathered copy of the step before) instead of converting the fp32 rows while staging them.  The copy is the staging's own
-    rounding, so c' and h' must be BIT-identical to the fp32-row launch, and h_out_bf16 must be h' rounded to nearest even.  Below
-    384 rows (32-row workgroups) the options are refused."""
+    """Round 5: from 384 rows on (CharRNN.TWIN_MIN_ROWS) the beam search's LM cells read their operand rows from bf16 copies (x = the layer
+    below's h_out_bf16, h = the gathered copy of the step before) instead of converting the fp32 rows while staging them.  The copy is
+    the staging's own rounding, so c' and h' must be BIT-identical to the fp32-row launch, and h_out_bf16 must be h' rounded to nearest
+    even.  The kernel takes the options from 128 rows on (the pipelined body); below, the unpipelined body refuses them."""
     import ctypes
     from las import _hip
     dev, I, H, V, shift = "cuda", 512, 512, 28, 2
@@ -143,7 +145,7 @@ def test_lstm_cell_rows_bf16_state_copies_are_bit_identical(M, onehot):
     assert rc0 == 0 and rc1 == 0
     assert torch.equal(c0, c1) and torch.equal(h0, h1)
     assert torch.equal(hb0, h0.to(torch.bfloat16)) and torch.equal(hb1, hb0)
-    # 32-row workgroups do not take the options
+    # below 128 rows (the unpipelined body) the options are refused
     a = _hip.LstmCellArgs()
     hs_ = h[:64].to(torch.bfloat16).contiguous()
     c2, h2 = torch.empty(64, H, device=dev), torch.empty(64, H, device=dev)
