@@ -43,6 +43,7 @@
 //                      still covers whole cache lines).  A row is read twice, for the two windows of the cross-fade, the second
 //                      time from cache.
 #include "las_common.h"
+#include "bf_fft.h"
 #include <math.h>
 #include <limits.h>
 
@@ -55,37 +56,11 @@ constexpr int BP_CHUNK_ENTRIES = 16384;               // back-pointers staged pe
 constexpr int TRACK_ROWS = 8;                         // rows of r the tracker stages ahead
 constexpr float PHAT_EPS = 1e-12f;
 
-template <bool I16>
-__device__ __forceinline__ float sample_at(const void* __restrict__ x, long long i) {
-    if (I16) return (float)((const short*)x)[i] / 32767.0f;
-    return ((const float*)x)[i];
-}
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
 __global__ __launch_bounds__(256) void bf_tables_kernel(const double* __restrict__ hann, const double* __restrict__ tw, int L, int M,
                                                         float* __restrict__ hann_f, float2* __restrict__ tw_f) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < L) hann_f[i] = (float)hann[i];
     if (i <= M) tw_f[i] = make_float2((float)tw[2 * i], (float)tw[2 * i + 1]);
-}
-
-// in-place radix-2 decimation-in-time FFT of M = 2^lgM complex points in LDS (input bit-reversed, output in order); tw[k] = exp(-2 pi i
-// k / NF), NF = 2^lgNF >= 2 M.  Every thread of the workgroup calls it; it ends with a barrier.
-__device__ __forceinline__ void fft_lds(float2* z, int lgM, const float2* __restrict__ tw, int lgNF) {
-    const int nb = 1 << (lgM - 1);
-    for (int st = 0; st < lgM; ++st) {
-        const int half = 1 << st;
-        for (int b = threadIdx.x; b < nb; b += blockDim.x) {
-            const int j = b & (half - 1);
-            const int i0 = ((b >> st) << (st + 1)) + j, i1 = i0 + half;
-            const float2 t = tw[j << (lgNF - 1 - st)];                // exp(-2 pi i j / (2 half))
-            const float2 v = cmul(t, z[i1]), u = z[i0];
-            z[i0] = make_float2(u.x + v.x, u.y + v.y);
-            z[i1] = make_float2(u.x - v.x, u.y - v.y);
-        }
-        __syncthreads();
-    }
 }
 
 // window w of channel row `row` times the Hann table, zero-padded to NF, as M complex points z[m] = x[2m] + i x[2m+1], bit-reversed
@@ -102,28 +77,10 @@ __device__ __forceinline__ void load_window(float2* z, int lgM, const void* __re
     }
 }
 
-// X[k], 0 <= k <= M, of the real sequence whose packed transform is Z: X = E + W^k O, E = (Z[k] + conj Z[M-k]) / 2, O = (Z[k] - conj Z[M-k]) / 2i
-__device__ __forceinline__ float2 split_at(const float2* Z, int k, int M, const float2* __restrict__ tw) {
-    const float2 a = Z[k & (M - 1)], b = Z[(M - k) & (M - 1)];
-    const float2 e = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
-    const float2 o = make_float2(0.5f * (a.y + b.y), -0.5f * (a.x - b.x));
-    const float2 wo = cmul(tw[k], o);
-    return make_float2(e.x + wo.x, e.y + wo.y);
-}
-
 __device__ __forceinline__ float2 phat(float2 xc, float2 xr) {
     const float2 p = make_float2(xc.x * xr.x + xc.y * xr.y, xc.y * xr.x - xc.x * xr.y);      // xc conj(xr)
     const float inv = 1.0f / fmaxf(sqrtf(p.x * p.x + p.y * p.y), PHAT_EPS);
     return make_float2(p.x * inv, p.y * inv);
-}
-
-// the packed point k of the inverse transform, conjugated: conj(E + i O), E = (Ga + conj Gb) / 2, O = (Ga - conj Gb) / 2 conj(tw[k]);
-// Ga = G[k], Gb = G[M - k]
-__device__ __forceinline__ float2 unsplit_conj(float2 ga, float2 gb, float2 t) {
-    const float2 e = make_float2(0.5f * (ga.x + gb.x), 0.5f * (ga.y - gb.y));
-    const float2 h = make_float2(0.5f * (ga.x - gb.x), 0.5f * (ga.y + gb.y));
-    const float2 o = cmul(h, make_float2(t.x, -t.y));
-    return make_float2(e.x - o.y, -(e.y + o.x));
 }
 
 template <bool I16>

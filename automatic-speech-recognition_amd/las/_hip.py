@@ -291,6 +291,16 @@ _SIGS = {
                              c_size_t, c_void_p]),
     "las_tdoa_track": (c_int, [c_void_p, c_int, c_longlong, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "las_delay_sum": (c_int, [c_void_p, c_int, c_longlong, c_int, c_longlong, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "las_mvdr_frames": (c_longlong, [c_longlong, c_int]),
+    "las_mvdr_blocks": (c_longlong, [c_longlong, c_int]),
+    "las_mvdr_workspace_bytes": (c_size_t, [c_int, c_longlong, c_int, c_int]),
+    "las_mvdr_mask": (c_int, [c_void_p, c_int, c_longlong, c_int, c_longlong, c_int, c_int, c_double, c_double, c_int, c_void_p, c_void_p,
+                              c_void_p, c_size_t, c_void_p]),
+    "las_mvdr_cov": (c_int, [c_void_p, c_int, c_longlong, c_int, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_size_t, c_void_p]),
+    "las_mvdr_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_longlong, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    "las_mvdr_apply": (c_int, [c_void_p, c_int, c_longlong, c_int, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_size_t, c_void_p]),
 }
 
 

@@ -39,6 +39,9 @@ def add_diarize_flags(parser):
 
 
 BEAMFORM_DEFAULTS = dict(bf_window_ms=500.0, bf_max_delay_ms=10.0, bf_jump_penalty=0.01, bf_ref=0)
+# the flags of --bf_method mvdr; --mvdr_floor_db: None = as --vad_floor_db
+MVDR_DEFAULTS = dict(mvdr_frame_ms=32.0, mvdr_block_ms=2000.0, mvdr_top_db=25.0, mvdr_floor_db=None, mvdr_pad_ms=100.0, mvdr_loading=1e-3)
+DELAYSUM_ONLY = ("bf_window_ms", "bf_max_delay_ms", "bf_jump_penalty")
 
 
 def add_beamform_flags(parser):
@@ -51,20 +54,53 @@ def add_beamform_flags(parser):
     parser.add_argument("--bf_jump_penalty", type=float, default=None, help="Viterbi penalty per sample of lag change per window (default 0.01).")
     parser.add_argument("--bf_ref", type=int, default=None, help="The reference channel (default 0).")
     parser.add_argument("--beamform_wav", type=str, default="", metavar="DIR", help="Also write every beamformed file as DIR/<stem>.wav (16-bit).")
+    parser.add_argument("--bf_method", type=str, default="delaysum", choices=("delaysum", "mvdr"), help="delaysum: the tracked delays, whole-"
+                        "sample shifts and a sum.  mvdr: a mask-driven MVDR beamformer in the STFT domain (noise covariance from the frames an "
+                        "energy rule calls non-speech, speech covariance per block), which also cancels directional disturbances.")
+    parser.add_argument("--mvdr_frame_ms", type=float, default=None, help="mvdr: the frame is the next power of two samples at or above this (default 32).")
+    parser.add_argument("--mvdr_block_ms", type=float, default=None, help="mvdr: the weights are recomputed per block of this length (default 2000).")
+    parser.add_argument("--mvdr_top_db", type=float, default=None, help="mvdr: speech = frames within this many dB of the loudest frame of "
+                        "--bf_ref (default 25); everything else trains the noise covariance.")
+    parser.add_argument("--mvdr_floor_db", type=float, default=None, help="mvdr: absolute floor of the mask rule (default: --vad_floor_db).")
+    parser.add_argument("--mvdr_pad_ms", type=float, default=None, help="mvdr: the speech frames are widened by this much either way (default 100).")
+    parser.add_argument("--mvdr_loading", type=float, default=None, help="mvdr: diagonal loading of the noise covariance, relative to its mean "
+                        "diagonal (default 1e-3).")
 
 
 def check_beamform_flags(args):
     """--beamform and its values: refusals before any audio is read; the defaults filled in (--bf_ref against a file's channels: at load time)"""
     given = [k for k in BEAMFORM_DEFAULTS if getattr(args, k, None) is not None]
+    mvdr = [k for k in MVDR_DEFAULTS if getattr(args, k, None) is not None]
+    method = getattr(args, "bf_method", None) or "delaysum"
+    if method not in ("delaysum", "mvdr"):
+        raise ValueError("--bf_method %r: delaysum or mvdr" % (method,))
     if not getattr(args, "beamform", False):
         if given or getattr(args, "beamform_wav", ""):
             raise ValueError("--%s sets the beamformer of --beamform True: give both" % (given[0] if given else "beamform_wav"))
+        if method == "mvdr":
+            raise ValueError("--bf_method mvdr chooses the beamformer of --beamform True: give both")
+        if mvdr:
+            raise ValueError("--%s sets the beamformer of --beamform True --bf_method mvdr: give all three" % mvdr[0])
         return False
+    if method != "mvdr" and mvdr:
+        raise ValueError("--%s sets the beamformer of --bf_method mvdr: give both" % mvdr[0])
+    if method == "mvdr":
+        idle = [k for k in DELAYSUM_ONLY if getattr(args, k, None) is not None]
+        if idle:
+            raise ValueError("--%s sets the delay tracker of --bf_method delaysum and would do nothing with --bf_method mvdr: use one of them" % idle[0])
     for k, v in BEAMFORM_DEFAULTS.items():
         if getattr(args, k, None) is None:
             setattr(args, k, v)
     from las import beamform as BF                                     # (las.beamform is imported only when the flag is given)
     BF.check_values(args.bf_window_ms, args.bf_max_delay_ms, args.bf_jump_penalty, args.bf_ref)
+    if method == "mvdr":
+        for k, v in MVDR_DEFAULTS.items():
+            if getattr(args, k, None) is None:
+                setattr(args, k, v)
+        if args.mvdr_floor_db is None:
+            floor_db = getattr(args, "vad_floor_db", None)
+            args.mvdr_floor_db = -70.0 if floor_db is None else floor_db      # (las.vad.DEFAULTS["vad_floor_db"])
+        BF.check_mvdr_values(args.mvdr_frame_ms, args.mvdr_block_ms, args.mvdr_top_db, args.mvdr_floor_db, args.mvdr_pad_ms, args.mvdr_loading)
     return True
 
 

@@ -17,6 +17,7 @@
     python transcribe.py --coverage_weight 0.3 --overattend_weight 0.7 a.wav ...   (attention coverage scored in the beam search)
     python transcribe.py --segment True --diarize True meeting.wav ...  (who spoke when: every segment labelled with its speaker)
     python transcribe.py --beamform True array.wav ...                 (microphone arrays: delay-and-sum to one channel first)
+    python transcribe.py --beamform True --bf_method mvdr array.wav ...   (... or a mask-driven MVDR beamformer: cancels directional noise)
 
 With --timestamps the best hypothesis is aligned to the encoder frames by the CTC head (las.align, csrc/ctc_align.hip: a Viterbi pass
 over the head's log-probabilities) and every line is {"text", "score", "words": [{"word", "start", "end"}]}: times in seconds, None when
@@ -87,6 +88,18 @@ untouched; the output records are what they are without the flag.  --beamform_wa
 DIR/<stem>.wav, 16-bit at the file's rate.  No trained model is involved, nobody has measured a word error rate with it, and no
 default has been tuned on a real room.  A --bf_* value or --beamform_wav without --beamform True is refused before audio is read;
 without the flag las.beamform is not imported and a multi-channel file is refused as before.
+
+With --beamform True --bf_method mvdr (csrc/mvdr.hip) the channels are combined by an MVDR beamformer in the STFT domain
+instead: frames of --mvdr_frame_ms (the next power of two samples; 32) every half frame; the frames of --bf_ref within --mvdr_top_db (25)
+of its loudest frame and over --mvdr_floor_db (as --vad_floor_db), widened by --mvdr_pad_ms (100), are speech and every other frame
+trains the noise covariance; the speech covariance and the weights are taken per block of --mvdr_block_ms (2000), with
+--mvdr_loading (1e-3) on the noise covariance's diagonal.  It needs no delays and no geometry and cancels a directional disturbance,
+which delay-and-sum cannot.  A file whose mask leaves no noise frame or no speech frame comes out as its reference channel, with a
+one-line warning on stderr that names --mvdr_top_db (a disturbance as loud as the talker needs a small value, a few dB).  A --mvdr_*
+value without --bf_method mvdr, --bf_method mvdr without --beamform True, and --bf_window_ms, --bf_max_delay_ms or --bf_jump_penalty
+with --bf_method mvdr are refused before audio is read.  Everything downstream is as with delay-and-sum.  Not built: online or
+recursive covariance updates, GEV / rank-1 variants, a learned mask, cross-fades between blocks, and handing y to the front end on
+the device.
 
 The files are read with preprocess.read_audio (.flac needs `soundfile`), `--decode_batch` of them at a time go through the device front
 end (las.frontend.FeatureExtractor: waveform -> feature cube, csrc/frontend.hip; a file at another rate than --sample_rate is resampled
@@ -181,7 +194,7 @@ def main(argv=None):
 
     def load(i):
         audio, fs = (waves[i], args.sample_rate) if waves is not None else read_audio(args.audio[i])
-        if beamformer is not None and audio.ndim == 2 and audio.shape[1] >= 2:      # one upload, three calls, one read-back per file
+        if beamformer is not None and audio.ndim == 2 and audio.shape[1] >= 2:      # one upload, three (mvdr: four) calls, one read-back per file
             audio, _ = beamformer.enhance(audio, int(fs))
             if args.beamform_wav:
                 BF.write_wav(os.path.join(args.beamform_wav, os.path.splitext(os.path.basename(args.audio[i]))[0] + ".wav"), audio, fs)

@@ -1365,6 +1365,69 @@ int       las_tdoa_track(const float* r, int C, long long Wn, int D, int ref, do
 int       las_delay_sum(const void* x, int x_i16, long long ld, int C, long long n, int L, long long Wn,
                         const int* tau, const float* a, float* y, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K19  microphone arrays, adaptive: a mask-driven MVDR (minimum-variance distortionless-response) beamformer in the STFT
+ * domain, in Souden's reference-channel form (Souden, Benesty, Affes 2010): the noise covariance from the frames an energy rule
+ * calls non-speech, the speech covariance per block of frames, no array geometry, no delay estimate, no steering vector.  No trained
+ * model.  Plain arguments, no struct (as K18).  One recording per call; every pointer is a device pointer.  All work goes on the
+ * caller's stream, no atomics, no cross-workgroup synchronisation: every output value is computed by one thread or one workgroup in
+ * a fixed order, and two calls give the same bits.  Samples at or behind n in a row are never read.
+ *   geometry   x [C, ld], int16 (x_i16 != 0; widened as v / 32767) or fp32; 2 <= C <= LAS_BF_MAX_CHANNELS; n <= ld.  The frame length
+ *              NF is a power of two, 64 <= NF <= LAS_MVDR_MAX_FFT; the hop Hs = NF / 2; K = NF / 2 + 1 bins.
+ *              Tf = las_mvdr_frames(n, NF) = ceil(n / Hs) + 1 (< 0: bad arguments); frame t covers the samples [(t - 1) Hs, (t + 1) Hs),
+ *              reads outside [0, n) are 0: every sample lies in exactly two frames.  The window win[i] = sin(pi (i + 0.5) / NF) serves
+ *              analysis and synthesis (win[i]^2 + win[i + Hs]^2 = 1: the pair reconstructs exactly).  win: double [NF]; twiddle: double
+ *              [NF / 2 + 1, 2], (cos, -sin)(2 pi k / NF) -- the caller computes both in double, a call rounds them to fp32 once (as
+ *              las_gcc_phat); the transforms run in fp32: X_c[t, k] = FFT_NF(win . x_c[frame t])[k].  Blocks of Bf >= 1 frames: block b
+ *              holds the frames [b Bf, min(Tf, (b + 1) Bf)), Nb = las_mvdr_blocks(Tf, Bf) = ceil(Tf / Bf) (< 0: bad arguments).
+ *              Complex doubles are interleaved (re, im).  ws >= las_mvdr_workspace_bytes(C, Tf, NF, Bf) (0: bad arguments), 8-byte
+ *              aligned, the same buffer for the calls of one recording: the fp32 tables, the frame energies of las_mvdr_mask, and
+ *              the partial sums las_mvdr_cov's first launch hands to its last two.
+ *
+ * las_mvdr_mask   m fp32 [Tf] from channel ref alone, by las_vad's rule on these frames:  e[t] (double) = the sum over the frame's
+ *   samples, in ascending order from 0, of x x with x widened to double (no window; reads outside [0, n) are 0);  emax = max_t e[t];
+ *   thr = max(emax * ratio, floor), one multiply;  raw[t] = e[t] >= thr && e[t] > 0;  m[t] = 1 if any raw[t'] with |t' - t| <= hang,
+ *   else 0.  energy: double [Tf] or NULL.  ratio in (0, 1]; floor >= 0, finite; hang >= 0.  Three launches.
+ *
+ * las_mvdr_cov   takes any m with values in [0, 1] (not checked: the array is on the device).  s_t = (double) m[t], q_t = 1.0 - s_t.
+ *   counts double [1 + Nb]: counts[1 + b] = M_b = sum_{t in b} s_t in ascending t; counts[0] = N0 = sum_b (sum_{t in b} q_t), the
+ *   inner sums in ascending t, the outer in ascending b.  phi_n [K, C, C] complex double:  phi_n[k][i][j] = (sum_t q_t X_i[t, k]
+ *   conj(X_j[t, k])) / N0, zeros where N0 == 0;  phi_y [Nb, K, C, C]:  phi_y[b][k][i][j] = (sum_{t in b} s_t X_i conj(X_j)) / M_b,
+ *   zeros where M_b == 0.  Both exactly Hermitian as stored (the lower triangle the conjugate of the upper, the diagonal's imaginary
+ *   part 0).  WHERE THE SUMS ARE ROUNDED: s_t and q_t are rounded to fp32; a block's frames are cut into tiles of at most 256
+ *   consecutive frames (fewer where that gives the device about a thousand tiles); within a tile the products and the sums are
+ *   fp32 (fused multiply-adds, in ascending t); the tiles' sums are added in double, in ascending tile order, and divided in
+ *   double.  Six launches (tables; tiles; the counts, two; phi_y; phi_n).
+ *
+ * las_mvdr_weights   w [Nb, K, C] complex double, valid int32 [Nb, K]; all in double, per (b, k):  tn = Re tr(phi_n[k]) / C;
+ *   A = phi_n[k] + loading tn I (loading > 0, finite);  P = phi_y[b][k] - phi_n[k];  G = A^-1 P from a Cholesky factorisation of A;
+ *   g = Re tr(G), the diagonal added in channel order;  valid = (N0 > 0 && M_b > 0 && tn > 0 && g > 1e-6) (an A that does not
+ *   factorise gives g = NaN: not valid);  where valid, w_raw[c] = G[c][ref] / g.  A hold pass per bin over the blocks:  w[b][k] =
+ *   w_raw of the nearest valid block b' <= b; if there is none, of the nearest valid b' > b; if bin k has no valid block, the unit
+ *   vector e_ref.  valid reports the test, not the hold.  Two launches, no workspace.
+ *
+ * las_mvdr_apply   y fp32 [n]:  b(t) = t / Bf;  Y[t, k] = sum_c conj(w[b(t)][k][c]) X_c[t, k], in channel order in fp32, w rounded to
+ *   fp32 once; the imaginary parts of Y[t, 0] and Y[t, NF / 2] are dropped;  f_t = win . IFFT_NF(Y[t, .]) (the Hermitian extension
+ *   of the K bins);  output segment j, the samples [j Hs, (j + 1) Hs), is f_j's second half plus f_j+1's first half, in that
+ *   order.  With w = e_ref everywhere y is x_ref up to the fp32 transforms' error.  Two launches.
+ *
+ * Refused on the host before anything is launched (< 0, las_last_error): a NULL pointer (but energy); C, NF, n, ld, ref, Bf, Nb, ratio,
+ * floor, hang, loading outside the above; a workspace that is too small or misaligned.
+ */
+#define LAS_MVDR_MAX_FFT 1024
+long long las_mvdr_frames(long long n, int NF);
+long long las_mvdr_blocks(long long Tf, int Bf);
+size_t    las_mvdr_workspace_bytes(int C, long long Tf, int NF, int Bf);
+int       las_mvdr_mask(const void* x, int x_i16, long long ld, int C, long long n, int ref, int NF, double ratio, double floor,
+                        int hang, float* m, double* energy, void* ws, size_t ws_bytes, void* stream);
+int       las_mvdr_cov(const void* x, int x_i16, long long ld, int C, long long n, int NF, int Bf, const float* m,
+                       const double* win, const double* twiddle, double* counts, double* phi_n, double* phi_y,
+                       void* ws, size_t ws_bytes, void* stream);
+int       las_mvdr_weights(const double* phi_n, const double* phi_y, const double* counts, int C, int NF, long long Nb, int ref,
+                           double loading, double* w, int* valid, void* stream);
+int       las_mvdr_apply(const void* x, int x_i16, long long ld, int C, long long n, int NF, int Bf, const double* w,
+                         const double* win, const double* twiddle, float* y, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
