@@ -7,17 +7,16 @@
 // Everything runs on the caller's stream; no atomics, no cross-workgroup synchronisation: every output value is computed by one
 // thread in a fixed order, so two calls give the same bits.
 //
-//   bf_tables_kernel   the caller's double tables (Hann window, exp(-2 pi i k / NF)) rounded to fp32 once, into the workspace.
+// The windowed transform (the fp32 tables, the packed loader, the FFT in LDS, the real-FFT split and the way back) is bf_fft.h's,
+// shared with mvdr.hip.
 //   bf_gcc_kernel      one workgroup per WINDOW, which keeps the window's channels to itself (the alternative -- spectra through the
 //                      workspace, a grid over (window, channel) -- is in DESIGN 7v with what it would cost).  Two LDS buffers of NF / 2
 //                      complex fp32 points (64 KiB each at NF = 16384): A holds the reference channel's spectrum X_ref[0 .. NF/2],
-//                      computed once per window; B is the work buffer.  Per channel: the windowed samples are packed two to a
-//                      complex point and stored bit-reversed, a radix-2 decimation-in-time FFT of NF / 2 points runs in B, the
-//                      real-FFT split gives X_c[k] and X_c[NF/2 - k] in registers, G = X_c conj X_ref / max(|.|, 1e-12), the inverse
-//                      split packs the Hermitian G into NF / 2 complex points (conjugated and bit-reversed: the inverse transform
-//                      is the forward one between two conjugations), the same FFT runs again and the lags -D .. D are read out.
-//                      The reference channel's own row skips the forward transform (its spectrum is A) and is otherwise computed
-//                      like any other.  2 C transforms per window.
+//                      computed once per window; B is the work buffer.  Per channel: the window is loaded and transformed in B, the
+//                      split gives X_c[k] and X_c[NF/2 - k] in registers, G = X_c conj X_ref / max(|.|, 1e-12), the Hermitian G is
+//                      packed back into B (through registers: B is source and destination), transformed again and the lags
+//                      -D .. D are read out.  The reference channel's own row skips the forward transform (its spectrum is A) and
+//                      is otherwise computed like any other.  2 C transforms per window.
 //   bf_track_kernel    one WAVE per channel steps through the windows, score in LDS in double.  The linear penalty splits the
 //                      maximisation into two sweeps: the best predecessor s' <= s maximises u[s'] = score[s'] + gamma s' (a prefix
 //                      maximum), the best s' >= s maximises score[s'] - gamma s' (a suffix maximum).  Both are wave scans (six
@@ -56,27 +55,6 @@ constexpr int BP_CHUNK_ENTRIES = 16384;               // back-pointers staged pe
 constexpr int TRACK_ROWS = 8;                         // rows of r the tracker stages ahead
 constexpr float PHAT_EPS = 1e-12f;
 
-__global__ __launch_bounds__(256) void bf_tables_kernel(const double* __restrict__ hann, const double* __restrict__ tw, int L, int M,
-                                                        float* __restrict__ hann_f, float2* __restrict__ tw_f) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < L) hann_f[i] = (float)hann[i];
-    if (i <= M) tw_f[i] = make_float2((float)tw[2 * i], (float)tw[2 * i + 1]);
-}
-
-// window w of channel row `row` times the Hann table, zero-padded to NF, as M complex points z[m] = x[2m] + i x[2m+1], bit-reversed
-template <bool I16>
-__device__ __forceinline__ void load_window(float2* z, int lgM, const void* __restrict__ x, long long row, long long t0, long long n, int L,
-                                            const float* __restrict__ hann_f) {
-    const int M = 1 << lgM;
-    for (int m = threadIdx.x; m < M; m += blockDim.x) {
-        const int i = 2 * m;
-        float a = 0.f, b = 0.f;
-        if (i < L && t0 + i < n) a = hann_f[i] * sample_at<I16>(x, row + t0 + i);             // (t0 + i < n <= ld: inside the row)
-        if (i + 1 < L && t0 + i + 1 < n) b = hann_f[i + 1] * sample_at<I16>(x, row + t0 + i + 1);
-        z[__brev((unsigned)m) >> (32 - lgM)] = make_float2(a, b);
-    }
-}
-
 __device__ __forceinline__ float2 phat(float2 xc, float2 xr) {
     const float2 p = make_float2(xc.x * xr.x + xc.y * xr.y, xc.y * xr.x - xc.x * xr.y);      // xc conj(xr)
     const float inv = 1.0f / fmaxf(sqrtf(p.x * p.x + p.y * p.y), PHAT_EPS);
@@ -94,14 +72,14 @@ __global__ __launch_bounds__(NT_MAX) void bf_gcc_kernel(const void* __restrict__
     const long long w = blockIdx.x, t0 = w * (L / 2);
     const int tid = threadIdx.x, nt = blockDim.x;
 
-    load_window<I16>(B, lgM, x, (long long)ref * ld, t0, n, L, hann_f);
+    load_windowed<I16>(B, 0, lgM, 1, x, (long long)ref * ld, 0, t0, n, L, hann_f);
     __syncthreads();
     fft_lds(B, lgM, tw, lgNF);
     for (int k = tid; k <= M; k += nt) A[k] = split_at(B, k, M, tw);
     for (int c = 0; c < C; ++c) {                     // (uniform)
         __syncthreads();                              // B's readers (the split above, the previous channel's read-out) are through
         if (c != ref) {
-            load_window<I16>(B, lgM, x, (long long)c * ld, t0, n, L, hann_f);
+            load_windowed<I16>(B, 0, lgM, 1, x, (long long)c * ld, 0, t0, n, L, hann_f);
             __syncthreads();
             fft_lds(B, lgM, tw, lgNF);
         }
@@ -120,20 +98,13 @@ __global__ __launch_bounds__(NT_MAX) void bf_gcc_kernel(const void* __restrict__
 #pragma unroll
         for (int i = 0; i < PAIRS; ++i) {
             const int k = tid + i * nt;
-            if (k <= M / 2) {
-                B[__brev((unsigned)k) >> (32 - lgM)] = zk[i];
-                if (k > 0 && k < M - k) B[__brev((unsigned)(M - k)) >> (32 - lgM)] = zm[i];
-            }
+            if (k <= M / 2) store_unsplit(B, lgM, k, zk[i], zm[i]);
         }
         __syncthreads();
-        fft_lds(B, lgM, tw, lgNF);                    // B = conj(M z): x[2m] = Re B[m] / M, x[2m+1] = -Im B[m] / M
+        fft_lds(B, lgM, tw, lgNF);
         const float scale = 1.0f / (float)M;
         float* out = r + ((long long)c * Wn + w) * S;
-        for (int j = tid; j < S; j += nt) {
-            const int nn = (j - D) & (NF - 1);        // lag mod NF
-            const float2 v = B[nn >> 1];
-            out[j] = ((nn & 1) ? -v.y : v.x) * scale;
-        }
+        for (int j = tid; j < S; j += nt) out[j] = real_at(B, (j - D) & (NF - 1), scale);     // lag mod NF
     }
 }
 
@@ -382,21 +353,16 @@ __global__ __launch_bounds__(256) void bf_sum_kernel(const void* __restrict__ x,
 }
 
 // the workspace: [back-pointers int16 [C, Wn, 2 D + 1] (las_tdoa_track) | tw fp32 [NF/2 + 1, 2] | hann fp32 [NF] (las_gcc_phat)]
-struct Layout { size_t bp, tw, hann, total; };
+struct Layout { size_t bp; TableSlice tab; size_t total; };
 Layout layout(int C, long long Wn, int NF, int D) {
     Layout l;
-    size_t o = 0;
-    l.bp = o;   o += align256((size_t)C * Wn * (2 * (size_t)D + 1) * sizeof(short));
-    l.tw = o;   o += align256(((size_t)NF / 2 + 1) * sizeof(float2));
-    l.hann = o; o += align256((size_t)NF * sizeof(float));
-    l.total = o;
+    l.bp = 0;
+    l.total = table_slice(align256((size_t)C * Wn * (2 * (size_t)D + 1) * sizeof(short)), NF, l.tab);
     return l;
 }
 
-int log2_of(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 bool geometry_ok(int C, int L, int D, int NF) {
-    return C >= 2 && C <= MAX_C && L >= 2 && (L & 1) == 0 && D >= 1 && D <= MAX_LAG && NF >= 4 && NF <= MAX_NF && (NF & (NF - 1)) == 0 &&
-           (long long)L + D <= NF;
+    return C >= 2 && C <= MAX_C && L >= 2 && (L & 1) == 0 && D >= 1 && D <= MAX_LAG && pow2_in(NF, 4, MAX_NF) && (long long)L + D <= NF;
 }
 int track_chunk(int S) { return clampi(BP_CHUNK_ENTRIES / S, 1, 1024); }   // windows per backtrack chunk
 
@@ -409,7 +375,7 @@ extern "C" long long las_bf_windows(long long n, int L) {
 }
 
 extern "C" size_t las_bf_workspace_bytes(int C, long long Wn, int NF, int D) {
-    if (C < 2 || C > MAX_C || Wn < 1 || Wn > INT32_MAX || NF < 4 || NF > MAX_NF || (NF & (NF - 1)) || D < 1 || D > MAX_LAG) return 0;
+    if (C < 2 || C > MAX_C || Wn < 1 || Wn > INT32_MAX || !pow2_in(NF, 4, MAX_NF) || D < 1 || D > MAX_LAG) return 0;
     return layout(C, Wn, NF, D).total;
 }
 
@@ -418,30 +384,18 @@ extern "C" int las_gcc_phat(const void* x, int x_i16, long long ld, int C, long 
     LAS_ARG(x && hann && twiddle && r && ws, "las_gcc_phat: null pointer (x, hann, twiddle, r, ws)");
     LAS_ARG(geometry_ok(C, L, D, NF), "las_gcc_phat: bad geometry (C=%d, 2..%d; L=%d, even, >= 2; D=%d, 1..%d; NF=%d, a power of two with "
             "L + D <= NF <= %d)", C, MAX_C, L, D, MAX_LAG, NF, MAX_NF);
-    LAS_ARG(n >= 1 && n <= ld && ld <= INT32_MAX, "las_gcc_phat: n=%lld samples in rows of ld=%lld (1 <= n <= ld <= INT32_MAX)", n, ld);
-    LAS_ARG(ref >= 0 && ref < C, "las_gcc_phat: ref=%d outside the %d channels", ref, C);
+    ARG_ROWS("las_gcc_phat", n, ld);
+    ARG_REF("las_gcc_phat", ref, C);
     const long long Wn = las_bf_windows(n, L);
-    const size_t need = las_bf_workspace_bytes(C, Wn, NF, D);
-    LAS_ARG(need && ws_bytes >= need, "las_gcc_phat: workspace of %zu bytes, %zu needed", ws_bytes, need);
-    LAS_ARG(((uintptr_t)ws & 7) == 0, "las_gcc_phat: ws is 8-byte aligned");
-    const Layout l = layout(C, Wn, NF, D);
-    float2* tw_f = (float2*)((char*)ws + l.tw);
-    float* hann_f = (float*)((char*)ws + l.hann);
+    ARG_WS("las_gcc_phat", ws, ws_bytes, las_bf_workspace_bytes(C, Wn, NF, D));
     const int M = NF / 2, lgNF = log2_of(NF);
     const size_t lds = (size_t)(2 * M + 2) * sizeof(float2);
-    static int attr = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(bf_gcc_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (2 * (MAX_NF / 2) + 2) * (int)sizeof(float2)) |
-                      (int)hipFuncSetAttribute(reinterpret_cast<const void*>(bf_gcc_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (2 * (MAX_NF / 2) + 2) * (int)sizeof(float2));
-    LAS_ARG(attr == 0, "hipFuncSetAttribute(bf_gcc_kernel) failed: %d", attr);
+    RAISE_LDS_I16(bf_gcc_kernel, (2 * (MAX_NF / 2) + 2) * sizeof(float2));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bf_tables_kernel, dim3(cdiv(NF, 256)), dim3(256), 0, st, hann, twiddle, L, M, hann_f, tw_f);
-    LAS_LAUNCHED();
+    Tables t;
+    if (const int rc = tables_launch(hann, twiddle, L, NF, ws, layout(C, Wn, NF, D).tab, st, t)) return rc;
     const int nt = clampi(M / 8, 64, NT_MAX);
-    if (x_i16)
-        hipLaunchKernelGGL(bf_gcc_kernel<true>, dim3((unsigned)Wn), dim3(nt), lds, st, x, ld, C, n, ref, L, D, lgNF, hann_f, tw_f, r, Wn);
-    else
-        hipLaunchKernelGGL(bf_gcc_kernel<false>, dim3((unsigned)Wn), dim3(nt), lds, st, x, ld, C, n, ref, L, D, lgNF, hann_f, tw_f, r, Wn);
+    WITH_I16(x_i16, hipLaunchKernelGGL(bf_gcc_kernel<I16>, dim3((unsigned)Wn), dim3(nt), lds, st, x, ld, C, n, ref, L, D, lgNF, t.win, t.tw, r, Wn));
     LAS_LAUNCHED();
     return 0;
 }
@@ -451,11 +405,9 @@ extern "C" int las_tdoa_track(const float* r, int C, long long Wn, int D, int re
     LAS_ARG(r && tau && a && ws, "las_tdoa_track: null pointer (r, tau, a, ws)");
     LAS_ARG(C >= 2 && C <= MAX_C && D >= 1 && D <= MAX_LAG && Wn >= 1 && Wn <= INT32_MAX, "las_tdoa_track: bad geometry (C=%d, 2..%d; D=%d, "
             "1..%d; Wn=%lld, >= 1)", C, MAX_C, D, MAX_LAG, Wn);
-    LAS_ARG(ref >= 0 && ref < C, "las_tdoa_track: ref=%d outside the %d channels", ref, C);
+    ARG_REF("las_tdoa_track", ref, C);
     LAS_ARG(isfinite(gamma) && gamma >= 0.0, "las_tdoa_track: gamma=%g (finite, >= 0)", gamma);
-    const size_t bp_bytes = layout(C, Wn, 4, D).tw;   // (the back-pointers lead the workspace, whatever NF it was sized for)
-    LAS_ARG(ws_bytes >= bp_bytes, "las_tdoa_track: workspace of %zu bytes, %zu needed", ws_bytes, bp_bytes);
-    LAS_ARG(((uintptr_t)ws & 7) == 0, "las_tdoa_track: ws is 8-byte aligned");
+    ARG_WS("las_tdoa_track", ws, ws_bytes, layout(C, Wn, 4, D).tab.tw);      // (the back-pointers lead the workspace, whatever NF it was sized for)
     short* bp = (short*)ws;
     const int S = 2 * D + 1, K = track_chunk(S);
     const size_t lds = track_lds(S, K).total;         // (at most 62 KiB, at 2 D + 1 = 1025: no attribute to raise)
@@ -471,14 +423,11 @@ extern "C" int las_delay_sum(const void* x, int x_i16, long long ld, int C, long
                              float* y, void* stream) {
     LAS_ARG(x && tau && a && y, "las_delay_sum: null pointer (x, tau, a, y)");
     LAS_ARG(C >= 2 && C <= MAX_C && L >= 2 && (L & 1) == 0, "las_delay_sum: bad geometry (C=%d, 2..%d; L=%d, even, >= 2)", C, MAX_C, L);
-    LAS_ARG(n >= 1 && n <= ld && ld <= INT32_MAX, "las_delay_sum: n=%lld samples in rows of ld=%lld (1 <= n <= ld <= INT32_MAX)", n, ld);
+    ARG_ROWS("las_delay_sum", n, ld);
     LAS_ARG(Wn == las_bf_windows(n, L), "las_delay_sum: Wn=%lld, but %lld samples in windows of %d are %lld windows", Wn, n, L, las_bf_windows(n, L));
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)cdiv((n + 3) / 4, 256);
-    if (x_i16)
-        hipLaunchKernelGGL(bf_sum_kernel<true>, dim3(grid), dim3(256), 0, st, x, ld, C, n, L / 2, Wn, tau, a, y);
-    else
-        hipLaunchKernelGGL(bf_sum_kernel<false>, dim3(grid), dim3(256), 0, st, x, ld, C, n, L / 2, Wn, tau, a, y);
+    WITH_I16(x_i16, hipLaunchKernelGGL(bf_sum_kernel<I16>, dim3(grid), dim3(256), 0, st, x, ld, C, n, L / 2, Wn, tau, a, y));
     LAS_LAUNCHED();
     return 0;
 }

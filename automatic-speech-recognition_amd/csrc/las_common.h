@@ -257,6 +257,13 @@ __device__ __forceinline__ u32x2_t granule8_load(__amdgpu_buffer_rsrc_t rs, unsi
     return __builtin_amdgcn_raw_buffer_load_b64(rs, byte_off, 0, 16);
 }
 
+// sample i of a waveform buffer: int16 over 32767 (the front end's scale) or fp32 as it is
+template <bool I16>
+__device__ __forceinline__ float sample_at(const void* __restrict__ x, long long i) {
+    if (I16) return (float)((const short*)x)[i] / 32767.0f;
+    return ((const float*)x)[i];
+}
+
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 __host__ __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }      // (lo <= hi)
 __host__ __device__ inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }                   // workspace carving

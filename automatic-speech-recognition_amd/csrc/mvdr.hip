@@ -7,7 +7,9 @@
 //   las_mvdr_apply    y = the inverse STFT of sum_c conj(w_c) X_c
 // Everything runs on the caller's stream; no atomics, no cross-workgroup synchronisation: every output value is computed by one
 // thread or one workgroup in a fixed order, so two calls give the same bits.  The spectra are never stored: the covariance pass and
-// the apply pass each transform their frames in LDS (bf_fft.h) and read the samples once (the apply pass: 1 + 1 / 16 times).
+// the apply pass each transform their frames in LDS and read the samples once (the apply pass: 1 + 1 / 16 times).  The windowed
+// transform (the fp32 tables, the packed loader, the FFT in LDS, the real-FFT split and the way back) is bf_fft.h's, shared with
+// beamform.hip.
 //
 //   mvdr_energy_kernel   one thread per frame adds the frame's squared samples in ascending order in double (the contract's order).
 //   mvdr_max_kernel      one workgroup: emax.  mvdr_mask_kernel: one thread per frame, the threshold and the dilation by `hang`.
@@ -33,7 +35,7 @@
 //                        vector in registers; the columns' diagonal entries meet in LDS for the trace, and the thread of column
 //                        ref writes w_raw and valid.  mvdr_hold_kernel: one thread per (bin, channel) walks the blocks.
 //   mvdr_apply_kernel    a workgroup owns 16 output segments: it transforms 17 frames (one halo frame), keeps the block's weights
-//                        as fp32 in LDS, Y = sum_c conj(w_c) X_c in channel order, the inverse transform as in las_gcc_phat, the
+//                        as fp32 in LDS, Y = sum_c conj(w_c) X_c in channel order, the inverse transform, the
 //                        window, and every sample it owns is written once: f_j's second half (kept in LDS) plus f_j+1's first.
 #include "las_common.h"
 #include "bf_fft.h"
@@ -52,13 +54,6 @@ constexpr int WT_NT = 256;
 constexpr double G_MIN = 1e-6;
 
 __host__ __device__ constexpr int cov_items(int CP) { return CP == 16 ? 4 : CP == 8 ? 5 : CP == 4 ? 5 : 3; }   // items a thread holds
-
-__global__ __launch_bounds__(256) void mvdr_tables_kernel(const double* __restrict__ win, const double* __restrict__ tw, int NF,
-                                                          float* __restrict__ win_f, float2* __restrict__ tw_f) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < NF) win_f[i] = (float)win[i];
-    if (i <= NF / 2) tw_f[i] = make_float2((float)tw[2 * i], (float)tw[2 * i + 1]);
-}
 
 template <bool I16>
 __global__ __launch_bounds__(64) void mvdr_energy_kernel(const void* __restrict__ x, long long row, long long n, int Hs, long long Tf,
@@ -101,29 +96,6 @@ __global__ __launch_bounds__(256) void mvdr_mask_kernel(const double* __restrict
     m[t] = on ? 1.f : 0.f;
 }
 
-// frame t of the C channels, windowed, as C buffers of M packed points (z[m] = x[2m] + i x[2m+1]) stored bit-reversed
-template <bool I16>
-__device__ __forceinline__ void load_frame(float2* z, int stride, int lgM, int C, const void* __restrict__ x, long long ld, long long n,
-                                           long long t, const float* __restrict__ win_f) {
-    const int M = 1 << lgM;
-    const long long t0 = (t - 1) * M;                 // (Hs = M)
-    for (int e = threadIdx.x; e < (C << lgM); e += blockDim.x) {
-        const int c = e >> lgM, mm = e & (M - 1), i = 2 * mm;
-        const long long s0 = t0 + i;
-        float a = 0.f, b = 0.f;
-        if (s0 >= 0 && s0 < n) a = win_f[i] * sample_at<I16>(x, (long long)c * ld + s0);             // (s0 < n <= ld: inside the row)
-        if (s0 + 1 >= 0 && s0 + 1 < n) b = win_f[i + 1] * sample_at<I16>(x, (long long)c * ld + s0 + 1);
-        z[c * stride + (__brev((unsigned)mm) >> (32 - lgM))] = make_float2(a, b);
-    }
-}
-
-__device__ __forceinline__ float2 split_ab(float2 a, float2 b, float2 t) {      // split_at on the two points it reads
-    const float2 e = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
-    const float2 o = make_float2(0.5f * (a.y + b.y), -0.5f * (a.x - b.x));
-    const float2 wo = cmul(t, o);
-    return make_float2(e.x + wo.x, e.y + wo.y);
-}
-
 // the C packed transforms in place to the spectra X_c[0 .. M] (buffers of stride >= M + 1); ends with a barrier
 __device__ __forceinline__ void split_frames(float2* z, int stride, int lgM, int C, const float2* __restrict__ tw) {
     const int M = 1 << lgM, per = M / 2 + 1;
@@ -131,7 +103,7 @@ __device__ __forceinline__ void split_frames(float2* z, int stride, int lgM, int
         const int c = e / per, k = e - c * per;
         float2* Z = z + c * stride;
         const float2 a = Z[k], b = Z[(M - k) & (M - 1)];
-        const float2 xk = split_ab(a, b, tw[k]), xm = split_ab(b, a, tw[M - k]);
+        const float2 xk = split_pt(a, b, tw[k]), xm = split_pt(b, a, tw[M - k]);
         Z[k] = xk;
         if (k != M - k) Z[M - k] = xm;                // (k = 0 writes the slot M behind the packed points)
     }
@@ -166,7 +138,8 @@ __global__ __launch_bounds__(COV_NT) void mvdr_cov_kernel(const void* __restrict
     __syncthreads();
     for (long long tb = t0; tb < t1; tb += FB) {      // (uniform)
         const int nf = (int)min((long long)FB, t1 - tb);
-        for (int f = 0; f < nf; ++f) load_frame<I16>(z + f * CP * stride, stride, lgM, C, x, ld, n, tb + f, win_f);
+        for (int f = 0; f < nf; ++f)                  // frame t: the samples from (t - 1) Hs on, Hs = M
+            load_windowed<I16>(z + f * CP * stride, stride, lgM, C, x, 0, ld, (tb + f - 1) * M, n, 2 * M, win_f);
         __syncthreads();
         fft_lds_batch(z, lgM, nf * CP, stride, tw, lgNF);
         split_frames(z, stride, lgM, nf * CP, tw);
@@ -433,7 +406,7 @@ __global__ __launch_bounds__(512) void mvdr_apply_kernel(const void* __restrict_
     const float scale = 1.0f / (float)M;
     for (long long t = j0; t <= tl; ++t) {            // (uniform)
         const long long b = t / Bf;
-        load_frame<I16>(z, stride, lgM, C, x, ld, n, t, win_f);
+        load_windowed<I16>(z, stride, lgM, C, x, 0, ld, (t - 1) * M, n, 2 * M, win_f);
         if (b != cur) {                               // (uniform; the previous frame's readers of wl passed the barriers below)
             const double* wb = w + (size_t)b * K * C * 2;
             for (int e = tid; e < K * C; e += nt) {
@@ -457,34 +430,28 @@ __global__ __launch_bounds__(512) void mvdr_apply_kernel(const void* __restrict_
         __syncthreads();
         for (int k = tid; k <= M / 2; k += nt) {
             const float2 gk = Y[k], gm = Y[M - k];
-            B[__brev((unsigned)k) >> (32 - lgM)] = unsplit_conj(gk, gm, tw[k]);
-            if (k > 0 && k < M - k) B[__brev((unsigned)(M - k)) >> (32 - lgM)] = unsplit_conj(gm, gk, tw[M - k]);
+            store_unsplit(B, lgM, k, unsplit_conj(gk, gm, tw[k]), unsplit_conj(gm, gk, tw[M - k]));
         }
         __syncthreads();
-        fft_lds(B, lgM, tw, lgNF);                    // B = conj(M f): f[2m] = Re B[m] / M, f[2m+1] = -Im B[m] / M
+        fft_lds(B, lgM, tw, lgNF);                    // B holds the frame f_t for real_at
         for (int i = tid; i < M; i += nt) {           // the first half of f_t closes the segment t - 1
-            const float2 v = B[i >> 1];
-            const float f = ((i & 1) ? -v.y : v.x) * scale * win_f[i];
+            const float f = real_at(B, i, scale) * win_f[i];
             const long long s = (t - 1) * M + i;
             if (t > j0 && s < n) y[s] = prev[i] + f;
         }
         __syncthreads();                              // prev has been read
-        for (int i = tid; i < M; i += nt) {
-            const float2 v = B[(M + i) >> 1];
-            prev[i] = (((M + i) & 1) ? -v.y : v.x) * scale * win_f[M + i];
-        }
+        for (int i = tid; i < M; i += nt) prev[i] = real_at(B, M + i, scale) * win_f[M + i];
         __syncthreads();
     }
 }
 
 // the workspace: [tw fp32 [NF/2 + 1, 2] | win fp32 [NF] | e double [Tf] | emax double | nb double [Nb] | the tiles' partial sums]
 struct Tiling { int CP, FT, nsplit, KS, slices, nt; long long Nb, ntiles; };
-struct Layout { size_t tw, win, e, emax, nb, part, total; };
+struct Layout { TableSlice tab; size_t e, emax, nb, part, total; };
 
 long long frames_of(long long n, int NF) { return (n + NF / 2 - 1) / (NF / 2) + 1; }
 long long blocks_of(long long Tf, long long Bf) { return (Tf + Bf - 1) / Bf; }
-int log2_of(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-bool fft_ok(int NF) { return NF >= MIN_NF && NF <= MAX_NF && (NF & (NF - 1)) == 0; }
+bool fft_ok(int NF) { return pow2_in(NF, MIN_NF, MAX_NF); }
 
 Tiling tiling(int C, long long Tf, int NF, long long Bf) {
     Tiling t;
@@ -508,9 +475,7 @@ Tiling tiling(int C, long long Tf, int NF, long long Bf) {
 Layout layout(int C, long long Tf, int NF, long long Bf) {
     const Tiling t = tiling(C, Tf, NF, Bf);
     Layout l;
-    size_t o = 0;
-    l.tw = o;   o += align256(((size_t)NF / 2 + 1) * sizeof(float2));
-    l.win = o;  o += align256((size_t)NF * sizeof(float));
+    size_t o = table_slice(0, NF, l.tab);
     l.e = o;    o += align256((size_t)Tf * sizeof(double));
     l.emax = o; o += 256;
     l.nb = o;   o += align256((size_t)t.Nb * sizeof(double));
@@ -567,28 +532,24 @@ extern "C" size_t las_mvdr_workspace_bytes(int C, long long Tf, int NF, int Bf) 
     return layout(C, Tf, NF, Bf).total;
 }
 
-#define MVDR_GEOMETRY(name)                                                                                                                     \
-    LAS_ARG(C >= 2 && C <= MAX_C && fft_ok(NF), name ": bad geometry (C=%d, 2..%d; NF=%d, a power of two, %d..%d)", C, MAX_C, NF, MIN_NF, MAX_NF); \
-    LAS_ARG(n >= 1 && n <= ld && ld <= INT32_MAX, name ": n=%lld samples in rows of ld=%lld (1 <= n <= ld <= INT32_MAX)", n, ld)
+#define MVDR_GEOMETRY(name) \
+    LAS_ARG(C >= 2 && C <= MAX_C && fft_ok(NF), name ": bad geometry (C=%d, 2..%d; NF=%d, a power of two, %d..%d)", C, MAX_C, NF, MIN_NF, MAX_NF)
 
 extern "C" int las_mvdr_mask(const void* x, int x_i16, long long ld, int C, long long n, int ref, int NF, double ratio, double floor, int hang,
                              float* m, double* energy, void* ws, size_t ws_bytes, void* stream) {
     LAS_ARG(x && m && ws, "las_mvdr_mask: null pointer (x, m, ws)");
     MVDR_GEOMETRY("las_mvdr_mask");
-    LAS_ARG(ref >= 0 && ref < C, "las_mvdr_mask: ref=%d outside the %d channels", ref, C);
+    ARG_ROWS("las_mvdr_mask", n, ld);
+    ARG_REF("las_mvdr_mask", ref, C);
     LAS_ARG(ratio > 0.0 && ratio <= 1.0, "las_mvdr_mask: ratio=%g (in (0, 1])", ratio);
     LAS_ARG(isfinite(floor) && floor >= 0.0 && hang >= 0, "las_mvdr_mask: floor=%g (finite, >= 0), hang=%d (>= 0)", floor, hang);
     const long long Tf = frames_of(n, NF);
     const Layout l = layout(C, Tf, NF, 1);
-    LAS_ARG(ws_bytes >= l.nb, "las_mvdr_mask: workspace of %zu bytes, %zu needed", ws_bytes, l.nb);
-    LAS_ARG(((uintptr_t)ws & 7) == 0, "las_mvdr_mask: ws is 8-byte aligned");
+    ARG_WS("las_mvdr_mask", ws, ws_bytes, l.nb);
     double* e = energy ? energy : (double*)((char*)ws + l.e);
     double* emax = (double*)((char*)ws + l.emax);
     hipStream_t st = (hipStream_t)stream;
-    if (x_i16)
-        hipLaunchKernelGGL(mvdr_energy_kernel<true>, dim3(cdiv(Tf, 64)), dim3(64), 0, st, x, (long long)ref * ld, n, NF / 2, Tf, e);
-    else
-        hipLaunchKernelGGL(mvdr_energy_kernel<false>, dim3(cdiv(Tf, 64)), dim3(64), 0, st, x, (long long)ref * ld, n, NF / 2, Tf, e);
+    WITH_I16(x_i16, hipLaunchKernelGGL(mvdr_energy_kernel<I16>, dim3(cdiv(Tf, 64)), dim3(64), 0, st, x, (long long)ref * ld, n, NF / 2, Tf, e));
     LAS_LAUNCHED();
     hipLaunchKernelGGL(mvdr_max_kernel, dim3(1), dim3(1024), 0, st, e, Tf, emax);
     LAS_LAUNCHED();
@@ -601,23 +562,21 @@ extern "C" int las_mvdr_cov(const void* x, int x_i16, long long ld, int C, long 
                             const double* twiddle, double* counts, double* phi_n, double* phi_y, void* ws, size_t ws_bytes, void* stream) {
     LAS_ARG(x && m && win && twiddle && counts && phi_n && phi_y && ws, "las_mvdr_cov: null pointer (x, m, win, twiddle, counts, phi_n, phi_y, ws)");
     MVDR_GEOMETRY("las_mvdr_cov");
+    ARG_ROWS("las_mvdr_cov", n, ld);
     LAS_ARG(Bf >= 1, "las_mvdr_cov: Bf=%d frames per block (>= 1)", Bf);
     const long long Tf = frames_of(n, NF);
     const Layout l = layout(C, Tf, NF, Bf);
-    LAS_ARG(ws_bytes >= l.total, "las_mvdr_cov: workspace of %zu bytes, %zu needed", ws_bytes, l.total);
-    LAS_ARG(((uintptr_t)ws & 7) == 0, "las_mvdr_cov: ws is 8-byte aligned");
+    ARG_WS("las_mvdr_cov", ws, ws_bytes, l.total);
     const Tiling t = tiling(C, Tf, NF, Bf);
     const int K = NF / 2 + 1, lgNF = log2_of(NF);
     LAS_ARG(t.ntiles <= INT32_MAX && t.Nb * K * C * C / 256 < INT32_MAX, "las_mvdr_cov: %lld blocks of %d bins are more than one launch takes", t.Nb, K);
-    float2* tw_f = (float2*)((char*)ws + l.tw);
-    float* win_f = (float*)((char*)ws + l.win);
     double* nb = (double*)((char*)ws + l.nb);
     float2* part = (float2*)((char*)ws + l.part);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(mvdr_tables_kernel, dim3(cdiv(NF, 256)), dim3(256), 0, st, win, twiddle, NF, win_f, tw_f);
-    LAS_LAUNCHED();
-    const int rc = x_i16 ? launch_cov<true>(t, C, x, ld, n, lgNF, Tf, Bf, m, win_f, tw_f, part, st)
-                         : launch_cov<false>(t, C, x, ld, n, lgNF, Tf, Bf, m, win_f, tw_f, part, st);
+    Tables tab;
+    int rc = tables_launch(win, twiddle, NF, NF, ws, l.tab, st, tab);
+    if (rc) return rc;
+    WITH_I16(x_i16, rc = launch_cov<I16>(t, C, x, ld, n, lgNF, Tf, Bf, m, tab.win, tab.tw, part, st));
     if (rc) return rc;
     hipLaunchKernelGGL(mvdr_counts_kernel, dim3(cdiv(t.Nb, 256)), dim3(256), 0, st, m, Tf, (long long)Bf, t.Nb, counts, nb);
     LAS_LAUNCHED();
@@ -633,9 +592,9 @@ extern "C" int las_mvdr_cov(const void* x, int x_i16, long long ld, int C, long 
 extern "C" int las_mvdr_weights(const double* phi_n, const double* phi_y, const double* counts, int C, int NF, long long Nb, int ref, double loading,
                                 double* w, int* valid, void* stream) {
     LAS_ARG(phi_n && phi_y && counts && w && valid, "las_mvdr_weights: null pointer (phi_n, phi_y, counts, w, valid)");
-    LAS_ARG(C >= 2 && C <= MAX_C && fft_ok(NF), "las_mvdr_weights: bad geometry (C=%d, 2..%d; NF=%d, a power of two, %d..%d)", C, MAX_C, NF, MIN_NF, MAX_NF);
+    MVDR_GEOMETRY("las_mvdr_weights");
     LAS_ARG(Nb >= 1 && Nb <= INT32_MAX, "las_mvdr_weights: Nb=%lld blocks (>= 1)", Nb);
-    LAS_ARG(ref >= 0 && ref < C, "las_mvdr_weights: ref=%d outside the %d channels", ref, C);
+    ARG_REF("las_mvdr_weights", ref, C);
     LAS_ARG(isfinite(loading) && loading > 0.0, "las_mvdr_weights: loading=%g (finite, > 0)", loading);
     const int K = NF / 2 + 1;
     const long long splits = clampi(cdiv(Nb * C, 4 * WT_NT), 1, 64), per = (Nb + splits - 1) / splits;
@@ -652,29 +611,20 @@ extern "C" int las_mvdr_apply(const void* x, int x_i16, long long ld, int C, lon
                               const double* twiddle, float* y, void* ws, size_t ws_bytes, void* stream) {
     LAS_ARG(x && w && win && twiddle && y && ws, "las_mvdr_apply: null pointer (x, w, win, twiddle, y, ws)");
     MVDR_GEOMETRY("las_mvdr_apply");
+    ARG_ROWS("las_mvdr_apply", n, ld);
     LAS_ARG(Bf >= 1, "las_mvdr_apply: Bf=%d frames per block (>= 1)", Bf);
     const long long Tf = frames_of(n, NF);
     const Layout l = layout(C, Tf, NF, Bf);
-    LAS_ARG(ws_bytes >= l.e, "las_mvdr_apply: workspace of %zu bytes, %zu needed", ws_bytes, l.e);
-    LAS_ARG(((uintptr_t)ws & 7) == 0, "las_mvdr_apply: ws is 8-byte aligned");
-    float2* tw_f = (float2*)((char*)ws + l.tw);
-    float* win_f = (float*)((char*)ws + l.win);
+    ARG_WS("las_mvdr_apply", ws, ws_bytes, l.e);
     const int M = NF / 2, lgNF = log2_of(NF);
     const size_t lds = apply_lds(C, NF);              // at most (2 x 16 x 513 + 513 + 512) x 8 + 2048 = 138 KiB
-    static int attr = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(mvdr_apply_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)apply_lds(MAX_C, MAX_NF)) |
-                      (int)hipFuncSetAttribute(reinterpret_cast<const void*>(mvdr_apply_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)apply_lds(MAX_C, MAX_NF));
-    LAS_ARG(attr == 0, "hipFuncSetAttribute(mvdr_apply_kernel) failed: %d", attr);
+    RAISE_LDS_I16(mvdr_apply_kernel, apply_lds(MAX_C, MAX_NF));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(mvdr_tables_kernel, dim3(cdiv(NF, 256)), dim3(256), 0, st, win, twiddle, NF, win_f, tw_f);
-    LAS_LAUNCHED();
+    Tables tab;
+    if (const int rc = tables_launch(win, twiddle, NF, NF, ws, l.tab, st, tab)) return rc;
     const int nt = clampi((C * M / 8 + 63) / 64 * 64, 64, 512);
     const unsigned grid = (unsigned)cdiv(Tf - 1, APPLY_SEG);
-    if (x_i16)
-        hipLaunchKernelGGL(mvdr_apply_kernel<true>, dim3(grid), dim3(nt), lds, st, x, ld, C, n, lgNF, Tf, (long long)Bf, w, win_f, tw_f, y);
-    else
-        hipLaunchKernelGGL(mvdr_apply_kernel<false>, dim3(grid), dim3(nt), lds, st, x, ld, C, n, lgNF, Tf, (long long)Bf, w, win_f, tw_f, y);
+    WITH_I16(x_i16, hipLaunchKernelGGL(mvdr_apply_kernel<I16>, dim3(grid), dim3(nt), lds, st, x, ld, C, n, lgNF, Tf, (long long)Bf, w, tab.win, tab.tw, y));
     LAS_LAUNCHED();
     return 0;
 }

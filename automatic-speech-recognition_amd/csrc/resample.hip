@@ -27,11 +27,6 @@ constexpr int TABLE_LDS_MAX = 4096;                   // table entries kept in L
 constexpr int RATIO_MAX = 1 << 20;                    // L, M: (tile - 1) * M + L stays below 2^31
 constexpr int TAPS_MAX = 1024;
 
-template <bool I16>
-__device__ __forceinline__ float sample_at(const void* __restrict__ row, long long i) {
-    return I16 ? (float)((const short*)row)[i] / 32767.0f : ((const float*)row)[i];
-}
-
 // the input span of a tile of `tile` outputs: the first output reads from n0 - W + 1, the last up to n0' + W with n0' - n0 <= ((tile - 1) M + L - 1) / L
 long long tile_span(int tile, int L, int M, int W) { return ((long long)(tile - 1) * M + L - 1) / L + 2LL * W; }
 

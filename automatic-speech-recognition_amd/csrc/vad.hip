@@ -45,12 +45,6 @@ __device__ __forceinline__ int frames_of(int n_u, int fl, int step, long long ld
     return min(T, Tmax);
 }
 
-template <bool I16>
-__device__ __forceinline__ float sample_at(const void* __restrict__ samples, long long i) {
-    if (I16) return (float)((const short*)samples)[i] / 32767.0f;
-    return ((const float*)samples)[i];
-}
-
 __device__ __forceinline__ double wave_max_f64(double v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o));

@@ -87,18 +87,20 @@ def mvdr_geometry(frame_ms, block_ms, pad_ms, fs):
     return NF, max(1, int(round(block_ms / hop_ms))), int(round(pad_ms / hop_ms))
 
 
+def twiddle(NF):
+    """exp(-2 pi i k / NF), k = 0 .. NF / 2, float64 [NF / 2 + 1, 2]: the table of csrc/bf_fft.h's transform"""
+    k = np.arange(NF // 2 + 1)
+    return np.stack([np.cos(2.0 * np.pi * k / NF), -np.sin(2.0 * np.pi * k / NF)], axis=1)
+
+
 def mvdr_tables(NF):
     """(win float64 [NF], twiddle float64 [NF / 2 + 1, 2]) as las_mvdr_cov and las_mvdr_apply take them"""
-    k = np.arange(NF // 2 + 1)
-    return (np.sin(np.pi * (np.arange(NF) + 0.5) / NF),
-            np.stack([np.cos(2.0 * np.pi * k / NF), -np.sin(2.0 * np.pi * k / NF)], axis=1))
+    return np.sin(np.pi * (np.arange(NF) + 0.5) / NF), twiddle(NF)
 
 
 def tables(L, NF):
     """(hann float64 [L], twiddle float64 [NF / 2 + 1, 2]) as las_gcc_phat takes them"""
-    hann = 0.5 - 0.5 * np.cos(2.0 * np.pi * (np.arange(L) + 0.5) / L)
-    k = np.arange(NF // 2 + 1)
-    return hann, np.stack([np.cos(2.0 * np.pi * k / NF), -np.sin(2.0 * np.pi * k / NF)], axis=1)
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * (np.arange(L) + 0.5) / L), twiddle(NF)
 
 
 class Beamformer:
@@ -124,10 +126,9 @@ class Beamformer:
         self.device = device
         self._tables = {}                             # (L, NF) -> the two tables on the device
 
-    def enhance(self, audio, fs):
-        """audio [n, C] (int16 or float; C >= 2) at fs Hz -> (y float32 numpy [n], info)"""
-        if self.method == "mvdr":
-            return self.enhance_mvdr(audio, fs)
+    def _open(self, audio, entry, geometry):
+        """what both methods begin with: the checks of the device and of audio [n, C] against the limits of `entry` and --bf_ref, the
+        method's geometry() (which may refuse) and the one upload -> (dev, x [C, n] int16 or float32 on it, i16, n, C, the geometry)"""
         dev = torch.device(self.device if self.device is not None else "cuda")
         if dev.type != "cuda":
             raise RuntimeError("las.beamform needs a ROCm device (got %s); there is no CPU fallback" % dev)
@@ -136,16 +137,22 @@ class Beamformer:
             raise ValueError("enhance takes audio [n, C >= 2], got %s" % (audio.shape,))
         n, C = audio.shape
         if C > MAX_CHANNELS:
-            raise ValueError("%d channels: las_gcc_phat takes %d" % (C, MAX_CHANNELS))
+            raise ValueError("%d channels: %s takes %d" % (C, entry, MAX_CHANNELS))
         if self.ref >= C:
             raise ValueError("--bf_ref %d: the recording has the channels 0 to %d" % (self.ref, C - 1))
-        L, D, NF = geometry(self.window_ms, self.max_delay_ms, int(fs))
+        geo = geometry()
         i16 = audio.dtype == np.int16
         rows = np.ascontiguousarray(audio.T if i16 else audio.T.astype(np.float32, copy=False))
+        return dev, torch.from_numpy(rows).to(dev), i16, n, C, geo            # the one upload
+
+    def enhance(self, audio, fs):
+        """audio [n, C] (int16 or float; C >= 2) at fs Hz -> (y float32 numpy [n], info)"""
+        if self.method == "mvdr":
+            return self.enhance_mvdr(audio, fs)
+        dev, x, i16, n, C, (L, D, NF) = self._open(audio, "las_gcc_phat", lambda: geometry(self.window_ms, self.max_delay_ms, int(fs)))
         lib = _hip.lib()
         Wn = int(lib.las_bf_windows(n, L))
         with torch.cuda.device(dev):
-            x = torch.from_numpy(rows).to(dev)                            # the one upload
             if (L, NF) not in self._tables:
                 self._tables[(L, NF)] = tuple(torch.from_numpy(t).to(dev) for t in tables(L, NF))
             hann, tw = self._tables[(L, NF)]
@@ -165,26 +172,13 @@ class Beamformer:
     def enhance_mvdr(self, audio, fs):
         """--bf_method mvdr: one upload, the four calls of K19, one read-back of y; a one-line warning on stderr where the mask leaves no
         noise frame or no speech frame (a second, small read-back: the counts)"""
-        dev = torch.device(self.device if self.device is not None else "cuda")
-        if dev.type != "cuda":
-            raise RuntimeError("las.beamform needs a ROCm device (got %s); there is no CPU fallback" % dev)
-        audio = np.asarray(audio)
-        if audio.ndim != 2 or audio.shape[1] < 2 or audio.shape[0] < 1:
-            raise ValueError("enhance takes audio [n, C >= 2], got %s" % (audio.shape,))
-        n, C = audio.shape
-        if C > MAX_CHANNELS:
-            raise ValueError("%d channels: las_mvdr_cov takes %d" % (C, MAX_CHANNELS))
-        if self.ref >= C:
-            raise ValueError("--bf_ref %d: the recording has the channels 0 to %d" % (self.ref, C - 1))
-        NF, Bf, hang = mvdr_geometry(self.frame_ms, self.block_ms, self.pad_ms, int(fs))
+        dev, x, i16, n, C, (NF, Bf, hang) = self._open(audio, "las_mvdr_cov",
+                                                       lambda: mvdr_geometry(self.frame_ms, self.block_ms, self.pad_ms, int(fs)))
         ratio, floor = 10.0 ** (-self.top_db / 10.0), NF * 10.0 ** (self.floor_db / 10.0)
-        i16 = audio.dtype == np.int16
-        rows = np.ascontiguousarray(audio.T if i16 else audio.T.astype(np.float32, copy=False))
         lib = _hip.lib()
         Tf = int(lib.las_mvdr_frames(n, NF))
         Nb, K = int(lib.las_mvdr_blocks(Tf, Bf)), NF // 2 + 1
         with torch.cuda.device(dev):
-            x = torch.from_numpy(rows).to(dev)                            # the one upload
             if ("mvdr", NF) not in self._tables:
                 self._tables[("mvdr", NF)] = tuple(torch.from_numpy(t).to(dev) for t in mvdr_tables(NF))
             win, tw = self._tables[("mvdr", NF)]

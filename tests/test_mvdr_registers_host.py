@@ -34,7 +34,7 @@ def report():
 def test_no_mvdr_kernel_uses_scratch_or_spills():
     rep = report()
     names = " ".join(rep)
-    for kernel in ("mvdr_tables_kernel", "mvdr_energy_kernel", "mvdr_max_kernel", "mvdr_mask_kernel", "mvdr_cov_kernel", "mvdr_counts_kernel",
+    for kernel in ("fft_tables_kernel","mvdr_energy_kernel", "mvdr_max_kernel", "mvdr_mask_kernel", "mvdr_cov_kernel", "mvdr_counts_kernel",
                    "mvdr_n0_kernel", "mvdr_phi_y_kernel", "mvdr_phi_n_kernel", "mvdr_weights_kernel", "mvdr_hold_kernel", "mvdr_apply_kernel"):
         assert kernel in names, kernel
     assert len(rep) == 21                             # 8 instantiations of the covariance kernel, 2 each of the energy and apply kernels
