@@ -119,6 +119,7 @@ extern "C" int las_ce_loss(const float* logits, long long sb, long long st, cons
                            size_t ws_bytes, void* stream) {
     LAS_ARG(logits && y && sums && B > 0 && U > 0 && V > 0 && ldy >= U, "las_ce_loss: bad arguments");
     LAS_ARG(!dlogits || scale_ptr, "las_ce_loss: dlogits needs scale_ptr");
+    LAS_ARG(!(smooth & 4) || scale_ptr, "las_ce_loss: bit 2 of smooth (write sums, sums[2] = scaled loss) needs scale_ptr");
     LAS_ARG(ws && ws_bytes >= las_ce_loss_workspace_bytes(B, U), "las_ce_loss: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     float* row_ce = (float*)ws;
@@ -134,7 +135,6 @@ extern "C" int las_ce_loss(const float* logits, long long sb, long long st, cons
     hipLaunchKernelGGL(ce_rows_kernel, cg, dim3(256), 0, s, logits, sb, st, y, ldy, B, U, V,
                        epsilon, smooth, scale_ptr, dlogits, row_ce, row_mask);
     LAS_LAUNCHED();
-    LAS_ARG(!(smooth & 4) || scale_ptr, "las_ce_loss: bit 2 of smooth (write sums, sums[2] = scaled loss) needs scale_ptr");
     hipLaunchKernelGGL(sum2_kernel, dim3(1), dim3(1024), 0, s, (const float*)row_ce, (const float*)row_mask, (long long)B * U, sums,
                        (smooth & 4) ? scale_ptr : (const float*)nullptr);
     LAS_LAUNCHED();

@@ -6,6 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from helpers import grad_errors, make_args, oracle_mode_for, row_mode, synthetic_batch
+from loss_ref import ctc_ref as _reference          # (per-row float64 torch ctc_loss: nll and gradient, None where torch cannot align)
 
 pytestmark = pytest.mark.gpu
 
@@ -36,26 +37,6 @@ def _labels(y, U, drop_row):
     if drop_row >= 0 and labs[drop_row]:
         labs[drop_row] = labs[drop_row][:-1]
     return labs
-
-
-def _reference(logits, labs, enc_len):
-    """per-row nll and d(sum nll)/d logits, float64 on the CPU; None for rows torch cannot align (nll = inf)."""
-    B, Tp, Vc = logits.shape
-    nll, grad = [], []
-    for b in range(B):
-        x = torch.tensor(logits[b:b + 1], dtype=torch.float64, requires_grad=True)
-        lp = torch.log_softmax(x, -1).transpose(0, 1)
-        tg = torch.tensor(labs[b] if labs[b] else [0], dtype=torch.long).reshape(1, -1)
-        l = F.ctc_loss(lp, tg, torch.tensor([int(enc_len[b])]), torch.tensor([len(labs[b])]), blank=Vc - 1, reduction="none",
-                       zero_infinity=False)
-        if not torch.isfinite(l).all():
-            nll.append(float("inf"))
-            grad.append(None)
-            continue
-        l.sum().backward()
-        nll.append(float(l[0]))
-        grad.append(x.grad[0].numpy())
-    return nll, grad
 
 
 def _run(logits, y, U, enc_len, drop_row, dtype=torch.float32, scale=1.0):
